@@ -11,7 +11,14 @@ configurations and `config.workload` says which one ran.  Frames (depth, mask) a
 region; poses stay on the host like any small per-frame metadata.  With N > 1 every rank owns one scene (its volumes
 + its own frame stream): no data-path collective, weak scaling, value = N*K / max-over-ranks time.
 
-Rank 0 prints ONE JSON line with the driver's contract fields plus
+A plain run does only what the headline needs: set-up, W warm-up steps, ONE timed loop of exactly K steps (no events
+inside it), the outputs if ``--dump-outputs DIR`` is given, and rank 0's JSON line with the contract fields (metric, value,
+unit, ms_per_step, higher_is_better, dtype, ...).  ``--dump-outputs DIR`` writes what a caller of the timed path holds after
+its last timed step - the scene's volumes (Database: TSDF, fusion weights, + semantic ids / scores) - as DIR/<name>.npy
+in float32, whole when small, else the same seeded sample of voxels on every run (<= 32 MB of volumes in all; with
+--train also the fusion net's state).  The inputs are seeded: the same arguments fuse the same frames with the same weights.
+
+``--full`` adds everything else, as follows.  Rank 0's line then also holds
   stages_ms            extract / net / integrate from fence-free HIP events on the launch stream, sampled on every 4th
                        frame INSIDE the timed region (an event record is a marker packet that idles the queue ~4.5 us)
   stages_ms_all_frames the same from a separate UNTIMED pass with events on every frame
@@ -26,8 +33,8 @@ Rank 0 prints ONE JSON line with the driver's contract fields plus
                        640x480 -> 512^3 (configs[4] size) without / with semantics, and the configs[3] TRAINING frame step
 
 Timing: after W warm-up steps the K-step timed loop (barrier + synchronize on both sides, max over ranks) is run
-``--repeats`` times (default 5) back to back; ``value`` / ``ms_per_step`` are the MEDIAN repeat, ``value_min`` / ``value_max``
-the slowest / fastest one (a single 9 ms region moves by a percent with one slow launch).
+``--repeats`` times (default 1; 5 with --full) back to back; ``value`` / ``ms_per_step`` are the MEDIAN repeat, ``value_min`` /
+``value_max`` the slowest / fastest one (a single 9 ms region moves by a percent with one slow launch).
 
 ``--train`` times BASELINE configs[3]'s frame step instead (train_fusion.py:145-189): fuse_training + FusionLoss + backward
 on every frame, and at every accumulation boundary (8 frames) the flat-gradient all-reduce over RCCL + the RMSprop step;
@@ -63,6 +70,38 @@ ARITH = {'f32': ('f32', 'f32-input MFMA (v_mfma_f32_16x16x4_f32)', F32_MFMA_PEAK
          'f16x3': ('f16x3', 'split-fp16: 3 x v_mfma_f32_16x16x32_f16 per product block, fp32 accumulate, fp32 activations',
                    F16_MFMA_PEAK_TF / 3.0)}
 DISTINCT_FRAMES = 64  # distinct synthetic frames kept resident per case (cycled when steps + warmup exceed it)
+DUMP_VOLUME_BYTES = 32 << 20  # --dump-outputs: float32 bytes of all dumped volumes together (the whole dump stays <= 64 MB)
+DUMP_SEED = 1911              # --dump-outputs: the voxel sample of a volume too large to dump whole
+
+
+def volume_outputs(db, scenes):
+    """The volumes a caller of the fuse path holds (Database: TSDF, fusion weights, semantic ids / scores) of
+    ``scenes`` = [(name prefix, scene)], as float32 host arrays: whole when they fit DUMP_VOLUME_BYTES, else the voxels at
+    the same sorted seeded flat indices in every volume and on every run."""
+    vols = {}
+    for prefix, s in scenes:
+        vols[prefix + 'tsdf'] = db.scenes_est[s].volume
+        vols[prefix + 'weights'] = db.fusion_weights[s]
+        if db.semantics:
+            vols[prefix + 'semantic_ids'] = db.ids_est[s].volume
+            vols[prefix + 'semantic_scores'] = db.scores[s].volume
+    n = torch.as_tensor(next(iter(vols.values()))).numel()
+    k = min(n, DUMP_VOLUME_BYTES // (4 * len(vols)))
+    idx = None if k == n else torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False)))
+    out = {}
+    for name, v in vols.items():
+        v = torch.as_tensor(v).reshape(-1)
+        out[name] = (v if idx is None else v[idx.to(v.device)]).float().cpu().numpy()
+    return out
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 / float64, at most 64 MB in all)."""
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()), {k: a.dtype for k, a in arrays.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20, sum(a.nbytes for a in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 class BenchStream(SyntheticStream):
@@ -87,6 +126,15 @@ def seeded_weights(pipe, seed=1911):
         if isinstance(m, torch.nn.BatchNorm2d):
             m.running_mean.normal_(0, 0.1)
             m.running_var.uniform_(0.5, 1.5)
+
+
+def seeded_pipeline(cfg, seed=1911):
+    """Pipeline(cfg) + seeded_weights: the seed also goes in front of the constructor, whose default initialisation (the conv
+    biases, the 2-D network) would otherwise differ from process to process."""
+    torch.manual_seed(seed)
+    pipe = Pipeline(cfg)
+    seeded_weights(pipe, seed)
+    return pipe
 
 
 def workload_name(c):
@@ -208,8 +256,7 @@ class Case:
         n_distinct = min(n_frames, DISTINCT_FRAMES)
         self.st = BenchStream(h, w, grid, max(n_distinct, 40), scene='room_%d' % rank, seed=1911 + rank, n_classes=c['n_classes'])
         self.db = Database(self.st, database_config(cfg))
-        pipe = Pipeline(cfg)
-        seeded_weights(pipe)
+        pipe = seeded_pipeline(cfg)
         self.pipe = pipe.to(dev).eval()
         self.dev = dev
         # frames resident in HBM before the clock starts; poses and ids stay host-side metadata
@@ -230,13 +277,18 @@ class Case:
     def fuse(self, i):
         self.pipe.fuse(self.batches[i % len(self.batches)], self.db, self.dev)
 
-    def run(self, steps, warmup, sync, profile_frames=32, kernel_reps=5, repeats=1):
+    def outputs(self):
+        return volume_outputs(self.db, [('', self.st.scene)])
+
+    def run(self, steps, warmup, sync, profile_frames=32, kernel_reps=5, repeats=1, marks=4, capture=False):
+        """``marks``: stage events on every marks-th frame of the timed region (False: none); ``capture``: res['outputs'] =
+        the volumes as the last timed step left them (before the untimed passes fuse more frames)."""
         pipe = self.pipe
         with torch.no_grad():
             pipe.profile = False
             for i in range(warmup):
                 self.fuse(i)
-            pipe.profile = 4  # stage events on every 4th frame of the timed region
+            pipe.profile = marks
             pipe.reset_profile()
             times = []
             at = warmup
@@ -250,6 +302,7 @@ class Case:
                 at += steps
             steps_done = at - warmup
             pipe.check()  # outside the timed region: raises if the split-fp16 range guard fired on any frame
+            outputs = self.outputs() if capture else None
             stages = pipe.stage_times_ms()
             n_samples = len(pipe._marks) // 4
             # separate UNTIMED pass: stage events on every frame
@@ -270,7 +323,7 @@ class Case:
             kernels = {name: {'launches_per_frame': n / reps, 'us_per_frame': us / reps} for name, (n, us) in table.items()}
             pipe.check()
         return {'times': times, 'stages': stages, 'stage_samples': n_samples, 'stages_all': stages_all,
-                'stages_all_frames': profile_frames, 'kernels': kernels, 'launches': pipe._engine.launches}
+                'stages_all_frames': profile_frames, 'kernels': kernels, 'launches': pipe._engine.launches, 'outputs': outputs}
 
 
 def run_lookahead(case, steps, warmup, sync, L, repeats=3, prefetch=True):
@@ -330,8 +383,7 @@ class ManyCase:
                    for k in range(S)]
         self.db = Database(ManyScenes(streams), database_config(cfg))
         self.streams0 = streams[0]
-        pipe = Pipeline(cfg)
-        seeded_weights(pipe)
+        pipe = seeded_pipeline(cfg)
         self.pipe = pipe.to(dev).eval()
         predict = c['semantics'] and c['strategy'] == 'predict'
         image = torch.zeros((1, 3, h, w), device=dev)
@@ -348,7 +400,10 @@ class ManyCase:
                 row.append(b)
             self.batches.append(row)
 
-    def run(self, steps, warmup, sync, repeats=3):
+    def outputs(self):
+        return volume_outputs(self.db, [('scene%d_' % k, s) for k, s in enumerate(self.db.scenes)])
+
+    def run(self, steps, warmup, sync, repeats=3, stage_pass=True, capture=False):
         times = []
         with torch.no_grad():
             for i in range(warmup):
@@ -365,18 +420,20 @@ class ManyCase:
                 times.append(time.perf_counter() - t0)
                 at += steps
             self.pipe.check()
+            self.captured = self.outputs() if capture else None
             # stage times of the joint launches (events around extract_many / integrate_many on every call of an untimed pass)
             stages = {}
-            try:
-                self.pipe.profile = True
-                self.pipe.reset_profile()
-                for i in range(at, at + 12):
-                    self.pipe.fuse_many(self.batches[i % len(self.batches)], self.db, self.dev)
-                stages = self.pipe.stage_times_ms()
-                self.pipe.profile = False
-                self.pipe.check()
-            except Exception as e:
-                stages = {'error': repr(e)}
+            if stage_pass:
+                try:
+                    self.pipe.profile = True
+                    self.pipe.reset_profile()
+                    for i in range(at, at + 12):
+                        self.pipe.fuse_many(self.batches[i % len(self.batches)], self.db, self.dev)
+                    stages = self.pipe.stage_times_ms()
+                    self.pipe.profile = False
+                    self.pipe.check()
+                except Exception as e:
+                    stages = {'error': repr(e)}
         self.host_ms_per_call = 1e3 * sorted(host)[len(host) // 2] / steps
         times.sort()
         med = times[len(times) // 2]
@@ -555,8 +612,7 @@ class TrainCase:
         n_distinct = min(n_frames, DISTINCT_FRAMES)
         self.st = SyntheticStream(h, w, grid, max(n_distinct, 40), scene='room_%d' % rank, seed=1911 + rank)
         self.db = Database(self.st, database_config(cfg))
-        pipe = Pipeline(cfg)
-        seeded_weights(pipe)  # the same on every rank (a replica), like train_fusion's broadcast initial state
+        pipe = seeded_pipeline(cfg)  # the same on every rank (a replica), like train_fusion's broadcast initial state
         self.pipe = pipe.to(dev).train()
         self.crit = FusionLoss(w_l1=cfg.TRAINING.loss.w_l1, w_l2=cfg.TRAINING.loss.w_l2, w_cos=cfg.TRAINING.loss.w_cos)
         self.grads = FlatGradientAllReduce(self.pipe._fusion_network)
@@ -604,6 +660,13 @@ class TrainCase:
                 self.opt.step()
                 self.grads.zero()
         self.pipe.gradient_work(gradient_step, join=boundary)  # like drivers.train_fusion: this thread waits only where the weights change
+
+    def outputs(self):
+        """The volumes and the fusion net's state (parameters + BatchNorm statistics, in state_dict order) after the last step."""
+        out = volume_outputs(self.db, [('', self.st.scene)])
+        state = [v.detach().reshape(-1).float() for v in self.pipe._fusion_network.state_dict().values() if v.is_floating_point()]
+        out['fusion_net_state'] = torch.cat(state).cpu().numpy()
+        return out
 
     def run(self, steps, warmup, sync, repeats):
         for i in range(warmup):
@@ -708,7 +771,13 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
-    ap.add_argument('--repeats', type=int, default=5, help='how many times the K-step timed loop runs; value = the median repeat')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='how many times the K-step timed loop runs (default 1; 5 with --full); value = the median repeat')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: stage events in the timed region, the untimed stage / per-kernel passes, '
+                         'roofline figures, the secondary workloads and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed path left after its last timed step as DIR/<name>.npy (float32, <= 64 MB)')
     ap.add_argument('--height', type=int, default=240)
     ap.add_argument('--width', type=int, default=320)
     ap.add_argument('--grid', type=int, default=256)
@@ -724,9 +793,9 @@ def main():
     ap.add_argument('--no-prefetch', action='store_true', help='with --lookahead: the next chunk is NOT announced to fuse_sequence (its 2-D pass then runs in front of its frame steps instead of beside the previous chunk\'s)')
     ap.add_argument('--lookahead', type=int, default=0, help='L > 1 (with --semantics --semantic-strategy predict): time Pipeline.fuse_sequence on chunks of L consecutive frames (prints its own line)')
     ap.add_argument('--scenes', type=int, default=0, help='S > 1: time Pipeline.fuse_many over S scenes on this GPU instead (prints its own line)')
-    ap.add_argument('--cpu-frames', type=int, default=10, help='timed frames of the CPU baseline (0 = skip)')
+    ap.add_argument('--cpu-frames', type=int, default=10, help='with --full: timed frames of the CPU baseline (0 = skip)')
     ap.add_argument('--secondary', type=int, default=None,
-                    help='steps of each secondary workload (default: 60 when the headline runs with default flags on 1 GPU, else 0)')
+                    help='with --full: steps of each secondary workload (default: 60 when the headline runs with default flags on 1 GPU, else 0)')
     ap.add_argument('--lean', action='store_true',
                     help='counter-collection runs (tools/final_profile.sh): only warm-up + timed frames are fused - no stage-mark '
                          'pass, no profiled forwards, no secondary / CPU legs - so every kernel runs exactly steps + warmup times per launch site')
@@ -736,6 +805,8 @@ def main():
                          'library load, communicator set-up and the collective launch of the 8-GPU path on a one-GPU box)')
     ap.add_argument('--no-pin', action='store_true', help='N > 1: do not pin the ranks to disjoint core sets')
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if args.gpus < 1 or args.steps < 1 or args.repeats < 1:
         raise SystemExit('bench.py: --gpus, --steps and --repeats must be positive')
 
@@ -805,11 +876,14 @@ def main():
                                                        mode='fast', arith='f16x3', n_classes=30)
     metric = 'frames/sec fused (%dx%d, %d^3 grid)' % (args.width, args.height, args.grid)
     total = args.warmup + args.steps * args.repeats
+    dump = args.dump_outputs is not None and rank == 0  # (rank 0 writes its own scene's outputs)
     if args.train:
         # (--dist-backend gloo: a dry run of the training schedule on one device - launch, barrier, accumulation boundary,
         # max over ranks; FlatGradientAllReduce stages the gradient buffer through the host for gloo, 'allreduce_backend' says so)
         tc = TrainCase(args.height, args.width, args.grid, dev, rank, total)
         res = tc.run(args.steps, args.warmup, sync, args.repeats)
+        if dump:
+            write_outputs(args.dump_outputs, tc.outputs())
         own = sorted(res['times'])[len(res['times']) // 2]
         rank_ms = [1e3 * t / args.steps for t in per_rank(own)]      # each rank's own median loop time per frame
         rank_host = per_rank(tc.host_ms_per_frame)
@@ -833,7 +907,9 @@ def main():
         return
     if args.scenes > 1:  # aggregate of S scenes on one GPU (a secondary measurement: the headline stays one scene per GPU)
         mc = ManyCase(head, dev, rank, total, args.scenes)
-        r = mc.run(args.steps, args.warmup, sync, args.repeats)
+        r = mc.run(args.steps, args.warmup, sync, args.repeats, stage_pass=args.full, capture=dump)
+        if dump:
+            write_outputs(args.dump_outputs, mc.captured)
         if rank == 0:
             print(json.dumps(dict(r, metric=metric + ', %d scenes per GPU (fuse_many)' % args.scenes, n_gpus=world)))
         if grouped:
@@ -842,6 +918,8 @@ def main():
     if args.lookahead > 1:
         case = Case(head, dev, rank, total + args.lookahead)
         r = run_lookahead(case, args.steps, args.warmup, sync, args.lookahead, args.repeats, prefetch=not args.no_prefetch)
+        if dump:
+            write_outputs(args.dump_outputs, case.outputs())
         if rank == 0:
             print(json.dumps(dict(r, metric=metric + ', %d-frame look-ahead of the 2-D network (fuse_sequence)' % args.lookahead, n_gpus=world)))
         if grouped:
@@ -849,7 +927,9 @@ def main():
         return
     case = Case(head, dev, rank, total)
     if args.lean:
-        res = case.run(args.steps, args.warmup, sync, profile_frames=0, kernel_reps=0, repeats=1)
+        res = case.run(args.steps, args.warmup, sync, profile_frames=0, kernel_reps=0, repeats=1, capture=dump)
+        if dump:
+            write_outputs(args.dump_outputs, res['outputs'])
         if rank == 0:
             r = report(case, res, args.steps, args.warmup, world, full=False)
             print(json.dumps({'metric': metric, 'value': r['value'],
@@ -858,11 +938,16 @@ def main():
         if grouped:
             torch.distributed.destroy_process_group()
         return
-    res = case.run(args.steps, args.warmup, sync, repeats=args.repeats)
+    if args.full:
+        res = case.run(args.steps, args.warmup, sync, repeats=args.repeats, capture=dump)
+    else:  # the headline only: no events inside the timed loop, no untimed stage / per-kernel passes
+        res = case.run(args.steps, args.warmup, sync, profile_frames=0, kernel_reps=0, repeats=args.repeats, marks=False, capture=dump)
     res['times'] = max_over_ranks(res['times'])
+    if dump:
+        write_outputs(args.dump_outputs, res['outputs'])
 
     if rank == 0:
-        r = report(case, res, args.steps, args.warmup, world)
+        r = report(case, res, args.steps, args.warmup, world, full=args.full)
         cfg = case.cfg
         out = {
             'metric': metric, 'value': r['value'], 'unit': 'frames/sec',
@@ -875,13 +960,16 @@ def main():
             'timing': 'median of %d back-to-back repeats of the %d-step timed loop (each bracketed by barrier + synchronize, max over ranks)'
                       % (args.repeats, args.steps),
         }
-        for k in ('repeats', 'value_min', 'value_max', 'stages_ms', 'stage_samples_in_timed_region', 'stages_ms_all_frames',
-                  'stages_all_frames_pass', 'net_launches_per_frame', 'kernels', 'segmentation', 'roofline', 'roofline_net', 'roofline_hbm'):
+        keys = ('repeats', 'value_min', 'value_max', 'net_launches_per_frame')
+        if args.full:
+            keys += ('stages_ms', 'stage_samples_in_timed_region', 'stages_ms_all_frames', 'stages_all_frames_pass', 'kernels', 'segmentation',
+                     'roofline', 'roofline_net', 'roofline_hbm')
+        for k in keys:
             if k in r:
                 out[k] = r[k]
         del case
         torch.cuda.empty_cache()
-        n_sec = args.secondary if args.secondary is not None else (60 if (world == 1 and default_flags) else 0)
+        n_sec = 0 if not args.full else args.secondary if args.secondary is not None else (60 if (world == 1 and default_flags) else 0)
         if world == 1 and n_sec > 0:
             secondary = []
             for extra in (dict(arith='f32'),
@@ -931,7 +1019,7 @@ def main():
             torch.cuda.empty_cache()
             secondary.append(rccl_world1_probe())
             out['secondary'] = secondary
-        if world == 1 and args.cpu_frames > 0:
+        if args.full and world == 1 and args.cpu_frames > 0:
             out['cpu_baseline'] = cpu_baseline(args, args.height, args.width, args.grid, args.semantics)
             out['speedup_vs_cpu_baseline'] = out['value'] / out['cpu_baseline']['value']
         print(json.dumps(out))

@@ -26,13 +26,38 @@ def _bench(*flags, timeout=600):
 
 
 def test_single_gpu_line_has_contract_fields_and_repeats(cuda):
-    out = _bench('--steps', '6', '--warmup', '3', '--repeats', '3', *SMALL)
+    out = _bench('--full', '--steps', '6', '--warmup', '3', '--repeats', '3', *SMALL)
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline',
               'dtype', 'data', 'config', 'roofline', 'roofline_net', 'roofline_hbm', 'kernels'):
         assert k in out, k
     assert out['n_gpus'] == 1 and out['steps'] == 6 and out['warmup'] == 3 and out['repeats'] == 3
     assert out['value_min'] <= out['value'] <= out['value_max']
     assert abs(out['value'] * out['ms_per_step'] / 1e3 - 1.0) < 1e-6
+
+
+def test_plain_run_times_one_loop_of_steps_and_dumps_the_same_outputs_twice(cuda, tmp_path):
+    """A plain run: one timed loop of exactly --steps frames, the contract fields and nothing that needs passes of its own;
+    --dump-outputs writes the volumes the last timed step left (float32, <= 64 MB), the same on every run of the same arguments."""
+    import numpy as np
+    flags = ['--steps', '5', '--warmup', '2', '--height', '120', '--width', '160', '--grid', '64']
+    a = _bench(*flags, '--dump-outputs', str(tmp_path / 'a'))
+    for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'dtype'):
+        assert k in a, k
+    assert a['steps'] == 5 and a['warmup'] == 2 and a['repeats'] == 1 and a['unit'] == 'frames/sec' and a['higher_is_better'] is True
+    assert abs(a['value'] * a['ms_per_step'] / 1e3 - 1.0) < 1e-6
+    for k in ('stages_ms', 'kernels', 'roofline', 'roofline_hbm', 'secondary', 'cpu_baseline'):
+        assert k not in a, k
+    _bench(*flags, '--dump-outputs', str(tmp_path / 'b'))
+    names = sorted(os.listdir(str(tmp_path / 'a')))
+    assert names == ['tsdf.npy', 'weights.npy'] and sorted(os.listdir(str(tmp_path / 'b'))) == names
+    total = 0
+    for n in names:
+        x, y = np.load(str(tmp_path / 'a' / n)), np.load(str(tmp_path / 'b' / n))
+        assert x.dtype == np.float32 and x.shape == (64 ** 3,)
+        total += x.nbytes
+        np.testing.assert_array_equal(x, y)
+    assert total <= 64 << 20
+    assert (np.load(str(tmp_path / 'a' / 'weights.npy')) > 0).sum() > 1000  # frames were fused into the dumped volume
 
 
 def test_gpus_2_launches_its_own_ranks_over_gloo_on_one_device(cuda):

@@ -1,6 +1,6 @@
 """Helper: run bench.py with the given args and print a one-line summary."""
 import json, subprocess, sys, os
-out = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'bench.py')] + sys.argv[1:],
+out = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'bench.py'), '--full'] + sys.argv[1:],
                      capture_output=True, text=True)
 line = [l for l in out.stdout.splitlines() if l.startswith('{')]
 if not line:
