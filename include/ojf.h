@@ -528,6 +528,23 @@ int ojf_points_within(const double *query_dev, size_t n_query, const double *poi
                       const uint32_t *cell_start_dev, const double *grid_origin_host, double cell_size, int GX, int GY,
                       int GZ, double tau, uint8_t *hit_dev, uint32_t *n_hit_dev, ojf_stream_t stream);
 
+/* ---- RENDER (ray casting of a fused volume; no counterpart in the reference's hot path) ---------------------------
+ * ojf_render: depth, normal and label images of n views (1 <= n <= OJF_RENDER_MAX_VIEWS, one h x w for all) of the
+ *   volume tsdf_dev fp16[X,Y,Z] (X, Y, Z >= 2), KinectFusion-style: each pixel's ray marches from max(box entry, near)
+ *   through the trilinear support box of the voxel centres (origin + (i+0.5)*resolution, the frame of extract /
+ *   integrate) with steps of max(0.5*resolution, 0.75*max(F,0)) along the ray, and stops at the first sign change
+ *   from F > 0 to F <= 0 between two samples whose 8 corners are observed (weights_dev NULL: all are); the hit is the
+ *   linear crossing of those two samples.  Kinv_host f32[n][9], E_host f32[n][12] as for ojf_extract; the ray
+ *   parameter is the camera z-depth.  Outputs: depth_dev f32[n,h,w] = z-depth of the hit; normals_dev (or NULL)
+ *   f32[n,h,w,3] = normalised central difference (+-1 voxel) of the interpolated TSDF at the hit, world frame, pointing
+ *   to free space; labels_dev (or NULL; needs ids_dev) u8[n,h,w] = ids_dev at the voxel that contains the hit.  A miss
+ *   writes 0 to all three.  Every output element is written once, no atomics: deterministic, the same bits for any n.
+ *   The exact fp32 operation order is in csrc/ojf_render.hip. */
+#define OJF_RENDER_MAX_VIEWS 64
+int ojf_render(const uint16_t *tsdf_dev, const uint16_t *weights_dev, const uint8_t *ids_dev, int X, int Y, int Z,
+               const double *origin_host, double resolution, int n, const float *Kinv_host, const float *E_host, int h,
+               int w, float near, float *depth_dev, float *normals_dev, uint8_t *labels_dev, ojf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

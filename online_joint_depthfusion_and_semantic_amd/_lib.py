@@ -42,6 +42,7 @@ _c = ctypes
 _vp, _i, _f, _d, _sz = _c.c_void_p, _c.c_int, _c.c_float, _c.c_double, _c.c_size_t
 
 MAX_SCENES = 8  # include/ojf.h OJF_MAX_SCENES
+RENDER_MAX_VIEWS = 64  # include/ojf.h OJF_RENDER_MAX_VIEWS
 
 
 class ExtractJob(ctypes.Structure):
@@ -146,6 +147,7 @@ SIGNATURES = {
     'ojf_points_within': (_i, [_vp, _sz, _vp, _vp, _vp, _d, _i, _i, _i, _d, _vp, _vp, _vp]),
     'ojf_mesh_workspace_bytes': (_sz, [_i, _i, _i]),
     'ojf_mesh_extract': (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _d, _vp, _sz, _vp, _vp, _vp, _c.c_uint32, _vp, _vp]),
+    'ojf_render': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _d, _i, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
 }
 
 _LIB = None

@@ -257,6 +257,17 @@ class Database(torch.utils.data.Dataset):
                               resolution=float(self.resolution[scene_id]), palette=palette)
         return m['vertices'], m['faces'], m['normals'], m['rgb']
 
+    def render(self, scene_id, intrinsics, extrinsics, shape, semantics=False, normals=True):
+        """Ray-cast the estimated volume of a scene at one or more camera poses (render.py): {'depth', 'normals',
+        'labels'} device tensors of [n,h,w](,3), 0 where a ray hits nothing.  Unobserved voxels (fusion weight 0) are
+        transparent; semantics=True labels every hit with ids_est.  Works on resident and on host (to_numpy) state."""
+        from . import render
+        tsdf = self._device_volume(self.scenes_est[scene_id].volume, torch.float16)
+        w = self._device_volume(self.fusion_weights[scene_id], torch.float16)
+        ids = self._device_volume(self.ids_est[scene_id].volume, torch.uint8) if semantics else None
+        return render.render_views(tsdf, w, ids, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]),
+                                   intrinsics=intrinsics, extrinsics=extrinsics, shape=shape, normals=normals)
+
     def save_to_workspace(self, workspace, mode, save_mode='ply'):
         """database.py:141-177: every scene that holds integrated frames goes to the workspace's output directory as
         ``<scene>.tsdf_<mode>.hf5`` / ``.weights_<mode>.hf5`` / ``.semantic_<mode>.hf5`` ('tsdf'), ``<scene>_<mode>.ply``
