@@ -231,12 +231,16 @@ int ojf_segdeconv_create(ojf_segconv **out, const float *weight_host, const floa
 void ojf_segconv_destroy(ojf_segconv *conv);
 /* The reference's multi-scale units end in `nn.Dropout(p=0.5)(out)` on a module constructed inside forward(), i.e.
  * ALWAYS in training mode (modules/adapnet.py:80-82): activations are dropped at inference too.  With a state set, the
- * launches of this layer apply that dropout in their epilogue (after residual + ReLU): element e of the layer is kept
- * (and doubled) iff bit 0 of Philox-4x32-10(counter = {e / 4, stream_id, frame}, key = seed) word e % 4 is set, with
- * rng_state_dev = {seed, frame} (two u64 in device memory, owned by the caller).  The masks are a pure function of
- * (seed, frame, stream_id, e): deterministic, graph-replayable, a fresh draw per frame.  advance != 0 instead marks
- * the layer whose launch increments `frame` (the LAST convolution of a forward pass; no dropout there).
- * rng_state_dev == NULL switches both off.  (torch's own generator is not consumed: seed it from torch.initial_seed().) */
+ * launches of this layer apply that dropout in their epilogue, last (after residual, activation and gate), with
+ * rng_state_dev = {seed, frame} (two u64 in device memory, owned by the caller, read at launch time).  Output element
+ * (p, c) - pixel p = (b * Ho + y) * Wo + x (batch-major, row-major), channel c < c_out - is kept iff bit 0 of word c % 4
+ * of Philox-4x32-10(counter = {p * ceil(c_out / 4) + c / 4, stream_id, frame & 0xffffffff, frame >> 32},
+ * key = {seed & 0xffffffff, seed >> 32}) is set (the first word of the counter modulo 2^32).  A kept value v becomes
+ * v + v, a dropped one +0.0; pad channels stay 0.  The masks are a pure function of (seed, frame, stream_id, p, c):
+ * deterministic, graph-replayable, a fresh draw per frame.  Members of a grouped launch draw with their own stream ids;
+ * either every member drops or none does.  advance != 0 instead marks the layer whose launch adds 1 to `frame` (the LAST
+ * convolution of a forward pass; no dropout there; member 0 only in a grouped launch).  rng_state_dev == NULL switches
+ * both off.  Not for transposed convolutions.  (torch's own generator is not consumed: seed it from torch.initial_seed().) */
 int ojf_segconv_set_dropout(ojf_segconv *conv, const unsigned long long *rng_state_dev, unsigned stream_id, int advance);
 int ojf_segconv_forward(const ojf_segconv *conv, const float *in_dev, int in_stride, float *out_dev, int out_stride,
                         const float *res_dev, int res_stride, const float *mul_dev, int mul_stride, int act, int h,

@@ -259,7 +259,8 @@ __device__ __forceinline__ void seg_epilogue_px(const SegArgs &a, const f32x4 (&
                 }
             }
             if constexpr (DROP) {  // nn.Dropout(p = 0.5) in training mode, always (adapnet.py:80-82): keep with probability 1/2, scale by 2
-                const unsigned e = (unsigned)p * (unsigned)(a.c_out >> 2) + (unsigned)(c >> 2);
+                // counter = (pixel, 4-channel group) with ceil(c_out / 4) groups per pixel: a partial last group has its own
+                const unsigned e = (unsigned)p * (unsigned)((a.c_out + 3) >> 2) + (unsigned)(c >> 2);
                 const uint4 r = philox4x32_10(uint4{e, a.drop_id, (unsigned)frame, (unsigned)(frame >> 32)},
                                               uint2{(unsigned)seed, (unsigned)(seed >> 32)});
                 v[0] = (r.x & 1u) ? v[0] + v[0] : 0.0f;
@@ -1458,6 +1459,9 @@ unsigned seg_map(SegMap &m, int X, int Y, int Z)
 // n members of one shape (the first one's n_kb / n_ct / output size decide the launch)
 int seg_launch(SegGroupArgs &g, int n, hipStream_t st)
 {
+    // the counter is bumped by thread 0 of block 0, which belongs to member 0: another member's bump would be lost
+    for (int i = 1; i < n; ++i)
+        if (g.a[i].rng_bump) return fail("ojf_segconv launch: only member 0 of a grouped launch may advance the frame counter");
     g.het.n = 0;
     static const int abl = getenv("OJF_SEG_ABL") ? atoi(getenv("OJF_SEG_ABL")) : 0;  // tuning only
     g.abl = abl;
@@ -1614,7 +1618,7 @@ int seg_launch(SegGroupArgs &g, int n, hipStream_t st)
         if (mw == 1) hipLaunchKernelGGL((segconv_kernel<1, 1, 1, 4, 3, true>), dim3(seg_map(g.map, n_pt, a.n_ct, n)), dim3(256), 0, st, g);
         else if (mw == 2) hipLaunchKernelGGL((segconv_kernel<2, 1, 1, 4, 3, true>), dim3(seg_map(g.map, n_pt, a.n_ct / 2, n)), dim3(256), 0, st, g);
         else hipLaunchKernelGGL((segconv_kernel<4, 1, 1, 4, 3, true>), dim3(seg_map(g.map, n_pt, groups, n)), dim3(256), 0, st, g);
-        variant = "<*,1,1,4> drop";
+        variant = mw == 1 ? "<1,1,1,4> drop" : (mw == 2 ? "<2,1,1,4> drop" : "<4,1,1,4> drop");
     } else if (!no_wide && a.n_kb >= 6 && (long)groups * ((n_pt + 7) / 8) * n >= wide_min) {
         variant = use_tile ? "tile<2>" : "wide<2>";
         if (use_tile && tile_u == 4) hipLaunchKernelGGL((segconv_tile_kernel<2, 4>), dim3(seg_map(g.map, (n_pt + 7) / 8, groups, n)), dim3(256), 0, st, g);
@@ -1797,7 +1801,7 @@ OJF_API int ojf_segconv_forward_group_batch(int n, int batch, const ojf_segconv 
                               muls ? muls[i] : nullptr, mul_stride, act, h, w, g.a[i])) return rc;
         const SegArgs &a = g.a[i], &b = g.a[0];
         if (a.n_kb != b.n_kb || a.n_ct != b.n_ct || a.c8 != b.c8 || a.c_out != b.c_out || a.ksize != b.ksize || a.stride != b.stride ||
-            a.Ho != b.Ho || a.Wo != b.Wo || a.up != b.up || (i > 0 && a.rng_bump))
+            a.Ho != b.Ho || a.Wo != b.Wo || a.up != b.up)
             return fail("ojf_segconv_forward_group: the members must share channels, kernel size, stride and output size");
     }
     return seg_launch(g, n, as_stream(stream));

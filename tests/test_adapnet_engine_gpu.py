@@ -40,11 +40,11 @@ def lively(net, seed=0, dropout=False):
     return net
 
 
-def build(stage, n_classes, seed=0):
+def build(stage, n_classes, seed=0, dropout=False):
     from online_joint_depthfusion_and_semantic_amd.adapnet import AdapNet
     from online_joint_depthfusion_and_semantic_amd.config import AttrDict
     torch.manual_seed(seed)
-    return lively(AdapNet(AttrDict({'stage': stage, 'n_classes': n_classes})), seed).cuda().eval()
+    return lively(AdapNet(AttrDict({'stage': stage, 'n_classes': n_classes})), seed, dropout).cuda().eval()
 
 
 @pytest.mark.parametrize('stage,n_classes,h,w', [(2, 30, 64, 96), (1, 12, 48, 64), (2, 40, 240, 320), (2, 40, 480, 640), (1, 5, 16, 16)])
@@ -175,3 +175,144 @@ def test_predict_many_equals_predict_per_frame():
             assert (scores[b] - s1).abs().max().item() <= 1e-6
             assert (ids[b] == i1).float().mean().item() >= 0.9995
     assert scores.shape == (B, h * w) and ids.dtype == torch.uint8
+
+
+# ---- the always-on dropout against the module with the restatement's masks (tests/dropout_ref.py) ------------------------
+def unit_pairs(net, eng):
+    """(module, engine unit) of every residual unit of every encoder."""
+    encs = [(net.encoder_mod1, eng.enc1)] + ([(net.encoder_mod2, eng.enc2)] if eng.fusion else [])
+    pairs = []
+    for mod, enc in encs:
+        r = mod.res_n50_enc
+        for li, layer in enumerate((r.layer1, r.layer2, r.layer3, r.layer4)):
+            assert len(layer) == len(enc.layers[li])
+            pairs += [(m, enc.layers[li][ui]) for ui, m in enumerate(layer)]
+    return pairs
+
+
+def module_with_masks(net, eng, args, seed, frame):
+    """net(*args)[0] with every dropping unit's F.dropout replaced by the restatement's masks for (seed, frame, the engine
+    unit's stream id): output x 2 x mask."""
+    from dropout_ref import keep_mask_nchw
+    hooks, units = [], []
+    for m, u in unit_pairs(net, eng):
+        if getattr(m, 'dropout', False) is True:
+            units.append(m)
+            m.dropout = False
+
+            def hook(module, inputs, out, sid=u.drop_id):
+                keep = keep_mask_nchw(seed, frame, sid, *out.shape)
+                return out * torch.from_numpy(2.0 * keep).to(out.device, out.dtype)
+            hooks.append(m.register_forward_hook(hook))
+    try:
+        with torch.no_grad():
+            return net(*args)[0]
+    finally:
+        for h in hooks:
+            h.remove()
+        for m in units:
+            m.dropout = True
+
+
+def lively_inputs(stage, h, w, batch=1, seed=5):
+    g = torch.Generator().manual_seed(seed)
+    img = torch.randn((batch, 3, h, w), generator=g).cuda()
+    dep = (torch.rand((batch, 3, h, w), generator=g) * 3).cuda()
+    return (img, dep) if stage != 1 else (img,)
+
+
+@pytest.mark.parametrize('stage,n_classes,h,w,state', [(2, 30, 64, 96, (0x0123456789abcdef, (3 << 32) | 0xfffffffe)),
+                                                       (2, 40, 240, 320, (-0x1234567890abcdef, (1 << 32) | 7)),
+                                                       (1, 12, 48, 64, (0x7edcba9876543210, 0xffffffff))])
+def test_engine_dropout_matches_module_with_restated_masks(stage, n_classes, h, w, state):
+    """SegEngine with every multi-scale unit dropping == the module forward with each unit's dropout replaced by the
+    restatement's masks for the engine's (seed, frame, stream id); one counter step per pass.  The masks of the next frame
+    miss by far more than the bar."""
+    from online_joint_depthfusion_and_semantic_amd.adapnet_engine import SegEngine
+    net = build(stage, n_classes, dropout=True)
+    args = lively_inputs(stage, h, w)
+    with torch.no_grad():
+        eng = SegEngine(net)
+        pairs = unit_pairs(net, eng)
+        ids = [u.drop_id for _, u in pairs]
+        assert len(set(ids)) == len(ids)  # a stream per unit and encoder
+        dropping = [m for m, _ in pairs if getattr(m, 'dropout', False) is True]
+        assert len(dropping) == 8 * (2 if stage != 1 else 1)  # layer2[-1], layer3[2..5], layer4[0..2] per encoder
+        eng.rng.copy_(torch.tensor(state, dtype=torch.int64))
+        seed, frame = eng.rng.tolist()
+        got = eng(*args)
+        torch.cuda.synchronize()
+        assert eng.rng.tolist() == [seed, frame + 1]
+    want = module_with_masks(net, eng, args, seed, frame)
+    top = want.abs().max().item()
+    assert 1e-2 < top < 1e4
+    err = (got - want).abs().max().item()
+    assert err <= 5e-4 * top, (err, top)
+    assert (got.argmax(1) == want.argmax(1)).float().mean().item() > 0.999
+    wrong = module_with_masks(net, eng, args, seed, frame + 1)
+    assert (got - wrong).abs().max().item() > 40 * 5e-4 * top  # the comparison sees the masks
+
+
+def test_engine_dropout_batch_is_one_pass_numbered_batch_major():
+    """eng.forward on 3 images: one pass, one counter step, masks over the batch-major pixel index."""
+    from online_joint_depthfusion_and_semantic_amd import segconv
+    from online_joint_depthfusion_and_semantic_amd.adapnet_engine import SegEngine
+    net = build(2, 30, dropout=True)
+    args = lively_inputs(2, 64, 96, batch=3, seed=6)
+
+    def packed(x):  # the stem's rows of every image: [B, 8, H, W] NHWC
+        out = segconv.nhwc(8, x.shape[2], x.shape[3], x.device, batch=x.shape[0])
+        for b in range(x.shape[0]):
+            segconv.pack_input(x[b:b + 1].contiguous(), 1.0, out=out[b:b + 1])
+        return out
+    with torch.no_grad():
+        eng = SegEngine(net)
+        eng.rng.copy_(torch.tensor([0x5eed0000cafe1234, (9 << 32) | 1], dtype=torch.int64))
+        seed, frame = eng.rng.tolist()
+        got = eng(*[packed(a) for a in args])
+        torch.cuda.synchronize()
+        assert eng.rng.tolist() == [seed, frame + 1]
+    want = module_with_masks(net, eng, args, seed, frame)
+    top = want.abs().max().item()
+    assert (got - want).abs().max().item() <= 5e-4 * top
+    assert (got.argmax(1) == want.argmax(1)).float().mean().item() > 0.999
+    # image 1 alone draws the masks of pixels 0.. (not H*W..): it differs from its slice of the batch
+    alone = module_with_masks(net, eng, [a[1:2] for a in args], seed, frame)
+    assert (got[1:2] - alone).abs().max().item() > 40 * 5e-4 * top
+
+
+def test_engine_dropout_graph_replay_advances_and_matches_eager():
+    """A captured forward pass: each replay adds one to the counter and equals, bit for bit, an eager pass run after
+    resetting the counter to the replay's frame; consecutive replays draw different masks."""
+    from online_joint_depthfusion_and_semantic_amd.adapnet_engine import SegEngine
+    net = build(2, 30, dropout=True)
+    args = lively_inputs(2, 64, 96, seed=7)
+    with torch.no_grad():
+        eng = SegEngine(net)
+        eng.rng.copy_(torch.tensor([-0x0fedcba987654321, (2 << 32) | 0xfffffffc], dtype=torch.int64))
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                eng(*args)
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out = eng(*args)
+        torch.cuda.synchronize()
+        seed, frame = eng.rng.tolist()
+        prev = None
+        for _ in range(3):
+            graph.replay()
+            torch.cuda.synchronize()
+            assert eng.rng.tolist() == [seed, frame + 1]
+            rep = out.clone()
+            eng.rng[1] = frame
+            eager = eng(*args)
+            torch.cuda.synchronize()
+            assert eng.rng.tolist() == [seed, frame + 1]
+            assert torch.equal(rep, eager)
+            if prev is not None:
+                assert not torch.equal(rep, prev)
+            prev, frame = rep, frame + 1
+    assert frame >> 32 == 3  # the replays carried into the high word
