@@ -549,6 +549,43 @@ int ojf_render(const uint16_t *tsdf_dev, const uint16_t *weights_dev, const uint
                const double *origin_host, double resolution, int n, const float *Kinv_host, const float *E_host, int h,
                int w, float near, float *depth_dev, float *normals_dev, uint8_t *labels_dev, ojf_stream_t stream);
 
+/* ---- TRACK (camera pose of a depth frame against the fused model; no counterpart in the reference) -----------------
+ * Frame-to-model projective point-to-plane ICP, KinectFusion-style, against ojf_render images of the model at a reference
+ *   pose.  Levels l = 0..levels-1 (1 <= levels <= OJF_TRACK_MAX_LEVELS; level l is (h>>l) x (w>>l), every level at least
+ *   8 x 8), coarsest first.  depth_dev f32[h*w] (0, negative or non-finite: no depth), mask_dev u8[h*w] or NULL;
+ *   K_host f64[9] the level-0 intrinsics (fx_l = fx/2^l, cx_l = (cx+0.5)/2^l - 0.5, likewise y); Kinv_host f32[levels][9]
+ *   the inverses the model images were rendered with (fp32(K_l).inverse()); model_depth_host / model_normals_host: host
+ *   arrays of `levels` device pointers to the level's ojf_render depth f32[h_l*w_l] and world normals f32[h_l*w_l*3] at
+ *   E_ref_host f64[12] (camera-to-world, 3x4 row-major); E_init_host f64[12] the starting pose; iterations_host
+ *   int[levels] per level (>= 0, sum <= OJF_TRACK_MAX_ITERATIONS); dist_thresh (m), angle_thresh_deg, pyramid_delta (m),
+ *   min_inlier_fraction of a level's pixels.  workspace_dev: >= ojf_track_workspace_bytes(h, w, levels) bytes of device
+ *   memory; its first bytes hold the depth pyramid, level after level, f32 row-major.
+ *   Outputs: pose_dev f64[12] the tracked camera-to-world pose; stats_dev f64[sum(iterations)][4] per iteration (inlier
+ *   count, mean squared residual, |omega|, |tau|); status_dev int[2] {0 | 1 too few inliers | 2 singular system |
+ *   3 non-finite step, iteration of the failure or -1}.  After a failure pose_dev holds E_init.  Enqueues
+ *   1 + 2*sum(iterations) kernels on `stream` and never waits.  The exact fp32 / fp64 definition is in csrc/ojf_track.hip.
+ * ojf_track_associate: one association + solve step at `level` from the pose E_pose_host (the pyramid up to that level is
+ *   built in the workspace, sized ojf_track_workspace_bytes(h, w, level + 1)): pose_dev receives the updated pose,
+ *   sums_dev f64[OJF_TRACK_TERMS] the reduced terms (21 upper-triangle J_i*J_j, 6 J_i*r, r*r, count), jr_dev (or NULL)
+ *   f32[h_l*w_l][7] = (J_0..J_5, r) of every pixel (0 for outliers), reason_dev (or NULL) u8[h_l*w_l] its reason code
+ *   (0 inlier, 1 no depth, 2 no normal, 3 behind the reference camera, 4 outside the model image, 5 no model depth,
+ *   6 too far, 7 normals disagree), status_dev int[2] as above.  For tests and diagnostics. */
+#define OJF_TRACK_MAX_LEVELS 4
+#define OJF_TRACK_MAX_ITERATIONS 128
+#define OJF_TRACK_TERMS 29
+size_t ojf_track_workspace_bytes(int h, int w, int levels);
+int ojf_track(const float *depth_dev, const uint8_t *mask_dev, int h, int w, int levels, const double *K_host,
+              const float *Kinv_host, const float *const *model_depth_host, const float *const *model_normals_host,
+              const double *E_ref_host, const double *E_init_host, const int *iterations_host, double dist_thresh,
+              double angle_thresh_deg, double pyramid_delta, double min_inlier_fraction, void *workspace_dev,
+              size_t workspace_bytes, double *pose_dev, double *stats_dev, int *status_dev, ojf_stream_t stream);
+int ojf_track_associate(const float *depth_dev, const uint8_t *mask_dev, int h, int w, int level, const double *K_host,
+                        const float *Kinv_host, const float *model_depth_dev, const float *model_normals_dev,
+                        const double *E_ref_host, const double *E_pose_host, double dist_thresh, double angle_thresh_deg,
+                        double pyramid_delta, double min_inlier_fraction, void *workspace_dev, size_t workspace_bytes,
+                        double *pose_dev, double *sums_dev, float *jr_dev, uint8_t *reason_dev, int *status_dev,
+                        ojf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

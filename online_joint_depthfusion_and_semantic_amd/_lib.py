@@ -43,6 +43,9 @@ _vp, _i, _f, _d, _sz = _c.c_void_p, _c.c_int, _c.c_float, _c.c_double, _c.c_size
 
 MAX_SCENES = 8  # include/ojf.h OJF_MAX_SCENES
 RENDER_MAX_VIEWS = 64  # include/ojf.h OJF_RENDER_MAX_VIEWS
+TRACK_MAX_LEVELS = 4  # include/ojf.h OJF_TRACK_MAX_LEVELS
+TRACK_MAX_ITERATIONS = 128  # include/ojf.h OJF_TRACK_MAX_ITERATIONS
+TRACK_TERMS = 29  # include/ojf.h OJF_TRACK_TERMS
 
 
 class ExtractJob(ctypes.Structure):
@@ -148,6 +151,14 @@ SIGNATURES = {
     'ojf_mesh_workspace_bytes': (_sz, [_i, _i, _i]),
     'ojf_mesh_extract': (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _d, _vp, _sz, _vp, _vp, _vp, _c.c_uint32, _vp, _vp]),
     'ojf_render': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _d, _i, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    'ojf_track_workspace_bytes': (_sz, [_i, _i, _i]),
+    # depth, mask, h, w, levels, K, Kinv, model depth[], model normals[], E_ref, E_init, iterations, dist, angle, delta,
+    # min_inlier_fraction, workspace, workspace_bytes, pose, stats, status, stream
+    'ojf_track': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _vp, _sz, _vp, _vp, _vp, _vp]),
+    # depth, mask, h, w, level, K, Kinv, model depth, model normals, E_ref, E_pose, dist, angle, delta, min_inlier_fraction,
+    # workspace, workspace_bytes, pose, sums, jr, reason, status, stream
+    'ojf_track_associate': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _vp, _sz, _vp, _vp, _vp,
+                                 _vp, _vp, _vp]),
 }
 
 _LIB = None

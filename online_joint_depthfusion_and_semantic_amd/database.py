@@ -59,6 +59,7 @@ class Database(torch.utils.data.Dataset):
         self.origin, self.resolution = {}, {}
         self.scenes_gt, self.scenes_est, self.fusion_weights = {}, {}, {}
         self.ids_gt, self.ids_est, self.scores = {}, {}, {}
+        self.tracked_poses = {}  # frame_id -> f64 [4,4] camera-to-world: frames fused with a tracked pose (drivers.test_fusion)
 
         for s in dataset.scenes:
             self.scenes.append(s)
@@ -267,6 +268,18 @@ class Database(torch.utils.data.Dataset):
         ids = self._device_volume(self.ids_est[scene_id].volume, torch.uint8) if semantics else None
         return render.render_views(tsdf, w, ids, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]),
                                    intrinsics=intrinsics, extrinsics=extrinsics, shape=shape, normals=normals)
+
+    def track(self, scene_id, depth, intrinsics, extrinsics, reference_extrinsics=None, **kw):
+        """Camera pose of a depth frame against the estimated volume of a scene (tracking.py, frame-to-model ICP):
+        tracking starts at ``extrinsics`` and the model is ray-cast at ``reference_extrinsics`` (default: the same pose);
+        ``kw`` goes to ``tracking.track_frame`` (mask, levels, iterations, thresholds).  Unobserved voxels are transparent.
+        Returns {'extrinsics' f64 [4,4], 'ok', 'status', 'stats'}.  Works on resident and on host (to_numpy) state."""
+        from . import tracking
+        tsdf = self._device_volume(self.scenes_est[scene_id].volume, torch.float16)
+        w = self._device_volume(self.fusion_weights[scene_id], torch.float16)
+        return tracking.track_frame(tsdf, w, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]),
+                                    depth=depth, intrinsics=intrinsics, extrinsics=extrinsics,
+                                    reference_extrinsics=reference_extrinsics, **kw)
 
     def save_to_workspace(self, workspace, mode, save_mode='ply'):
         """database.py:141-177: every scene that holds integrated frames goes to the workspace's output directory as

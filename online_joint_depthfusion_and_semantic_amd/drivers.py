@@ -124,11 +124,28 @@ def test_fusion(config, dataset, device, rank=0, world=1, state_dict=None, log=p
     # semantic_strategy 'predict': the 2-D network does not depend on the volumes, so the labels of TESTING.lookahead (default 8: 1075 frames/s against 940 at 4 and 511 frame at a time)
     # consecutive frames are predicted as one batched pass (Pipeline.fuse_sequence); the frame steps themselves stay in order
     lookahead = int(config.TESTING.get('lookahead', 8)) if (config.DATA.semantics and config.DATA.semantic_strategy == 'predict') else 1
+    # TESTING.track_invalid_poses: a frame without a finite pose is tracked against its scene's volume (tracking.py) from the
+    # last pose fused into that scene, and fused with the tracked pose; off (the default), such frames are skipped
+    track = bool(config.TESTING.get('track_invalid_poses', False))
+    last_pose = {}  # scene -> f64 [4,4] of the last frame fused into it (only kept when tracking)
     with torch.no_grad():
         chunk, ahead = [], None  # `ahead`: the chunk in front of `chunk`, fused once `chunk` is complete (its 2-D pass then runs beside ahead's frame steps)
         for batch in _loader(dataset, shard.scenes):
             if not torch.all(torch.isfinite(batch['extrinsics'])):
-                continue
+                if not track:
+                    continue
+                if ahead is not None:  # the tracker must see every earlier frame
+                    pipeline.fuse_sequence(ahead, database, device, prefetch=chunk or None)
+                    ahead = None
+                if chunk:
+                    pipeline.fuse_sequence(chunk, database, device)
+                    chunk = []
+                batch = _tracked_batch(batch, database, config, last_pose, log)
+                if batch is None:
+                    continue
+            if track:
+                E = batch['extrinsics'][0].to(torch.float64).reshape(-1, 4)
+                last_pose[batch['frame_id'][0].split('/')[0]] = np.concatenate([E[:3].numpy(), [[0.0, 0.0, 0.0, 1.0]]])
             if lookahead <= 1:
                 pipeline.fuse(_host_pose_batch(batch, device), database, device)
                 continue
@@ -179,6 +196,28 @@ def test_fusion(config, dataset, device, rank=0, world=1, state_dict=None, log=p
         for scene_id in database.scenes_est.keys():
             database.save(path=test_dir, save_mode=config.SETTINGS.get('save_mode', 'test'), scene_id=scene_id)
     return results, per_scene, database
+
+
+def _tracked_batch(batch, database, config, last_pose, log):
+    """``batch`` with the pose tracked against its scene's volume from the scene's last fused pose, recorded in
+    ``database.tracked_poses``; None (and a log line) when the scene has no earlier pose or tracking fails."""
+    frame_id = batch['frame_id'][0]
+    scene = frame_id.split('/')[0]
+    if scene not in last_pose:
+        log('track_invalid_poses: {} skipped: no earlier pose in scene {}'.format(frame_id, scene))
+        return None
+    E0 = last_pose[scene]
+    depth = batch[config.DATA.input][0]
+    mask = batch['mask'][0] if 'mask' in batch else None
+    res = database.track(scene, depth, batch['intrinsics'][0], E0, reference_extrinsics=E0, mask=mask)
+    if not res['ok']:
+        log('track_invalid_poses: {} skipped: tracking failed (status {})'.format(frame_id, res['status']))
+        return None
+    database.tracked_poses[frame_id] = res['extrinsics']
+    rows = batch['extrinsics'].shape[-2]
+    out = dict(batch)
+    out['extrinsics'] = torch.from_numpy(res['extrinsics'][:rows].copy()).to(batch['extrinsics'].dtype).unsqueeze(0)
+    return out
 
 
 def _dist_on():
