@@ -366,7 +366,7 @@ int ojf_trainer_set_arithmetic(ojf_trainer *t, int arithmetic);
 int ojf_trainer_set_backward_arithmetic(ojf_trainer *t, int arithmetic);
 int ojf_trainer_layer_count(const ojf_trainer *t);
 int ojf_trainer_launch_count(const ojf_trainer *t);
-/* Optional replay of the passes as device graphs (default off; OJF_TRAIN_GRAPH=1 in the environment turns it on at create):
+/* Optional replay of the passes as device graphs (default off; ojf_trainer_set_graph turns it on):
  * the launches of a forward / backward pass between the trainer's own buffers and the layer table's tensors are captured once
  * per (layer table contents, arithmetic) on a stream of the trainer's own and replayed with one hipGraphLaunch on the caller's
  * stream - same kernels, same arguments, same bits; a pass is captured the second time its key misses in a row, so a table

@@ -9,7 +9,6 @@
 // kernel is bound by instruction issue of the fp64 index math and the gather latency, not by bytes: the per-frame
 // gather footprint (<= a few MB of 128-B lines) lives in L2/MALL.
 #include <cmath>
-#include <cstdlib>
 
 #include "ojf_common.h"
 
@@ -50,11 +49,10 @@ constexpr int kMaxTilePoints = 16;  // at most 64 * n_points threads per block
 // Waves of an extract_tile_kernel block: every wave takes the samples k = wave, wave + waves, ... of the block's 64 pixels.  Rounds 1-6
 // ran one wave per sample: nine-wave blocks, of which a CU held TWO (nine waves do not spread 7 / 7 / 7 / 6 over the SIMDs that 72 VGPRs
 // allow), so the 1200 blocks of a 320x240 frame ran in three waves of 4.5 us each (profiles/r06_accumulate_stamps.txt).  Three samples per
-// wave: three-wave blocks, eight or nine per CU, the whole frame resident at once.  OJF_EXTRACT_WAVES=n forces n (A/B).
+// wave: three-wave blocks, eight or nine per CU, the whole frame resident at once.
 static int extract_block_waves(int n_points)
 {
-    static const int forced = getenv("OJF_EXTRACT_WAVES") ? atoi(getenv("OJF_EXTRACT_WAVES")) : 0;
-    int waves = forced > 0 ? forced : (n_points + 2) / 3;
+    int waves = (n_points + 2) / 3;
     if (waves > n_points) waves = n_points;
     return waves < 1 ? 1 : waves;
 }
@@ -242,8 +240,6 @@ __global__ __launch_bounds__(64 * kMaxTilePoints) void extract_tile_many_kernel(
 // volume-z components of the camera's x (image row direction) and y (image column direction) axes.
 static inline bool extract_columns(const float *E)
 {
-    static const int force = getenv("OJF_EXTRACT_TILE") ? atoi(getenv("OJF_EXTRACT_TILE")) : 0;  // A/B: 1 columns, 2 rows
-    if (force) return force == 1;
     return std::fabs(E[9]) >= std::fabs(E[8]);
 }
 static inline int extract_tiles(int h, int w, bool columns)

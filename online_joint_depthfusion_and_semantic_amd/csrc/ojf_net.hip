@@ -43,22 +43,16 @@
 //     instead of in_chs (114/228);
 //   * the global-average branch is constant over the image: it is reduced to a per-frame bias of
 //     the final 1x1 convolution (two tiny kernels on a side stream), removing its 114 input columns from that GEMM.
-// Launches of one forward pass (geometry-only v3): 10 dense-block convolutions, per VortexPooling {branch-entry
-// GEMM, pool pyramid, two grouped launches of the four branches' dilated 3x3, fused tail}; the last tail also runs
-// the 11-layer prediction head: 22 launches on the main stream.  Environment switches (tuning / ablation only):
-// OJF_CONV_MT, OJF_NO_TAIL, OJF_NO_CHAIN, OJF_NO_HEAD_FUSION, OJF_NET_GRAPH=1 (opt-in hipGraph replay).
-#ifndef OJF_CHAIN_DMA_HALF
-#define OJF_CHAIN_DMA_HALF 1536
-#endif
-#ifndef OJF_CHAIN_BLOCKS
-#define OJF_CHAIN_BLOCKS 3
-#endif
-#ifndef OJF_CHAIN_WAVES
-#define OJF_CHAIN_WAVES 4
-#endif
-#ifndef OJF_CHAIN_AHEAD
-#define OJF_CHAIN_AHEAD 2
-#endif
+// Launches of one forward pass (geometry-only v3, the default topology, frame width a multiple of 8; forward_launches /
+// run_vortex): dense_chain_kernel (all dense Blocks of the head), then per VortexPooling {pool pyramid (+ the global-average
+// fold), two grouped launches of the four branches' dilated 3x3, fused tail}: the first VortexPooling's entry GEMM is a launch
+// of its own (entry1x1_kernel), its tail runs the second one's entry GEMM, and the last tail runs the 11-layer prediction
+// head: 10 launches on one stream.  The two-head (semantic) net runs its second head beside the first on a second stream, each
+// head's tail computing its half of the last entry GEMM.  Other inputs take the general paths: dense_pair_kernel per Block
+// (w % 8 != 0), generic convolutions (fp32 arithmetic, other growth rates), the general VortexPooling flow with the
+// global-average branch on a side stream and an unfused tail / head (topologies without chain-layer forms).
+// Environment switches: OJF_NET_GRAPH=1 (opt-in hipGraph replay); test-only, each set by one test of tests/test_net_gpu.py:
+// OJF_NO_DENSE_CHAIN=1 (pair kernels instead of the chain kernel), OJF_BRANCH_KERNEL=1 / OJF_SUBCONV=1 (ojf_net_branch.h).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -109,30 +103,12 @@ __device__ __forceinline__ f32x4 unsplit4(const f32x4 &s)
 }
 // two split-plane float4 (channel groups A, B) -> the MFMA operand halves of their eight channels:
 // (A0 A1 A2 A3)(B0 B1 B2 B3) -> (A0 A1 B0 B1)(A2 A3 B2 B3).
-// Round 3 did this in place with two hand-placed v_swap_b32 (inline assembly: as plain vector shuffles the compiler spends
-// moves).  Round 4 found that form UNSAFE next to MFMAs: hipcc's hazard recogniser does not look inside inline assembly, so
-// nothing keeps a swap from rewriting a register an MFMA in flight still reads (or an MFMA from reading a register the
-// swap has not finished writing) - dense_chain_kernel's packed-row loop computed wrong sums for exactly the operand dwords
-// the swaps touch, on some waves, run after run, and a padding s_nop 7 did not cure all of it.  The convolution kernels
-// never failed a test with it, but "never failed" is not a proof: plain shuffles (OJF_UNSAFE_SWAP=1 restores the old form
-// for measurements: 2539 / 2542 frames/s with the shuffles against 2533 / 2538 with the swaps on one box, no difference).
-#ifndef OJF_UNSAFE_SWAP
-#define OJF_UNSAFE_SWAP 0
-#endif
+// Plain shuffles on purpose: round 3's two hand-placed v_swap_b32 (inline assembly, which hipcc's hazard recogniser does not look
+// into) computed wrong sums next to the MFMAs of dense_chain_kernel and measured no faster (2533 / 2538 against 2539 / 2542 frames/s).
 __device__ __forceinline__ void unpack_split(const f32x4 &a, const f32x4 &b, f16x8 &hi, f16x8 &lo)
 {
-#if OJF_UNSAFE_SWAP
-    u32x4 A = __builtin_bit_cast(u32x4, a), B = __builtin_bit_cast(u32x4, b);
-    unsigned a2 = A[2], a3 = A[3], b0 = B[0], b1 = B[1];
-    asm("v_swap_b32 %0, %1" : "+v"(a2), "+v"(b0));
-    asm("v_swap_b32 %0, %1" : "+v"(a3), "+v"(b1));
-    A[2] = a2; A[3] = a3; B[0] = b0; B[1] = b1;
-    hi = __builtin_bit_cast(f16x8, A);
-    lo = __builtin_bit_cast(f16x8, B);
-#else
     hi = __builtin_bit_cast(f16x8, __builtin_shufflevector(a, b, 0, 1, 4, 5));
     lo = __builtin_bit_cast(f16x8, __builtin_shufflevector(a, b, 2, 3, 6, 7));
-#endif
 }
 
 // acc += W * X for one 16x16 tile over a 32-wide K block, W and X given as split halves
@@ -575,12 +551,9 @@ constexpr int conv16_chunk(int nt) { return nt <= 2 ? 6 : 3; }  // supersteps pe
 // 4 = no MFMA, 8 = no fp16 split.  Product launches always use ABL = 0.
 // INS: the input planes are split planes (every convolution of the launch: the host checks)
 template <int MT, int NT, bool SKIP = true, int ABL = 0, bool LEAN = false, bool INS = false>
-#ifndef OJF_CONV_LB
-#define OJF_CONV_LB 1
-#endif
 // (the lean grouped 3x3 form keeps four waves per SIMD - 128 registers - now that its blocks are persistent: the pixel-block loop costs
-// 12 registers, which without the bound dropped it to three; OJF_CONV_LB=0 builds the unbounded form for A/B runs)
-__global__ __launch_bounds__(256, (OJF_CONV_LB && MT == 2 && NT == 2 && LEAN) ? 4 : 1) void conv_f16x3_kernel(const ConvGroup grp)
+// 12 registers, which without the bound dropped it to three)
+__global__ __launch_bounds__(256, (MT == 2 && NT == 2 && LEAN) ? 4 : 1) void conv_f16x3_kernel(const ConvGroup grp)
 {
     constexpr int CS = conv16_chunk(NT);
     const ConvArgs &a = grp.g[blockIdx.y];
@@ -762,7 +735,7 @@ __global__ __launch_bounds__(256, (OJF_CONV_LB && MT == 2 && NT == 2 && LEAN) ? 
 // 19- and 20-channel growth), so every register array is statically indexed.
 // ------------------------------------------------------------------------------------------------
 constexpr int kChainLdsFloat4 = 48 * 1024 / 16;
-constexpr int kChainDmaHalf = OJF_CHAIN_DMA_HALF;  // float4 per half of the split-fp16 weight double buffer
+constexpr int kChainDmaHalf = 1536;  // float4 per half of the split-fp16 weight double buffer
 
 struct ChainArgs {
     const f32x4 *in;  // input planes, c4_in groups starting at in_g0
@@ -815,8 +788,9 @@ constexpr int chain_first_size(int arith, int ntin, int ntout)
 }
 // per-layer floats in the bias stream: bias[NTOUT*16], and for split-fp16 the inverse row scales behind it
 constexpr int chain_bias_stride(int arith, int ntout) { return (arith == OJF_ARITH_F16X3 ? 2 : 1) * ntout * 16; }
-constexpr int kChainAhead = OJF_CHAIN_AHEAD;  // weight fragments requested ahead of their MFMAs (split-fp16 chain layers)
-constexpr int kChainWaves = OJF_CHAIN_WAVES, kChainThreads = 64 * kChainWaves;  // waves of a chain / tail / entry block
+constexpr int kChainAhead = 2;  // weight fragments requested ahead of their MFMAs (split-fp16 chain layers)
+constexpr int kChainWaves = 4, kChainThreads = 64 * kChainWaves;  // waves of a chain / tail / entry block
+constexpr int kChainBlocks = 3;  // blocks of them a CU is to hold (launch bound)
 constexpr int kChainPre = kChainLdsFloat4 / kChainThreads;  // float4 registers per thread holding the prefetched next part
 
 // LDS-DMA of `size` float4 (a multiple of 64) from src to the LDS address dst: wave w moves the 1 KB chunks
@@ -1046,50 +1020,6 @@ __device__ __forceinline__ void chain_run(f32x4 (&x)[MT][8], f32x4 (&y)[MT][8], 
                                                  bias + chain_bias_stride(ARITH, NTOUT), a, p, lane, pre, buf, vs);
 }
 
-template <int ARITH, int MT, int NT0, int... NTS>
-__global__ __launch_bounds__(kChainThreads, OJF_CHAIN_BLOCKS) void chain1x1_kernel(const ChainArgs a)
-{
-    __shared__ f32x4 wlds[chain_dma(ARITH) ? 2 * kChainDmaHalf : kChainLdsFloat4];
-    __shared__ f32x4 vec_lds[2 * kVecF4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i16 = lane & 15, g = lane >> 4;
-    const int strip = (banded_block_x() * kChainWaves + wave) * (MT * 16);
-    int p[MT];
-    f32x4 x[MT][8], y[MT][8];
-    VecStage vs;
-    vs.lds = vec_lds; vs.half = 0;
-    {
-        constexpr int first[] = {NTS...};
-        VecNext nx;
-        nx.a = a.bias; nx.na = chain_bias_stride(ARITH, first[0]) / 4;
-        vec_issue(vs, nx);  // the first layer's epilogue vectors
-    }
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        p[m] = strip + m * 16 + i16;  // waves past the image still take part in the barriers
-#pragma unroll
-        for (int S = 0; S < NT0; ++S) {
-            const int G = 4 * S + g;
-            const bool ok = p[m] < a.npix && G < a.c4_in;
-            x[m][S] = a.in[ok ? (a.in_g0 + G) * a.npix + p[m] : -1];
-        }
-    }
-    f32x4 pre[kChainPre];
-    int buf = 0;
-    {   // first part of the first layer
-        constexpr int first[] = {NTS...};
-        constexpr int size0 = chain_first_size(ARITH, NT0, first[0]);
-        if constexpr (chain_dma(ARITH)) {
-            dma_part(a.w, wlds, size0, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane);
-        } else {
-#pragma unroll
-            for (int k = 0; k < kChainPre; ++k)
-                if ((int)threadIdx.x + kChainThreads * k < size0) pre[k] = a.w[threadIdx.x + kChainThreads * k];
-        }
-    }
-    chain_run<ARITH, MT, NT0, NTS...>(x, y, wlds, a.w, a.bias, a, p, lane, pre, buf, vs);
-}
-
 // Channel sums of a register-resident activation tile set (the global-average branch of the NEXT VortexPooling,
 // model.py:107-112): x[m][S] of lane (pixel i16, g) holds channels 16S+4g..+3 of pixel p[m].  Within a block the sum
 // is formed in fp32 in a fixed order (butterfly over the 16 pixels of a tile, tiles, then the four waves through LDS);
@@ -1154,7 +1084,7 @@ __device__ __forceinline__ void block_colsum(const f32x4 (&x)[MT][NA], const int
 // convolution kernel needed 25 us for this launch (tap table, masks, 6 output tiles per wave) and a separate
 // column-sum launch re-read the same 37 MB.
 template <int ARITH, int MT, int NTIN, int NTOUT>
-__global__ __launch_bounds__(kChainThreads, OJF_CHAIN_BLOCKS) void entry1x1_kernel(const ChainArgs a)
+__global__ __launch_bounds__(kChainThreads, kChainBlocks) void entry1x1_kernel(const ChainArgs a)
 {
     __shared__ f32x4 wlds[chain_dma(ARITH) ? 2 * kChainDmaHalf : kChainLdsFloat4];
     __shared__ f32x4 vec_lds[2 * kVecF4];
@@ -1249,7 +1179,7 @@ constexpr int head_first_size(int arith, int kind) { return chain_first_size(ari
 // CHAIN = 0: write the VortexPooling result planes.  CHAIN = 19 / 20: feed it straight into the prediction head
 // (same accumulator -> operand identity) and write est rows; the 114-channel tensor between them never exists.
 template <int ARITH, int MT, int NV, int NO, int CHAIN = 0>
-__global__ __launch_bounds__(kChainThreads, OJF_CHAIN_BLOCKS) void vortex_tail_kernel(const TailArgs a)
+__global__ __launch_bounds__(kChainThreads, kChainBlocks) void vortex_tail_kernel(const TailArgs a)
 {
     static_assert(CHAIN == 0 || NO == 8, "the fused prediction head / entry layer expects 8 input tiles");
     __shared__ f32x4 wlds[chain_dma(ARITH) ? 2 * kChainDmaHalf : kChainLdsFloat4];
@@ -1358,7 +1288,7 @@ __global__ __launch_bounds__(kChainThreads, OJF_CHAIN_BLOCKS) void vortex_tail_k
 // reference); the intermediate levels never reach HBM.  Summation order per level = row-major taps, as before.
 // (used by gave_bias_block below; declared here because the pyramid launch carries one)
 struct GaveArgs {
-    const float *partial;   // legacy flow: nparts rows of pstride floats, added in row order
+    const float *partial;   // general flow: nparts rows of pstride floats, added in row order
     struct ColSums *fixed;  // chain flow: fixed-point sums (read, then zeroed for the next frame)
     int nparts, pstride, cphys, npix;
     const float *WgT, *bg, *WfgT, *bf;  // WgT [cphys][c_out], WfgT [c_out(j)][c_out(o)]: lane o reads consecutive addresses
@@ -1722,13 +1652,9 @@ static inline void mark_launch(const char *name, hipStream_t st)
     g_marks.push_back(LaunchMark{name, st, e});
 }
 
-// Fork / join events between streams of the same device: no timing, and (OJF_EVENT_FENCE=1 restores it) no system-scope
-// fence - nothing here is read by the host or another device through these events.
-static unsigned event_flags()
-{
-    static const bool fence = getenv("OJF_EVENT_FENCE") && atoi(getenv("OJF_EVENT_FENCE"));
-    return fence ? hipEventDisableTiming : (hipEventDisableTiming | hipEventDisableSystemFence);
-}
+// Fork / join events between streams of the same device: no timing and no system-scope fence - nothing here is read by
+// the host or another device through these events.
+static unsigned event_flags() { return hipEventDisableTiming | hipEventDisableSystemFence; }
 
 static const char *kChainStuckMsg =
     "fusion net: dense_chain_kernel gave up waiting for a neighbouring tile (internal error: the results of this forward pass are invalid)";
@@ -1866,24 +1792,17 @@ static long long *g_pair_dbg = nullptr;
 struct PackedPair {
     float *wa = nullptr, *wb = nullptr, *vec = nullptr;  // vec: bias_a | rinv_a | bias_b | rinv_b (32 floats each)
     int c4_in = 0, n_chunks = 0, np_last = 0, np_b = 0, og_store = 0;
-    int cfg = 0;  // PairCfg the weights were packed for (chunk size)
+    int cfg = 0;  // PairCfg of the launches
 };
 
-// Launch shapes of dense_pair_kernel (PairGeom): picked per frame size, the chunk size is part of the weight packing
-enum PairCfg { PAIR_20x16_W16 = 0, PAIR_12x8_W16 = 1, PAIR_20x8_W8 = 2, PAIR_16x8_W8 = 3, PAIR_20x8_W8_CP4 = 4,
-               PAIR_20x16_W16_P5 = 5, PAIR_12x8_W16_P5 = 6, PAIR_CFG_COUNT = 7 };
-static inline int pair_cfg_chunk_pairs(int cfg) { return cfg == PAIR_20x8_W8 || cfg == PAIR_16x8_W8 ? 3 : 4; }
-static inline bool pair_cfg_pack(int cfg) { return cfg == PAIR_20x16_W16_P5 || cfg == PAIR_12x8_W16_P5; }
-// c_out_phys: physical output channels of both convolutions (the packed-row shapes are written for 20 = 19 + padding)
-static int pair_cfg_for(int h, int w, int c_out_phys)
+// Launch shapes of dense_pair_kernel (PairGeom): picked per frame size
+enum PairCfg { PAIR_20x16_W16 = 0, PAIR_12x8_W16 = 1 };
+constexpr int kPairChunkPairs = 4;  // channel pairs per chunk of the first convolution's packed weights (PairGeom::CP)
+static int pair_cfg_for(int h, int w)
 {
-    static const int forced = getenv("OJF_PAIR_CFG") ? atoi(getenv("OJF_PAIR_CFG")) : -1;  // tuning switch
     // one block per tile, 16 waves: the large tile when it still gives every CU a block (320x240: 240 blocks)
-    const bool big = ((w + 19) / 20) * ((h + 15) / 16) >= 200;
-    // (round 4 measured the other shapes - two 8-wave blocks per CU, packed rows - against this one: DESIGN.md §5.0, no gain)
-    int cfg = big ? PAIR_20x16_W16 : PAIR_12x8_W16;
-    if (forced >= 0 && forced < PAIR_CFG_COUNT && (!pair_cfg_pack(forced) || c_out_phys == 20)) cfg = forced;
-    return cfg;
+    // (round 4 measured other shapes - two 8-wave blocks per CU, packed rows - against this one: DESIGN.md §5.0, no gain)
+    return ((w + 19) / 20) * ((h + 15) / 16) >= 200 ? PAIR_20x16_W16 : PAIR_12x8_W16;
 }
 
 static void release(PackedPair &pp)
@@ -1895,33 +1814,6 @@ static void release(PackedPair &pp)
 }
 
 // K blocks of `np_chunk`-pair chunks: unit u = 4S + g -> (tap = u / np, pair = u % np), K slot j = channel 8*pair + j
-// packed-row form (PairGeom PACK): [K block][3 row tiles][lane] x 8 halfs; packed row R = hi half of output row R for
-// R < c_out_phys, lo half of output row R - c_out_phys for R < 2 c_out_phys, zero beyond
-static void pack_pair_conv5(const ConvBuilder &b, const std::vector<float> &rs, std::vector<float> &dst, int cp)
-{
-    const int npairs = (b.c_in_phys + 7) / 8, n_chunks = (npairs + cp - 1) / cp, ocp = b.c_out_phys;
-    for (int c = 0; c < n_chunks; ++c) {
-        const int np = c == n_chunks - 1 ? npairs - cp * c : cp, nkb = (9 * np + 3) / 4;
-        const size_t base = dst.size();
-        dst.resize(base + (size_t)nkb * 192 * 4, 0.0f);
-        _Float16 *hp = reinterpret_cast<_Float16 *>(dst.data() + base);
-        for (int S = 0; S < nkb; ++S)
-            for (int t = 0; t < 3; ++t)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int R = t * 16 + (lane & 15), u = 4 * S + (lane >> 4);
-                        if (R >= 2 * ocp || u >= 9 * np) continue;
-                        const int oc = R < ocp ? R : R - ocp;
-                        const int tap = u / np, ch = 8 * (cp * c + u % np) + j;
-                        if (ch >= b.c_in_phys) continue;
-                        const float v = rs[oc] * b.W[((size_t)oc * b.taps + tap) * b.c_in_phys + ch];
-                        _Float16 hi, lo;
-                        split_weight(v, hi, lo);
-                        hp[(((size_t)S * 3 + t) * 64 + lane) * 8 + j] = R < ocp ? hi : lo;
-                    }
-    }
-}
-
 static void pack_pair_conv(const ConvBuilder &b, const std::vector<float> &rs, std::vector<float> &dst, int cp)
 {
     const int npairs = (b.c_in_phys + 7) / 8, n_chunks = (npairs + cp - 1) / cp;
@@ -1947,7 +1839,7 @@ static void pack_pair_conv(const ConvBuilder &b, const std::vector<float> &rs, s
 
 static int finish_pair(const ConvBuilder &ba, const ConvBuilder &bb, PackedPair &pp, int cfg = PAIR_20x16_W16)
 {
-    const int cp = pair_cfg_chunk_pairs(cfg);
+    constexpr int cp = kPairChunkPairs;
     pp.cfg = cfg;
     if (ba.taps != 9 || bb.taps != 9 || ba.dil != 1 || bb.dil != 1 || ba.c_out_phys > 24 || bb.c_in_phys != ba.c_out_phys ||
         bb.c_out_phys > 32 || ba.c_in_phys % 4)
@@ -1966,14 +1858,8 @@ static int finish_pair(const ConvBuilder &ba, const ConvBuilder &bb, PackedPair 
         return rs;
     };
     const std::vector<float> ra = scales(ba, 0), rb = scales(bb, 64);
-    if (pair_cfg_pack(cfg)) {
-        if (ba.c_out_phys != 20 || bb.c_out_phys != 20) return fail("pair packing: the packed-row shapes need 20 physical output channels");
-        pack_pair_conv5(ba, ra, wa, cp);
-        pack_pair_conv5(bb, rb, wb, 4);
-    } else {
-        pack_pair_conv(ba, ra, wa, cp);
-        pack_pair_conv(bb, rb, wb, 4);  // (3 pairs: one chunk whatever the chunk size)
-    }
+    pack_pair_conv(ba, ra, wa, cp);
+    pack_pair_conv(bb, rb, wb, cp);  // (3 pairs: one chunk)
     pp.np_b = (bb.c_in_phys + 7) / 8;
     const int npairs = (ba.c_in_phys + 7) / 8;
     pp.c4_in = ba.c_in_phys / 4;
@@ -1984,19 +1870,20 @@ static int finish_pair(const ConvBuilder &ba, const ConvBuilder &bb, PackedPair 
     return 0;
 }
 
-template <int TW, int TH, int WAVES = 16, int CP = 4, bool ALIAS = false, bool PACK = false>
+template <int TW, int TH>
 static int launch_pair_t(PairArgs &a, hipStream_t st)
 {
-    using G = PairGeom<TW, TH, WAVES, CP, ALIAS, PACK>;
+    using G = PairGeom<TW, TH>;
+    static_assert(G::CP == kPairChunkPairs, "the weights are packed in chunks of PairGeom::CP channel pairs");
     static bool configured = false;
     if (!configured) {
-        OJF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&dense_pair_kernel<TW, TH, WAVES, CP, ALIAS, PACK>),
+        OJF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&dense_pair_kernel<TW, TH>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES));
         configured = true;
     }
     a.tiles_x = (a.w + TW - 1) / TW;
     const int tiles = a.tiles_x * ((a.h + TH - 1) / TH);
-    hipLaunchKernelGGL((dense_pair_kernel<TW, TH, WAVES, CP, ALIAS, PACK>), dim3(tiles), dim3(G::THREADS), G::LDS_BYTES, st, a);
+    hipLaunchKernelGGL((dense_pair_kernel<TW, TH>), dim3(tiles), dim3(G::THREADS), G::LDS_BYTES, st, a);
     mark_launch("dense_pair_kernel", st);
     return check_hip(hipGetLastError(), "dense_pair_kernel launch");
 }
@@ -2011,8 +1898,6 @@ static int launch_pair(const PackedPair &pp, const float *in, int in_g0, float *
     a.in_g0 = in_g0; a.c4_in = pp.c4_in; a.out_g0 = out_g0; a.og_store = pp.og_store;
     a.h = h; a.w = w; a.npix = h * w; a.tiles_x = 0;
     a.n_chunks = pp.n_chunks; a.np_last = pp.np_last; a.np_b = pp.np_b;
-    static const bool no_band = getenv("OJF_NO_XCD_BAND") != nullptr;  // tuning switch only
-    a.xcd_bands = no_band ? 0 : 1;
     a.ovf = overflow_flag();
 #ifdef OJF_PAIR_TIMING
     a.dbg = g_pair_dbg;
@@ -2020,11 +1905,6 @@ static int launch_pair(const PackedPair &pp, const float *in, int in_g0, float *
     switch (pp.cfg) {
     case PAIR_20x16_W16: return launch_pair_t<20, 16>(a, st);
     case PAIR_12x8_W16: return launch_pair_t<12, 8>(a, st);
-    case PAIR_20x8_W8: return launch_pair_t<20, 8, 8, 3, true>(a, st);
-    case PAIR_16x8_W8: return launch_pair_t<16, 8, 8, 3, true>(a, st);
-    case PAIR_20x8_W8_CP4: return launch_pair_t<20, 8, 8, 4, true>(a, st);
-    case PAIR_20x16_W16_P5: return launch_pair_t<20, 16, 16, 4, false, true>(a, st);
-    case PAIR_12x8_W16_P5: return launch_pair_t<12, 8, 16, 4, false, true>(a, st);
     }
     return fail("dense pair: unknown launch shape");
 }
@@ -2149,15 +2029,12 @@ static int launch_chain(const PackedChain &pc, float *x, int h, int w, hipStream
     a.w = planes(pc.w); a.vec = pc.vec;
     a.sync = pc.sync; a.layers = pc.layers;
     a.h = h; a.w_img = w; a.npix = h * w; a.tiles_x = a.tiles_y = 0;
-    static const bool no_band = getenv("OJF_NO_XCD_BAND") != nullptr;  // tuning switch only
-    a.xcd_bands = no_band ? 0 : 1;
     a.ovf = overflow_flag();
 #ifdef OJF_CHAIN_TIMING
     a.dbg = g_chain_dbg;
 #endif
-    static const int waves = getenv("OJF_CHAIN_WAVES") ? atoi(getenv("OJF_CHAIN_WAVES")) : 16;  // tuning switch
-    if (((w + 19) / 20) * ((h + 15) / 16) >= 200)  // (the large tile when it still gives every CU an item per Block)
-        return waves == 16 ? launch_chain_t<20, 16, 16>(a, st) : (waves == 12 ? launch_chain_t<20, 16, 12>(a, st) : launch_chain_t<20, 16, 8>(a, st));
+    if (((w + 19) / 20) * ((h + 15) / 16) >= 200)  // (the large tile when it still gives every CU an item per Block; 16 waves: 12 and 8 measured slower)
+        return launch_chain_t<20, 16, 16>(a, st);
     return launch_chain_t<12, 8, 8>(a, st);
 }
 
@@ -2362,11 +2239,10 @@ static int launch_conv_args(const ConvArgs *args, int n, int nt, hipStream_t st,
     // rounds of twice the length (78 % vs 94 % balance); measured 14.9 vs 17.3 us on the 19->19 3x3 layers.
     // split-fp16: two pixel tiles per wave share the LDS weight reads and the per-wave prologue; measured in one run
     // (net stage): MT = 2 everywhere 0.501 ms, MT = 2 only for grouped / wide launches 0.508 ms, MT = 1 0.514 ms.
-    static const int mt_env = getenv("OJF_CONV_MT") ? atoi(getenv("OJF_CONV_MT")) : 0;  // tuning switch only
     // The wide launches of the training executor (NT >= 6: 96 / 128 output channels) need 204-212 + 64 registers at MT = 2 -
     // one wave per SIMD, nothing to run while a block waits for its weight chunk; MT = 1 (140 + 32) keeps two: training
     // frame step 216 -> 220 and 204 -> 217 frames/s on two boxes (NT <= 4: no difference).
-    const int mt = arith == OJF_ARITH_F16X3 ? (mt_env ? mt_env : (nt >= 6 ? 1 : 2)) : 1;
+    const int mt = arith == OJF_ARITH_F16X3 ? (nt >= 6 ? 1 : 2) : 1;
     const int strips = (args[0].npix + mt * 16 - 1) / (mt * 16);
     const dim3 grid((strips + 3) / 4, n), block(256);
 #define OJF_LAUNCH32(NT_) hipLaunchKernelGGL((conv_mfma_kernel<1, NT_>), grid, block, 0, st, grp)
@@ -2374,14 +2250,12 @@ static int launch_conv_args(const ConvArgs *args, int n, int nt, hipStream_t st,
     for (int i = 0; i < n; ++i) max_steps = args[i].nsteps > max_steps ? args[i].nsteps : max_steps;
     const size_t tab_bytes = (size_t)(max_steps + kPad16) * 8 * sizeof(int2);  // (no measurable effect vs the full 8.6 KB)
     // split-fp16 launches hand every XCD one band of the image (xcd_band_block)
-    static const bool no_band = getenv("OJF_NO_XCD_BAND") != nullptr;  // tuning switch only
     dim3 grid16 = grid;
-    if (arith == OJF_ARITH_F16X3 && !no_band && grid.x >= 64) {
+    if (arith == OJF_ARITH_F16X3 && grid.x >= 64) {
         grp.nblocks = (int)grid.x;
         grid16.x = round_up((int)grid.x, 8);
     }
-    static const bool no_perm = getenv("OJF_CONV_ROW_PERM") && atoi(getenv("OJF_CONV_ROW_PERM")) == 0;  // A/B switch
-    if (grp.nblocks && !no_perm)
+    if (grp.nblocks)
         for (int i = 0; i < n; ++i) {
             ConvArgs &g = grp.g[i];
             if (g.taps == 9 && g.dil > 1 && g.dil < g.h && g.w % (mt * 16) == 0) {
@@ -2389,8 +2263,8 @@ static int launch_conv_args(const ConvArgs *args, int n, int nt, hipStream_t st,
             }
         }
     // persistent blocks for single-chunk layers (ConvGroup::band): `bpc` blocks per CU over all members of the group
-    static const int persist_bpc = getenv("OJF_CONV_PERSIST") ? atoi(getenv("OJF_CONV_PERSIST")) : 3;  // A/B switch (0: one pixel block per launch block; measured 2 / 3 / 4 / 6: 3 is best, profiles/r06_fusion_net_experiments.txt)
-    if (grp.nblocks && persist_bpc > 0 && arith == OJF_ARITH_F16X3) {
+    constexpr int persist_bpc = 3;  // measured 2 / 3 / 4 / 6 and one pixel block per launch block: 3 is best (profiles/r06_fusion_net_experiments.txt)
+    if (grp.nblocks && arith == OJF_ARITH_F16X3) {
         bool single = true;
         for (int i = 0; i < n; ++i) single = single && args[i].nsteps <= conv16_chunk(nt);
         const int cus = device_cu_count();
@@ -2401,8 +2275,7 @@ static int launch_conv_args(const ConvArgs *args, int n, int nt, hipStream_t st,
             grid16.x = (unsigned)G;
         }
     }
-    static const bool no_lean = getenv("OJF_CONV_LEAN") && atoi(getenv("OJF_CONV_LEAN")) == 0;  // A/B switch
-    bool lean = arith == OJF_ARITH_F16X3 && !no_lean;
+    bool lean = arith == OJF_ARITH_F16X3;
     for (int i = 0; i < n && lean; ++i) lean = conv_lean_ok(args[i]);
     int n_ins = 0, n_outs = 0;
     for (int i = 0; i < n; ++i) { n_ins += args[i].in_split ? 1 : 0; n_outs += args[i].out_split ? 1 : 0; }
@@ -2434,18 +2307,11 @@ static int launch_conv_args(const ConvArgs *args, int n, int nt, hipStream_t st,
             default: return fail("conv: unsupported number of output tiles");
         }
     } else {
-        static const bool no_lds32 = getenv("OJF_CONV32_LDS") && atoi(getenv("OJF_CONV32_LDS")) == 0;  // A/B switch
         switch (nt) {
             case 2: OJF_LAUNCH32(2); break;
             case 4: OJF_LAUNCH32(4); break;
-            case 6:
-                if (no_lds32) OJF_LAUNCH32(6);
-                else hipLaunchKernelGGL((conv_mfma_lds_kernel<6>), grid, block, 0, st, grp);
-                break;
-            case 8:
-                if (no_lds32) OJF_LAUNCH32(8);
-                else hipLaunchKernelGGL((conv_mfma_lds_kernel<8>), grid, block, 0, st, grp);
-                break;
+            case 6: hipLaunchKernelGGL((conv_mfma_lds_kernel<6>), grid, block, 0, st, grp); break;
+            case 8: hipLaunchKernelGGL((conv_mfma_lds_kernel<8>), grid, block, 0, st, grp); break;
             default: return fail("conv: unsupported number of output tiles");
         }
     }
@@ -2679,8 +2545,7 @@ static int build_vortex(ojf_net *net, Vortex &v, const ojf_conv_layer *L, int c_
             }
         }
         if (finish(b, v.stacked, net->arith)) return -2;
-        static const bool no_wide_entry = getenv("OJF_NO_WIDE_ENTRY") != nullptr;  // A/B switch (round 6)
-        if ((c_in_phys <= 128 || (c_in_phys <= 256 && !no_wide_entry)) && 4 * cs <= 80) {
+        if (c_in_phys <= 256 && 4 * cs <= 80) {
             // chain-layer form (entry1x1_kernel / the previous tail): 8 input tiles -> 5; the two-head net's last VortexPooling
             // (228 = 2 x 114 input channels): 16 -> 5 (round 6: it ran the generic convolution + two side-stream kernels + three events)
             v.entry_ntin = c_in_phys <= 128 ? 8 : 16;
@@ -2690,8 +2555,7 @@ static int build_vortex(ojf_net *net, Vortex &v, const ojf_conv_layer *L, int c_
             pack_chain_layer(ew, net->arith, 5, v.entry_ntin, re, we);
             append_chain_bias(eb, net->arith, 5, 4 * cs, b.B.data(), re);
             if (upload(ew, &v.entry_w) || upload(eb, &v.entry_b)) return -2;
-            static const bool no_half = getenv("OJF_NO_HALF_ENTRY") != nullptr;  // A/B switch (round 6)
-            if (v.entry_ntin == 16 && c_in_phys == 2 * net->os && !no_half) {
+            if (v.entry_ntin == 16 && c_in_phys == 2 * net->os) {
                 const std::vector<float> zero_bias(4 * cs, 0.0f);
                 for (int hd = 0; hd < 2; ++hd) {
                     auto wh = [&](int oc, int k) { return oc < 4 * cs && k < net->os ? b.W[(size_t)oc * c_in_phys + hd * net->os + k] : 0.0f; };
@@ -2795,31 +2659,49 @@ static GaveArgs gave_args(const ojf_net *net, const Vortex &v, const float *part
 
 static int chain_blocks(const ojf_net *net) { return ((net->npix + 15) / 16 + ojf::kChainWaves - 1) / ojf::kChainWaves; }  // blocks of the MT = 1 chain kernels
 
+// What a VortexPooling's launches share with its neighbours (all optional: see the call sites in forward_launches)
+struct VortexLinks {
+    const ChainArgs *head = nullptr;  // the prediction head: the last VortexPooling's tail runs it where it can ...
+    bool *head_done = nullptr;        // ... and reports it here
+    bool entry_done = false;          // the previous tail already left this one's entry planes (sc.Z) and column sums (sc.colsum)
+    const Vortex *next = nullptr;     // when given (and supported), this tail runs the NEXT VortexPooling's entry GEMM on its
+    bool *next_done = nullptr;        //     register-resident result instead of writing `out`; *next_done reports it
+    bool in_split = false;            // `in` holds split planes (dense_chain_kernel's result)
+    // two-head nets: this head's tail runs half `half` of `next`'s entry GEMM (partial sums into sc.Z, the channel sums of its
+    // result into next_colsum at channel half * os)
+    int half = -1;
+    ColSums *next_colsum = nullptr;
+    // the OTHER head's partial entry planes: this VortexPooling's pyramid adds them to sc.Z and forms branch 0 (entry_done must be set)
+    const float *z2 = nullptr;
+};
+
 // in: planes, window starting at group in_g0 (c_in_phys/4 groups); out: planes at group out_g0.
-// entry_done: the previous VortexPooling's tail already left this one's entry planes (sc.Z) and column sums (sc.colsum).
-// next: when given (and supported), this tail runs the NEXT VortexPooling's entry GEMM on its register-resident result
-//       instead of writing `out`; *next_done reports it.
-// half / next_colsum (two-head nets): this head's tail runs half `half` of `next`'s entry GEMM (partial sums into sc.Z, the channel
-//       sums of its result into next_colsum at channel half * os).  z2: the OTHER head's partial entry planes - this
-//       VortexPooling's pyramid adds them to sc.Z and forms branch 0 (entry_done must be set).
 static int run_vortex(ojf_net *net, Vortex &v, const float *in, int in_g0, float *out, int out_g0, hipStream_t st,
-                      ojf_net::Scratch &sc, const ChainArgs *head = nullptr, bool *head_done = nullptr,
-                      bool entry_done = false, const Vortex *next = nullptr, bool *next_done = nullptr, bool in_split = false,
-                      int half = -1, ColSums *next_colsum = nullptr, const float *z2 = nullptr)
+                      ojf_net::Scratch &sc, const VortexLinks &l = VortexLinks())
 {
     const int h = net->h, w = net->w, c4 = net->cs / 4, o4 = net->os / 4;
     const bool h16 = net->arith == OJF_ARITH_F16X3;
-    static const bool legacy_env = getenv("OJF_LEGACY_VORTEX") != nullptr;  // ablation switch only
+    // ---- what runs --------------------------------------------------------------------------------------------------
     // Chain flow (no side stream, no events): entry GEMM + column sums in one chain-layer launch (or inside the previous
     // tail), the global-average fold as one extra block of the pyramid launch, all four branches in the grouped launches.
-    const bool chain_flow = v.entry_w && v.tail_w && !legacy_env;
+    // General flow (topologies whose entry or tail has no chain-layer form): generic convolutions, the global-average branch
+    // on the side stream.
+    const bool chain_flow = v.entry_w && v.tail_w;
     // split planes between the branch-entry producers (entry GEMM: branch 0; pool pyramid: branches 1-3), the branches' first
     // 3x3 and their second 3x3 (whose result the tail reads as plain fp32 planes)
-    static const bool no_split = getenv("OJF_CONV_SPLIT") && atoi(getenv("OJF_CONV_SPLIT")) == 0;  // A/B switch
-    const bool split = h16 && chain_flow && !no_split;
-    if (in_split && (!chain_flow || entry_done)) return fail("run_vortex: internal error (split-plane input without the entry kernel)");
+    const bool split = h16 && chain_flow;
+    // fused tail (the four branch-exit 1x1 and the final 1x1 in one launch), and what rides along with it
+    const bool fused = v.tail_w != nullptr;
+    enum { TAIL_ALONE, TAIL_HEAD, TAIL_HALF_ENTRY, TAIL_ENTRY } tail = TAIL_ALONE;
+    if (l.head && net->chain_kind) tail = TAIL_HEAD;  // last VortexPooling: the prediction head rides along
+    else if (chain_flow && l.next && l.half >= 0 && l.half < 2 && l.next->entry_wh[l.half] && l.next->tail_w && l.next_colsum) tail = TAIL_HALF_ENTRY;
+    else if (chain_flow && l.next && l.next->entry_w && l.next->tail_w && l.next->c_in_phys == net->os) tail = TAIL_ENTRY;
+    if (l.in_split && (!chain_flow || l.entry_done)) return fail("run_vortex: internal error (split-plane input without the entry kernel)");
+    if (!chain_flow && l.entry_done) return fail("run_vortex: internal error (entry planes without the chain flow)");
+    if (l.z2 && (!l.entry_done || !chain_flow || !sc.Q0 || !v.bias0)) return fail("run_vortex: internal error (partial entry sums without the chain flow)");
+
+    // ---- entry: the four branch-entry 1x1 as one GEMM into sc.Z, the global-average branch's column sums ----------------
     if (!chain_flow) {
-        if (entry_done) return fail("run_vortex: internal error (entry planes without the chain flow)");
         // global-average branch -> bias of the final conv, on the side stream (fork here, join before the tail)
         OJF_HIP(hipEventRecord(sc.ev_fork, st));
         OJF_HIP(hipStreamWaitEvent(sc.side, sc.ev_fork, 0));
@@ -2833,14 +2715,14 @@ static int run_vortex(ojf_net *net, Vortex &v, const float *in, int in_g0, float
         // branch entries: one GEMM, branch 0 gets bias + ReLU in the epilogue
         if (launch_conv(v.stacked, in, in_g0, sc.Z, 0, nullptr, OJF_ACT_RELU, net->cs, 1.0f, h, w, st)) return -2;
         OJF_HIP(hipEventRecord(sc.ev_entry, st));
-    } else if (!entry_done) {
+    } else if (!l.entry_done) {
         ChainArgs ea;
         ea.in = planes(in); ea.w = planes(v.entry_w); ea.bias = v.entry_b; ea.out_rows = nullptr;
         ea.in_g0 = in_g0; ea.c4_in = v.c_in_phys / 4; ea.npix = net->npix; ea.rows_stride = 0; ea.rows_n = 0; ea.scale = 1.0f;
         ea.ovf = h16 ? overflow_flag() : nullptr;
         ea.out_planes = planes(sc.Z); ea.out_g0 = 0; ea.og_store = 4 * c4; ea.act_n = net->cs; ea.colsum = sc.colsum;
         ea.split_groups = split ? c4 : 0;
-        ea.in_split = in_split ? 1 : 0;
+        ea.in_split = l.in_split ? 1 : 0;
         const dim3 grid(chain_blocks(net)), block(ojf::kChainThreads);
         // (two pixel tiles per wave - half the blocks, half the weight stream per pixel - measured 22.2 against 23.7 us and changes the
         // rounding of the channel sums: not kept, profiles/r06_fusion_net_experiments.txt)
@@ -2851,6 +2733,8 @@ static int run_vortex(ojf_net *net, Vortex &v, const float *in, int in_g0, float
         mark_launch("entry1x1_kernel", st);
         OJF_HIP(hipGetLastError());
     }
+
+    // ---- branches: pool pyramid, then the dilated 3x3 pair of each of the four branches into sc.V -------------------------
     {   // pool pyramid on the pre-activations of branches 1..3: Q_b = ReLU(pool^b(Z[slot b]) + bias_b), one launch
         PyramidArgs pa;
         pa.z = planes(sc.Z);
@@ -2858,21 +2742,16 @@ static int run_vortex(ojf_net *net, Vortex &v, const float *in, int in_g0, float
         for (int b = 0; b < 3; ++b) pa.bias[b] = v.pool_bias[b + 1];
         pa.h = h; pa.w = w; pa.c4 = c4;
         pa.tiles = ((w + kPoolTW - 1) / kPoolTW) * ((h + kPoolTH - 1) / kPoolTH);
-        pa.gave = gave_args(net, v, nullptr, 0, 0, (z2 && net->colsum3) ? net->colsum3 : sc.colsum);
+        pa.gave = gave_args(net, v, nullptr, 0, 0, (l.z2 && net->colsum3) ? net->colsum3 : sc.colsum);
         pa.fold_gave = chain_flow ? 1 : 0;
         pa.split_out = split ? 1 : 0;
-        if (z2) {
-            if (!entry_done || !chain_flow || !sc.Q0 || !v.bias0) return fail("run_vortex: internal error (partial entry sums without the chain flow)");
-            pa.z2 = planes(z2); pa.q0 = planes(sc.Q0); pa.bias0 = v.bias0;
-        }
+        if (l.z2) { pa.z2 = planes(l.z2); pa.q0 = planes(sc.Q0); pa.bias0 = v.bias0; }
         // grid.x: the tiles (+ the global-average block of the chain flow) rounded up to a multiple of 8 (XCD bands)
-        hipLaunchKernelGGL(pool_pyramid_kernel, dim3(round_up(pa.tiles + (chain_flow ? 1 : 0), 8), (z2 ? 4 : 3) * c4), dim3(256), 0, st, pa);
+        hipLaunchKernelGGL(pool_pyramid_kernel, dim3(round_up(pa.tiles + (chain_flow ? 1 : 0), 8), (l.z2 ? 4 : 3) * c4), dim3(256), 0, st, pa);
         mark_launch("pool_pyramid_kernel", st);
         OJF_HIP(hipGetLastError());
     }
-    const float *bin[4] = {z2 ? sc.Q0 : sc.Z, sc.Q1, sc.Q2, sc.Q3};
-    static const bool unfused = getenv("OJF_NO_TAIL") != nullptr;  // ablation switch only
-    const bool fused = v.tail_w && !unfused;
+    const float *bin[4] = {l.z2 ? sc.Q0 : sc.Z, sc.Q1, sc.Q2, sc.Q3};
     // (measured equal to the two grouped launches, not faster - 82 against 79-80 us per frame, profiles/r04_pair_experiments.txt -
     // so it is opt-in: OJF_BRANCH_KERNEL=1)
     static const bool branch_kernel = getenv("OJF_BRANCH_KERNEL") != nullptr && atoi(getenv("OJF_BRANCH_KERNEL")) != 0;
@@ -2896,12 +2775,10 @@ static int run_vortex(ojf_net *net, Vortex &v, const float *in, int in_g0, float
             fill_conv_args(gb[br], v.b3b[br], sc.U, br * c4, sc.V, br * c4, nullptr, OJF_ACT_RELU, net->cs, 1.0f, h, w);
             ga[br].in_split = ga[br].out_split = gb[br].in_split = split ? 1 : 0;
         }
-        // Legacy flow: branch 0 needs no pooling, its 3x3 pair follows the global-average kernels on the side stream
-        static const bool b0_main = getenv("OJF_BRANCH0_MAIN") != nullptr;  // ablation switch only
-        if (chain_flow || b0_main || net->npix < 32768) {  // (small frames: the stream hand-over costs more than it hides)
+        if (chain_flow || net->npix < 32768) {  // (small frames: the stream hand-over costs more than it hides)
             if (launch_conv_args(ga, 4, v.b3a[0].n_ot, st, net->arith)) return -2;
             if (launch_conv_args(gb, 4, v.b3b[0].n_ot, st, net->arith)) return -2;
-        } else {
+        } else {  // general flow: branch 0 needs no pooling, its 3x3 pair follows the global-average kernels on the side stream
             OJF_HIP(hipStreamWaitEvent(sc.side, sc.ev_entry, 0));
             if (launch_conv_args(ga, 1, v.b3a[0].n_ot, sc.side, net->arith)) return -2;
             if (launch_conv_args(gb, 1, v.b3b[0].n_ot, sc.side, net->arith)) return -2;
@@ -2909,6 +2786,8 @@ static int run_vortex(ojf_net *net, Vortex &v, const float *in, int in_g0, float
             if (launch_conv_args(gb + 1, 3, v.b3b[1].n_ot, st, net->arith)) return -2;
         }
     }
+
+    // ---- tail: the four branch-exit 1x1, the final 1x1 over their concatenation (+ the global-average bias) ---------------
     if (!chain_flow) {
         OJF_HIP(hipEventRecord(sc.ev_join, sc.side));
         OJF_HIP(hipStreamWaitEvent(st, sc.ev_join, 0));  // bias of the final conv is ready
@@ -2918,8 +2797,8 @@ static int run_vortex(ojf_net *net, Vortex &v, const float *in, int in_g0, float
         for (int br = 0; br < 4; ++br)
             if (launch_conv(v.b1[br], sc.V, br * c4, sc.CAT, br * o4, nullptr, OJF_ACT_RELU, net->os, 1.0f, h, w, st))
                 return -2;
+        return launch_conv(v.fin, sc.CAT, 0, out, out_g0, v.bias_final, OJF_ACT_NONE, 0, 1.0f, h, w, st);
     }
-    if (!fused) return launch_conv(v.fin, sc.CAT, 0, out, out_g0, v.bias_final, OJF_ACT_NONE, 0, 1.0f, h, w, st);
     TailArgs ta;
     for (int br = 0; br < 4; ++br) ta.v[br] = planes(sc.V) + (size_t)br * c4 * net->npix;
     ta.w = planes(v.tail_w); ta.b1 = v.tail_b1; ta.bias_final = v.bias_final; ta.rinv_final = v.tail_rinv;
@@ -2929,42 +2808,43 @@ static int run_vortex(ojf_net *net, Vortex &v, const float *in, int in_g0, float
     ta.entry_w = nullptr; ta.entry_b = nullptr; ta.entry_out = nullptr; ta.entry_og = 0; ta.entry_act_n = 0; ta.colsum = nullptr; ta.entry_split = 0;
     // MT = 1: two pixel tiles per wave (324 VGPRs, one wave per SIMD) measured slower (0.624 vs 0.609 ms net)
     const dim3 grid(chain_blocks(net)), block(ojf::kChainThreads);
-    static const bool no_head_fusion = getenv("OJF_NO_HEAD_FUSION") != nullptr;  // ablation switch only
-    static const bool no_entry_fusion = getenv("OJF_NO_ENTRY_FUSION") != nullptr;  // ablation switch only
-    if (head && net->chain_kind && !no_head_fusion) {  // last VortexPooling: the prediction head rides along
-        ta.chain_w = head->w; ta.chain_b = head->bias; ta.out_rows = head->out_rows;
-        ta.rows_stride = head->rows_stride; ta.rows_n = head->rows_n; ta.scale = head->scale;
+    switch (tail) {
+    case TAIL_HEAD:
+        ta.chain_w = l.head->w; ta.chain_b = l.head->bias; ta.out_rows = l.head->out_rows;
+        ta.rows_stride = l.head->rows_stride; ta.rows_n = l.head->rows_n; ta.scale = l.head->scale;
         if (net->chain_kind == 19 && h16) hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F16X3, 1, 2, 8, 19>), grid, block, 0, st, ta);
         else if (net->chain_kind == 19) hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F32, 1, 2, 8, 19>), grid, block, 0, st, ta);
         else if (h16) hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F16X3, 1, 2, 8, 20>), grid, block, 0, st, ta);
         else hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F32, 1, 2, 8, 20>), grid, block, 0, st, ta);
         mark_launch("vortex_tail_kernel (+ prediction head)", st);
-        if (head_done) *head_done = true;
-    } else if (chain_flow && next && half >= 0 && half < 2 && next->entry_wh[half] && next->tail_w && next_colsum && !legacy_env && !no_entry_fusion) {
+        if (l.head_done) *l.head_done = true;
+        break;
+    case TAIL_HALF_ENTRY:
         // two-head net: this head's HALF of the next VortexPooling's entry GEMM rides along (partial sums: no bias, no activation,
         // plain planes); `out` is never written
-        ta.entry_w = planes(next->entry_wh[half]); ta.entry_b = next->entry_bh[half]; ta.entry_out = planes(sc.Z);
-        ta.entry_og = 4 * c4; ta.entry_act_n = 0; ta.colsum = next_colsum; ta.colsum_off = half * net->os;
+        ta.entry_w = planes(l.next->entry_wh[l.half]); ta.entry_b = l.next->entry_bh[l.half]; ta.entry_out = planes(sc.Z);
+        ta.entry_og = 4 * c4; ta.entry_act_n = 0; ta.colsum = l.next_colsum; ta.colsum_off = l.half * net->os;
         ta.entry_split = 0;
         if (h16) hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F16X3, 1, 2, 8, kTailEntry>), grid, block, 0, st, ta);
         else hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F32, 1, 2, 8, kTailEntry>), grid, block, 0, st, ta);
         mark_launch("vortex_tail_kernel (+ half of the next entry GEMM)", st);
-        if (next_done) *next_done = true;
-    } else if (chain_flow && next && next->entry_w && next->tail_w && next->c_in_phys == net->os && !legacy_env && !no_entry_fusion) {
+        if (l.next_done) *l.next_done = true;
+        break;
+    case TAIL_ENTRY:
         // this VortexPooling feeds the next one: its entry GEMM and column sums ride along, `out` is never written
-        ta.entry_w = planes(next->entry_w); ta.entry_b = next->entry_b; ta.entry_out = planes(sc.Z);
+        ta.entry_w = planes(l.next->entry_w); ta.entry_b = l.next->entry_b; ta.entry_out = planes(sc.Z);
         ta.entry_og = 4 * c4; ta.entry_act_n = net->cs; ta.colsum = sc.colsum;
-        ta.entry_split = (h16 && !no_split) ? c4 : 0;  // (the next VortexPooling runs the chain flow: same rule as its `split`)
+        ta.entry_split = h16 ? c4 : 0;  // (the next VortexPooling runs the chain flow: same rule as its `split`)
         if (h16) hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F16X3, 1, 2, 8, kTailEntry>), grid, block, 0, st, ta);
         else hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F32, 1, 2, 8, kTailEntry>), grid, block, 0, st, ta);
         mark_launch("vortex_tail_kernel (+ next entry GEMM)", st);
-        if (next_done) *next_done = true;
-    } else if (h16) {
-        hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F16X3, 1, 2, 8>), grid, block, 0, st, ta);
+        if (l.next_done) *l.next_done = true;
+        break;
+    case TAIL_ALONE:
+        if (h16) hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F16X3, 1, 2, 8>), grid, block, 0, st, ta);
+        else hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F32, 1, 2, 8>), grid, block, 0, st, ta);
         mark_launch("vortex_tail_kernel", st);
-    } else {
-        hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F32, 1, 2, 8>), grid, block, 0, st, ta);
-        mark_launch("vortex_tail_kernel", st);
+        break;
     }
     return check_hip(hipGetLastError(), "vortex_tail_kernel launch");
 }
@@ -2973,9 +2853,8 @@ static int run_dense(ojf_net *net, int head, hipStream_t st)
 {
     const int c4 = net->cs / 4;
     float *T = net->sc[head].T;
-    static const bool no_pair = getenv("OJF_NO_PAIR") != nullptr;  // ablation switch only
     if (net->chain_dense) return launch_chain(net->chains[head], net->X[head], net->h, net->w, st);  // one launch (ojf_net_chain.h)
-    if (!no_pair && (int)net->pairs[head].size() == net->gf) {  // one fused launch per Block (ojf_net_pair.h)
+    if ((int)net->pairs[head].size() == net->gf) {  // one fused launch per Block (ojf_net_pair.h)
         for (int i = 0; i < net->gf; ++i)
             if (launch_pair(net->pairs[head][i], net->X[head], 0, net->X[head], (i + 1) * c4, net->h, net->w, st)) return -2;
         return 0;
@@ -3093,7 +2972,7 @@ OJF_API int ojf_net_create(ojf_net **out, int version, int n_points, int growth,
             net->dense[head].push_back(pb);
             if (net->arith == OJF_ARITH_F16X3 && cs <= 24) {
                 PackedPair pp;
-                if (finish_pair(ba, bb, pp, pair_cfg_for(net->h, net->w, cs))) return -2;
+                if (finish_pair(ba, bb, pp, pair_cfg_for(net->h, net->w))) return -2;
                 net->pairs[head].push_back(pp);
                 bas.push_back(ba);
                 bbs.push_back(bb);
@@ -3162,9 +3041,8 @@ OJF_API int ojf_net_create(ojf_net **out, int version, int n_points, int growth,
     }
     if (!rc) {
         // One dense_chain_kernel launch per head instead of gf dense_pair_kernel launches: the dense-growth buffers then hold
-        // split planes, which only the chain-flow entry kernel reads (OJF_NO_DENSE_CHAIN=1 / the legacy flow: pair kernels)
-        static const bool no_chain = getenv("OJF_NO_DENSE_CHAIN") != nullptr || getenv("OJF_LEGACY_VORTEX") != nullptr ||
-                                     getenv("OJF_NO_PAIR") != nullptr;
+        // split planes, which only the chain-flow entry kernel reads (OJF_NO_DENSE_CHAIN=1 / the general flow: pair kernels)
+        static const bool no_chain = getenv("OJF_NO_DENSE_CHAIN") != nullptr;
         bool ok = net->arith == OJF_ARITH_F16X3 && !no_chain;
         {
             //  frames the chain kernel is not the right tool for fall back to one dense_pair_kernel launch per Block:
@@ -3295,9 +3173,8 @@ static double spin_pair_us(hipStream_t a, hipStream_t b, long long cycles)
 }
 
 // makes `s` a stream that overlaps with every stream of `others` (replaces it by fresh ones until the test passes)
-static void pair_stream(hipStream_t &s, const hipStream_t *others, int n, double alone, long long cycles, const char *what)
+static void pair_stream(hipStream_t &s, const hipStream_t *others, int n, double alone, long long cycles)
 {
-    static const bool dbg = getenv("OJF_DEBUG_STREAMS") != nullptr;
     std::vector<hipStream_t> rejected;
     for (int attempt = 0; attempt < 8; ++attempt) {
         double worst = 0.0;
@@ -3305,7 +3182,6 @@ static void pair_stream(hipStream_t &s, const hipStream_t *others, int n, double
             const double both = spin_pair_us(others[k], s, cycles);
             worst = both > worst ? both : worst;
         }
-        if (dbg) fprintf(stderr, "ojf: %s stream, attempt %d: one spin %.0f us, one per stream %.0f us\n", what, attempt, alone, worst);
         if (worst < 1.5 * alone) break;  // overlaps with all of them
         // the replacement is created while the rejected streams still exist: a stream created right after a destroy
         // gets the freed queue slot again
@@ -3351,11 +3227,11 @@ static void pair_head_stream(ojf_net *net, hipStream_t st)
     const long long cycles = 300000;  // ~130 us
     (void)spin_pair_us(st, st, 1000);  // (the first launch of the kernel in a process loads its code object: not in the yardstick)
     const double alone = spin_pair_us(st, st, cycles) * 0.5;  // two spins back to back on one stream
-    pair_stream(net->head1, &st, 1, alone, cycles, "second head");
-    // the side streams of the legacy VortexPooling flow (global-average branch, branch 0): each must overlap with the
+    pair_stream(net->head1, &st, 1, alone, cycles);
+    // the side streams of the general VortexPooling flow (global-average branch, branch 0): each must overlap with the
     // stream of ITS head (only three queues ran concurrently in every test, so four-way distinctness is not asked for)
-    if (net->sc[1].side) pair_stream(net->sc[1].side, &net->head1, 1, alone, cycles, "head 1 side");
-    if (net->sc[0].side) pair_stream(net->sc[0].side, &st, 1, alone, cycles, "head 0 side");
+    if (net->sc[1].side) pair_stream(net->sc[1].side, &net->head1, 1, alone, cycles);
+    if (net->sc[0].side) pair_stream(net->sc[0].side, &st, 1, alone, cycles);
 }
 
 // every launch of one forward pass, in order, on `st` (+ the side stream, forked and joined with events)
@@ -3363,19 +3239,19 @@ static int forward_launches(ojf_net *net, float *est, int est_stride, hipStream_
 {
     const int o4 = net->os / 4;
     // prediction head: 1x1 chain; BN-folded LeakyReLU stages, the last layer is Tanh * output_scale
-    static const bool unfused = getenv("OJF_NO_CHAIN") != nullptr;  // ablation switch only
     ChainArgs ca;
     ca.in = planes(net->Y3); ca.w = planes(net->chain_w); ca.bias = net->chain_b;
     ca.out_rows = est; ca.in_g0 = 0; ca.c4_in = o4; ca.npix = net->npix;
     ca.rows_stride = est_stride; ca.rows_n = net->P; ca.scale = net->scale;
     ca.ovf = net->arith == OJF_ARITH_F16X3 ? overflow_flag() : nullptr;
-    const ChainArgs *head = (net->chain_kind && !unfused) ? &ca : nullptr;
     bool head_done = false;  // set when the last VortexPooling's tail kernel ran the head as well
-    static const bool serial_heads = getenv("OJF_SERIAL_HEADS") != nullptr;  // ablation switch only
+    VortexLinks last;        // links of the last VortexPooling: the head rides along where the tail can carry it
+    last.head = net->chain_kind ? &ca : nullptr;
+    last.head_done = &head_done;
     if (net->version == 3) {
         const bool two = net->heads == 2;
-        if (two && !serial_heads) pair_head_stream(net, st);
-        hipStream_t s1 = (two && !serial_heads) ? net->head1 : st;
+        if (two) pair_head_stream(net, st);
+        hipStream_t s1 = two ? net->head1 : st;
         if (two && s1 != st) {  // the semantic head runs beside the geometric one
             OJF_HIP(hipEventRecord(net->ev_head_fork, st));
             OJF_HIP(hipStreamWaitEvent(s1, net->ev_head_fork, 0));
@@ -3385,43 +3261,41 @@ static int forward_launches(ojf_net *net, float *est, int est_stride, hipStream_
         bool done1 = false;
         if (two) {
             if (run_dense(net, 1, s1)) return -2;
-            if (run_vortex(net, net->vortex[1], net->X[1], 0, net->YY, o4, s1, net->sc[1], nullptr, nullptr, false,
-                           halves ? &net->vortex[2] : nullptr, &done1, net->chain_dense, halves ? 1 : -1, net->colsum3)) return -2;
+            VortexLinks l1;
+            l1.in_split = net->chain_dense;
+            if (halves) { l1.next = &net->vortex[2]; l1.next_done = &done1; l1.half = 1; l1.next_colsum = net->colsum3; }
+            if (run_vortex(net, net->vortex[1], net->X[1], 0, net->YY, o4, s1, net->sc[1], l1)) return -2;
         }
         if (run_dense(net, 0, st)) return -2;
         bool entry_done = false;  // single head: vortex0's tail runs vortex3's entry GEMM (its own output is never written)
-        if (run_vortex(net, net->vortex[0], net->X[0], 0, net->YY, 0, st, net->sc[0], nullptr, nullptr, false,
-                       (two && !halves) ? nullptr : &net->vortex[2], &entry_done, net->chain_dense, halves ? 0 : -1, halves ? net->colsum3 : net->sc[0].colsum)) return -2;
+        VortexLinks l0;
+        l0.in_split = net->chain_dense;
+        if (halves) { l0.next = &net->vortex[2]; l0.half = 0; l0.next_colsum = net->colsum3; }
+        else if (!two) l0.next = &net->vortex[2];
+        l0.next_done = &entry_done;
+        if (run_vortex(net, net->vortex[0], net->X[0], 0, net->YY, 0, st, net->sc[0], l0)) return -2;
         if (two && s1 != st) {
             OJF_HIP(hipEventRecord(net->ev_head_join, s1));
             OJF_HIP(hipStreamWaitEvent(st, net->ev_head_join, 0));
         }
         if (halves && entry_done != done1) return fail("ojf_net_forward: internal error (one head ran its half of the entry GEMM, the other did not)");
-        if (run_vortex(net, net->vortex[2], net->YY, 0, net->Y3, 0, st, net->sc[0], head, &head_done, entry_done, nullptr, nullptr, false, -1,
-                       nullptr, (halves && entry_done) ? net->sc[1].Z : nullptr)) return -2;
+        last.entry_done = entry_done;
+        last.z2 = (halves && entry_done) ? net->sc[1].Z : nullptr;
+        if (run_vortex(net, net->vortex[2], net->YY, 0, net->Y3, 0, st, net->sc[0], last)) return -2;
     } else {
         if (run_dense(net, 0, st)) return -2;
         bool entry_done = false;
-        if (run_vortex(net, net->vortex[0], net->X[0], 0, net->YY, 0, st, net->sc[0], nullptr, nullptr, false, &net->vortex[2],
-                       &entry_done, net->chain_dense)) return -2;
-        if (run_vortex(net, net->vortex[2], net->YY, 0, net->Y3, 0, st, net->sc[0], head, &head_done, entry_done)) return -2;
+        VortexLinks l0;
+        l0.in_split = net->chain_dense;
+        l0.next = &net->vortex[2];
+        l0.next_done = &entry_done;
+        if (run_vortex(net, net->vortex[0], net->X[0], 0, net->YY, 0, st, net->sc[0], l0)) return -2;
+        last.entry_done = entry_done;
+        if (run_vortex(net, net->vortex[2], net->YY, 0, net->Y3, 0, st, net->sc[0], last)) return -2;
     }
     if (head_done) return 0;
-    if (net->chain_kind && !unfused) {
-        // stand-alone head (the tail fusion is off or unavailable); one pixel tile per wave: two measured slower
-        const bool h16 = net->arith == OJF_ARITH_F16X3;
-        const dim3 grid(chain_blocks(net)), block(ojf::kChainThreads);
-        if (net->chain_kind == 19 && h16)
-            hipLaunchKernelGGL((chain1x1_kernel<OJF_ARITH_F16X3, 1, 8, 6, 6, 5, 5, 4, 4, 3, 3, 2, 2, 1>), grid, block, 0, st, ca);
-        else if (net->chain_kind == 19)
-            hipLaunchKernelGGL((chain1x1_kernel<OJF_ARITH_F32, 1, 8, 6, 6, 5, 5, 4, 4, 3, 3, 2, 2, 1>), grid, block, 0, st, ca);
-        else if (h16)
-            hipLaunchKernelGGL((chain1x1_kernel<OJF_ARITH_F16X3, 1, 8, 7, 7, 5, 5, 4, 4, 3, 3, 2, 2, 1>), grid, block, 0, st, ca);
-        else
-            hipLaunchKernelGGL((chain1x1_kernel<OJF_ARITH_F32, 1, 8, 7, 7, 5, 5, 4, 4, 3, 3, 2, 2, 1>), grid, block, 0, st, ca);
-        mark_launch("chain1x1_kernel", st);
-        return check_hip(hipGetLastError(), "chain1x1_kernel launch");
-    }
+    // (a net with a chain-form head - chain_kind - has fused tails, and the last one ran the head: ojf_net_create)
+    if (net->chain_kind) return fail("ojf_net_forward: internal error (the last tail did not run the prediction head)");
     const float *pin = net->Y3;
     const int np = (int)net->pred.size();
     if (ensure_planes(&net->PA, (size_t)net->npix, net->os) || ensure_planes(&net->PB, (size_t)net->npix, net->os)) return -2;

@@ -73,7 +73,6 @@ struct ChainDenseArgs {
                       // [kChainFlags0 + tile] epoch + Blocks completed on that tile
     int layers;
     int h, w_img, npix, tiles_x, tiles_y;
-    int xcd_bands;
     int *ovf;         // split-fp16 range guard flag
 #ifdef OJF_CHAIN_TIMING
     long long *dbg;

@@ -31,27 +31,18 @@ namespace ojf {
 constexpr int pair_round16(int x) { return (x + 15) / 16 * 16; }
 constexpr int pair_max(int a, int b) { return a > b ? a : b; }
 
-// Two shapes of the same kernel:
-//   <TW, TH, 16, 4, false>  one 16-wave block per CU (143 KB of LDS at 20 x 16): four waves per SIMD take turns through the
-//                           load / split / epilogue phases of the ONE block a CU holds (8 waves 101 us, 12 waves 95 us, 16
-//                           waves 90 us per frame) - but all blocks of a launch fetch, compute and store in the same phases
-//   <TW, TH, 8, CP, true>   round 4: 8-wave blocks small enough for TWO per CU (<= 80 KB: chunks of CP = 3 channel pairs,
-//                           the T planes alias the window planes - the window is dead once conv a has finished), so that one
-//                           block's fetch / split / barrier phases run beside the other's MFMA phase
-//   <..., PACK = true>      round 4: FIVE MFMAs per (K block, pixel tile) instead of six.  The 19 (20 padded) output channels
-//                           occupy 2 x 16 MFMA rows per weight half = 4 row tiles for the hi and lo halves, 41 % of them
-//                           padding.  Packed, the 20 hi rows and the 20 lo rows are 40 consecutive rows = 3 row tiles:
-//                           x_hi meets all three (w_hi x_hi and w_lo x_hi), x_lo the two that hold hi rows (w_hi x_lo;
-//                           the lo rows riding along add w_lo x_lo, the term the split otherwise drops).  The epilogue
-//                           adds the hi-row and lo-row accumulators of a channel group (they sit 5 lane groups apart).
-//                           The K loops of this kernel run at ~89 % of the matrix pipe (s_memtime stamps,
-//                           profiles/r04_pair_stamps.txt), so the sixth MFMA was the bound.
-template <int TW, int TH, int WAVES_ = 16, int CP_ = 4, bool ALIAS_ = false, bool PACK_ = false>
+// One 16-wave block per CU (143 KB of LDS at 20 x 16): four waves per SIMD take turns through the load / split / epilogue
+// phases of the ONE block a CU holds (8 waves 101 us, 12 waves 95 us, 16 waves 90 us per frame).  Round 4 measured two other
+// shapes against it - 8-wave blocks small enough for two per CU (chunks of 3 channel pairs, the T planes aliasing the window),
+// and "packed rows" (five MFMAs per K block and pixel tile instead of six) - and neither won a frame size (DESIGN.md 5.0,
+// profiles/r04_pair_experiments.txt); they left the tree with the switch that selected them.
+constexpr int kPairWaves = 16;
+template <int TW, int TH>
 struct PairGeom {
-    static constexpr int WAVES = WAVES_, THREADS = 64 * WAVES, CP = CP_;
-    static constexpr bool ALIAS = ALIAS_, PACK = PACK_;
-    static constexpr int WT = PACK ? 3 : 4;               // weight float4 per lane and K block: 3 packed row tiles, or 2 x (hi, lo)
-    static constexpr int NACC = PACK ? 3 : 2;             // accumulator tiles per pixel tile
+    static constexpr int WAVES = kPairWaves, THREADS = 64 * WAVES;
+    static constexpr int CP = 4;                           // channel pairs of a full chunk (PackedPair is packed for it)
+    static constexpr int WT = 4;                           // weight float4 per lane and K block: 2 x (hi, lo)
+    static constexpr int NACC = 2;                         // accumulator tiles per pixel tile
     static constexpr int NKB = (9 * CP + 3) / 4;           // K blocks of a full chunk
     static constexpr int PW = TW + 4;                      // slot pitch = window width
     static constexpr int XS = (TH + 4) * PW;               // window slots
@@ -64,12 +55,11 @@ struct PairGeom {
     static constexpr int TP = pair_round16(pair_max(TILES_A * 16, TILES_B * 16 + 2 * PW + 2));
     // float4 counts of the three LDS areas (conv b always has 3 pairs = 7 K blocks of weights)
     static constexpr int X_F4 = CP * 2 * XP, T_F4 = 3 * 2 * TP, W_F4 = pair_max(NKB, 7) * 64 * WT;
-    static constexpr int XT_F4 = ALIAS ? pair_max(X_F4, T_F4) : X_F4 + T_F4;
+    static constexpr int XT_F4 = X_F4 + T_F4;
     static constexpr int NXI = (CP * XS + THREADS - 1) / THREADS;  // window items (pair, slot) per thread and chunk
     static constexpr int NWI = (W_F4 + THREADS - 1) / THREADS;     // weight float4 per thread and chunk
     static constexpr int NPRE = NXI > NWI ? NXI : NWI;
     static constexpr size_t LDS_BYTES = (size_t)(XT_F4 + W_F4) * 16 + 128 * sizeof(int) + 128 * sizeof(float);
-    static constexpr int BLOCKS_PER_CU = LDS_BYTES <= 80 * 1024 && WAVES <= 8 ? 2 : 1;
 };
 
 struct PairArgs {
@@ -82,7 +72,6 @@ struct PairArgs {
     int h, w, npix, tiles_x;
     int n_chunks, np_last;  // chunks of CP channel pairs; pairs in the last chunk (1..CP)
     int np_b;               // channel pairs of the intermediate (1..3)
-    int xcd_bands;          // 1: tile = xcd_band_block(blockIdx.x) (tuning switch)
     int *ovf;               // split-fp16 range guard flag
 #ifdef OJF_PAIR_TIMING
     long long *dbg;         // profiling builds only (tools/microbench/pair_bench.hip): s_memtime stamps of block 0
@@ -101,79 +90,39 @@ __device__ __forceinline__ void pair_split(const f32x4 &a, const f32x4 &b, f32x4
 // acc[m][n] += W[K block][n] * act[unit(K block, g)][slot[m] + tap] over `nkb` K blocks
 // `hook(S)` runs once per K block before its MFMAs: the caller trickles the next chunk's global loads through it (a
 // burst of 13 loads per lane at the top of the loop stalled the in-order waves at issue until the memory queue drained)
-template <int MT, int PLANE, int NACC, class Hook>
-__device__ __forceinline__ void pair_mac(f32x4 (&acc)[MT][NACC], const f32x4 *act, const int *uo, int nkb, const f32x4 *wl,
+template <int MT, int PLANE, class Hook>
+__device__ __forceinline__ void pair_mac(f32x4 (&acc)[MT][2], const f32x4 *act, const int *uo, int nkb, const f32x4 *wl,
                                          const int (&slot)[MT], int mt_wave, int lane, int g, Hook hook)
 {
     for (int S = 0; S < nkb; ++S) {
         hook(S);
         const int off = uo[4 * S + g];
-        if constexpr (NACC == 2) {
-            f32x4 wh[2], wlo[2];
+        f32x4 wh[2], wlo[2];
 #pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                wh[n] = wl[(S * 2 + n) * 128 + lane];
-                wlo[n] = wl[(S * 2 + n) * 128 + 64 + lane];
-            }
+        for (int n = 0; n < 2; ++n) {
+            wh[n] = wl[(S * 2 + n) * 128 + lane];
+            wlo[n] = wl[(S * 2 + n) * 128 + 64 + lane];
+        }
 #pragma unroll
-            for (int m = 0; m < MT; ++m) {
-                if (m < mt_wave) {  // wave-uniform
-                    const f16x8 xh = __builtin_bit_cast(f16x8, act[off + slot[m]]);
-                    const f16x8 xl = __builtin_bit_cast(f16x8, act[off + PLANE + slot[m]]);
+        for (int m = 0; m < MT; ++m) {
+            if (m < mt_wave) {  // wave-uniform
+                const f16x8 xh = __builtin_bit_cast(f16x8, act[off + slot[m]]);
+                const f16x8 xl = __builtin_bit_cast(f16x8, act[off + PLANE + slot[m]]);
 #pragma unroll
-                    for (int n = 0; n < 2; ++n) acc[m][n] = mfma_f16x3(wh[n], wlo[n], xh, xl, acc[m][n]);
-                }
-            }
-        } else {  // packed rows: tile 0 = hi rows 0..15, tile 1 = hi rows 16..19 | lo rows 0..11, tile 2 = lo rows 12..19
-            f16x8 w[3];
-#pragma unroll
-            for (int t = 0; t < 3; ++t) w[t] = __builtin_bit_cast(f16x8, wl[(S * 3 + t) * 64 + lane]);
-#pragma unroll
-            for (int m = 0; m < MT; ++m) {
-                if (m < mt_wave) {  // wave-uniform
-                    const f16x8 xh = __builtin_bit_cast(f16x8, act[off + slot[m]]);
-                    const f16x8 xl = __builtin_bit_cast(f16x8, act[off + PLANE + slot[m]]);
-                    // (small terms first, like mfma_f16x3)
-                    acc[m][2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[2], xh, acc[m][2], 0, 0, 0);
-                    acc[m][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[1], xl, acc[m][1], 0, 0, 0);
-                    acc[m][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[0], xl, acc[m][0], 0, 0, 0);
-                    acc[m][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[1], xh, acc[m][1], 0, 0, 0);
-                    acc[m][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[0], xh, acc[m][0], 0, 0, 0);
-                }
+                for (int n = 0; n < 2; ++n) acc[m][n] = mfma_f16x3(wh[n], wlo[n], xh, xl, acc[m][n]);
             }
         }
     }
 }
 
-// Packed rows (PairGeom PACK), 20 physical output channels: channel group og's hi rows are packed group og, its lo rows packed
-// group og + 5; lane (i16, g) of accumulator tile t holds packed group 4 t + g.  Returns hi + lo of group g in `main` (every
-// lane) and of group 4 in `extra` (meaningful in lanes g == 0).
-__device__ __forceinline__ void pair_unpack5(const f32x4 (&acc)[3], int lane, int i16, int g, f32x4 &main, f32x4 &extra)
+template <int TW, int TH>
+__global__ __launch_bounds__(64 * kPairWaves, kPairWaves / 4) void dense_pair_kernel(const PairArgs a)
 {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        // (through float temporaries: __builtin_bit_cast applied to a vector ELEMENT lvalue reads element 0 whatever the index
-        // - hipcc 7.2 - and all four exchanges collapse into one)
-        const float f1 = acc[1][j], f2 = acc[2][j];
-        const int a1 = __float_as_int(f1), a2 = __float_as_int(f2);
-        const int up1 = __builtin_amdgcn_ds_bpermute(((lane + 16) & 63) * 4, a1);  // tile 1, lane group g + 1: lo rows of groups 0..2
-        const int lo3 = __builtin_amdgcn_ds_bpermute(i16 * 4, a2);                 // tile 2, lane group 0: lo rows of group 3
-        const int up2 = __builtin_amdgcn_ds_bpermute(((lane + 16) & 63) * 4, a2);  // tile 2, lane group 1: lo rows of group 4
-        main[j] = acc[0][j] + __int_as_float(g < 3 ? up1 : lo3);
-        extra[j] = f1 + __int_as_float(up2);
-    }
-}
-
-template <int TW, int TH, int WAVES, int CP, bool ALIAS, bool PACK>
-__global__ __launch_bounds__(64 * WAVES, (WAVES / 4) * (WAVES <= 8 ? 2 : 1))  // (8-wave blocks: two per CU, <= 128 VGPRs)
-void dense_pair_kernel(const PairArgs a)
-{
-    using G = PairGeom<TW, TH, WAVES, CP, ALIAS, PACK>;
-    static_assert(WAVES > 8 || G::BLOCKS_PER_CU == 2, "8-wave shapes must fit two blocks into a CU's LDS");
-    constexpr int PW = G::PW, XP = G::XP, TP = G::TP;
+    using G = PairGeom<TW, TH>;
+    constexpr int PW = G::PW, XP = G::XP, TP = G::TP, CP = G::CP;
     extern __shared__ f32x4 pair_lds[];
     f32x4 *xl = pair_lds;                          // [CP pairs][hi | lo][XP]
-    f32x4 *tl = ALIAS ? xl : xl + G::X_F4;         // [3 pairs][hi | lo][TP] (ALIAS: over the window, once conv a is done)
+    f32x4 *tl = xl + G::X_F4;                      // [3 pairs][hi | lo][TP]
     f32x4 *wl = pair_lds + G::XT_F4;               // one chunk of weights
     int *uo = reinterpret_cast<int *>(wl + G::W_F4);  // unit tables: [0] full chunk, [1] last chunk, [2] conv b
     float *vl = reinterpret_cast<float *>(uo + 128);  // bias_a | rinv_a | bias_b | rinv_b (their global latency hides behind conv a)
@@ -181,7 +130,7 @@ void dense_pair_kernel(const PairArgs a)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i16 = lane & 15, g = lane >> 4;
     // (tile rows banded over the XCDs when the grid allows it: neighbouring tiles share their halo rows in one L2)
-    const int tile = (gridDim.x & 7) == 0 && a.xcd_bands ? xcd_band_block(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int tile = (gridDim.x & 7) == 0 ? xcd_band_block(blockIdx.x, gridDim.x) : (int)blockIdx.x;
     const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
     const int x0 = tx * TW, y0 = ty * TH;
     const int last = a.n_chunks - 1, nkb_b = (9 * a.np_b + 3) >> 2;
@@ -206,17 +155,14 @@ void dense_pair_kernel(const PairArgs a)
     if (tid >= 128 && tid < 160)  // the four epilogue vectors are contiguous (PackedPair::vec)
         reinterpret_cast<f32x4 *>(vl)[tid - 128] = reinterpret_cast<const f32x4 *>(a.bias_a)[tid - 128];
     // the T planes' tails (slots a junk output column may read; conv a writes every slot below) must hold finite values
-    auto zero_t_tails = [&]() {
-        constexpr int TAIL = TP - G::TILES_A * 16;
-        if constexpr (TAIL > 0) {
-            if (tid >= 192 && tid < 192 + 6 * TAIL) {
-                const int i = tid - 192, pl = i / TAIL, sl = i - pl * TAIL;
-                tl[pl * TP + G::TILES_A * 16 + sl] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
+    constexpr int TAIL = TP - G::TILES_A * 16;
+    static_assert(192 + 6 * TAIL <= G::THREADS, "T tail fill needs more threads");
+    if constexpr (TAIL > 0) {
+        if (tid >= 192 && tid < 192 + 6 * TAIL) {
+            const int i = tid - 192, pl = i / TAIL, sl = i - pl * TAIL;
+            tl[pl * TP + G::TILES_A * 16 + sl] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
-    };
-    static_assert(192 + 6 * (TP - G::TILES_A * 16) <= G::THREADS, "T tail fill needs more threads");
-    if constexpr (!ALIAS) zero_t_tails();
+    }
 
     // ---- window items of this thread: (pair, slot) -> byte offset of the pixel (or out of range) -----------------
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
@@ -291,7 +237,7 @@ void dense_pair_kernel(const PairArgs a)
         const bool more = c < last;
         const f32x4 *nsrc = more ? wsrc : a.wb;
         const int n_f4 = more ? nkb_of(c + 1) * wf4 : nkb_b * wf4;
-        pair_mac<G::MT_A, XP, G::NACC>(acc, xl, uo + (c == last ? 36 : 0), nkb, wl, slot_a, mt_a, lane, g,
+        pair_mac<G::MT_A, XP>(acc, xl, uo + (c == last ? 36 : 0), nkb, wl, slot_a, mt_a, lane, g,
                               [&](int S) { if (S < G::NPRE) prefetch_piece(S, c + 1, more, nsrc, n_f4); });
 #pragma unroll
         for (int k = 0; k < G::NPRE; ++k)
@@ -299,13 +245,6 @@ void dense_pair_kernel(const PairArgs a)
     }
 
     OJF_STAMP();  // conv a done
-    if constexpr (ALIAS) {  // the window is dead: T takes its place, conv b's weights take conv a's
-        __syncthreads();
-        zero_t_tails();
-#pragma unroll
-        for (int k = 0; k < G::NWI; ++k)
-            if (k * G::THREADS + tid < nkb_b * 64 * G::WT) wl[k * G::THREADS + tid] = wpre[k];
-    }
     // epilogue a: bias, LeakyReLU, zero outside the image / the needed region, split, into the T planes
     float gmax = 0.0f;
     {
@@ -339,32 +278,19 @@ void dense_pair_kernel(const PairArgs a)
                 *dh = __builtin_bit_cast(uint2, h4);
                 *dl = l4;
             };
-            if constexpr (G::PACK) {
-                f32x4 main, extra;
-                pair_unpack5(acc[m], lane, i16, g, main, extra);
-                put_t(g, main, rv[0], bv[0]);
-                if (g == 0) put_t(4, extra, rv[1], bv[1]);
-                if (g == 1) {  // group 5 = padding channels 20..23 of the third pair: zeros
-                    reinterpret_cast<uint2 *>(tl + 2 * 2 * TP + s)[1] = uint2{0u, 0u};
-                    reinterpret_cast<uint2 *>(tl + 2 * 2 * TP + TP + s)[1] = uint2{0u, 0u};
-                }
-            } else {
 #pragma unroll
-                for (int n = 0; n < 2; ++n) {
-                    if (2 * n + (g >> 1) >= 3) continue;
-                    put_t(4 * n + g, acc[m][n], rv[n], bv[n]);
-                }
+            for (int n = 0; n < 2; ++n) {
+                if (2 * n + (g >> 1) >= 3) continue;
+                put_t(4 * n + g, acc[m][n], rv[n], bv[n]);
             }
         }
     }
     OJF_STAMP();  // epilogue a done
     __syncthreads();  // T complete, conv a's weights no longer read
-    if constexpr (!ALIAS) {
 #pragma unroll
-        for (int k = 0; k < G::NWI; ++k)
-            if (k * G::THREADS + tid < nkb_b * 64 * G::WT) wl[k * G::THREADS + tid] = wpre[k];
-        __syncthreads();
-    }
+    for (int k = 0; k < G::NWI; ++k)
+        if (k * G::THREADS + tid < nkb_b * 64 * G::WT) wl[k * G::THREADS + tid] = wpre[k];
+    __syncthreads();
 
     OJF_STAMP();  // conv b weights in place
     // ---- conv b ----------------------------------------------------------------------------------------------
@@ -377,7 +303,7 @@ void dense_pair_kernel(const PairArgs a)
     for (int m = 0; m < G::MT_B; ++m)
 #pragma unroll
         for (int n = 0; n < G::NACC; ++n) accb[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-    pair_mac<G::MT_B, TP, G::NACC>(accb, tl, uo + 72, nkb_b, wl, slot_b, mt_b, lane, g, [](int) {});
+    pair_mac<G::MT_B, TP>(accb, tl, uo + 72, nkb_b, wl, slot_b, mt_b, lane, g, [](int) {});
     OJF_STAMP();  // conv b done
     {
         f32x4 bv[2], rv[2];
@@ -400,15 +326,8 @@ void dense_pair_kernel(const PairArgs a)
                 gmax = guard_max(gmax, lin);
                 a.out[(size_t)(a.out_g0 + og) * a.npix + p] = leaky_max4(lin, 0.01f);
             };
-            if constexpr (G::PACK) {
-                f32x4 main, extra;
-                pair_unpack5(accb[m], lane, i16, g, main, extra);  // (every lane takes part in the exchanges)
-                put_o(g, main, rv[0], bv[0]);
-                if (g == 0) put_o(4, extra, rv[1], bv[1]);
-            } else {
 #pragma unroll
-                for (int n = 0; n < 2; ++n) put_o(4 * n + g, accb[m][n], rv[n], bv[n]);
-            }
+            for (int n = 0; n < 2; ++n) put_o(4 * n + g, accb[m][n], rv[n], bv[n]);
         }
     }
     if (gmax > 65504.0f && a.ovf) guard_raise(a.ovf, 1);

@@ -18,17 +18,14 @@
 // Operands come straight from global memory through L1 (buffer loads; out-of-image taps are out-of-range offsets that
 // return zeros), three K blocks in flight per wave in a branch-free loop.  Channel slices of a wider tensor
 // (concatenations) are addressed by pointer + row stride.  Transposed convolutions: see ojf_segdeconv_create.
-// Tuning-only environment switches: OJF_SEG_MW, OJF_SEG_NO_WIDE, OJF_SEG_WIDE_MIN.
+// Environment: OJF_SEG_TRACE=1 prints one line per launch (form, shape, grid) to stderr; the thresholds of the form choice are
+// the named constants in front of seg_launch.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
 #include "ojf_common.h"
-
-#ifndef OJF_GEMM_ABL
-#define OJF_GEMM_ABL 0
-#endif
 
 namespace ojf {
 
@@ -119,7 +116,7 @@ struct SegMap { int X, Y, Z, S, chunk, V; };
 // (heterogeneous launches - ojf_segconv_forward_multi - : every member has its own map; member z owns the blocks
 // [off[z], off[z + 1]) of the 1-D grid, each range a multiple of 8 so that a block's XCD is the same in both numberings)
 struct SegHetero { int n; int off[kSegGroup + 1]; SegMap map[kSegGroup]; };
-struct SegGroupArgs { SegArgs a[kSegGroup]; SegMap map; SegHetero het; int abl; };  // abl: ablation bits of segconv_gemm_kernel (tools/ only, 0 in production)
+struct SegGroupArgs { SegArgs a[kSegGroup]; SegMap map; SegHetero het; };
 
 __device__ __forceinline__ bool seg_block_map(const SegMap &m, int b, int &bx, int &by, int &bz);
 
@@ -138,13 +135,6 @@ __device__ __forceinline__ bool seg_block(const SegGroupArgs &g, int &bx, int &b
 
 __device__ __forceinline__ bool seg_block_map(const SegMap &m, int b, int &bx, int &by, int &bz)
 {
-    if (m.S == 0) {  // plain numbering (OJF_SEG_XCD=0: A/B switch)
-                bx = b % m.X;
-        const int q = b / m.X;
-        by = q % m.Y;
-        bz = q / m.Y;
-        return true;
-    }
     const int xcd = b & 7, slot = b >> 3;
     const int vl = slot / m.chunk, xl = slot - vl * m.chunk;
     const int v = vl * 8 + xcd;
@@ -431,13 +421,13 @@ __global__ __launch_bounds__(KS > 4 ? 64 * KS : 256) void segconv_kernel(const S
 // 32 pixels each, and the weight fragments of a K block reach them through LDS (LDS-DMA, 8 KB per K block, three
 // stages): one global fetch per block instead of one per wave.  With per-wave fetches these layers were bound by
 // L1 (12 KB per wave per K block against 24 MFMAs); B operands stay per-wave buffer loads.
-template <int NW, int D>
+template <int NW>
 __global__ __launch_bounds__(256) void segconv_wide_kernel(const SegGroupArgs grp)
 {
     int bx, by, bz;
     if (!seg_block(grp, bx, by, bz)) return;  // block-uniform
     const SegArgs &a = grp.a[bz];
-    constexpr int MW = 4;  // D = stages of the weight ring / K blocks of pixel operands in flight per wave
+    constexpr int MW = 4, D = 3;  // D = stages of the weight ring / K blocks of pixel operands in flight per wave (6 and 8 measured no faster)
     __shared__ f32x4 wtile[D][MW * 2 * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ct0 = by * MW;
@@ -538,135 +528,6 @@ __global__ __launch_bounds__(256) void segconv_wide_kernel(const SegGroupArgs gr
     seg_epilogue<MW, NW>(a, acc, ct0, pt0, n_pix, col, kg, rvs, bvs);
 }
 
-// The same tile as segconv_wide_kernel (64 output channels x 4 waves x NW pixel tiles, weights shared through LDS), with the
-// weight fragments staged through REGISTERS instead of LDS-DMA (round 5).  A wave's `global_load_lds` instructions do not
-// overlap: the second one issues when the first has returned (tools/microbench/dma_issue_bench.hip, round 4), so the wide
-// kernel paid two memory latencies per K block whatever its ring depth - 1 us per K block on a 60x80 decoder layer, 71 us
-// for 72 K blocks where the MFMAs need 12.  Plain loads do not block: every wave keeps P K blocks of its two weight chunks
-// and of its pixel operands in flight in registers, writes the chunks of block i + 1 into the other half of a two-slot LDS
-// tile while block i is multiplied, one barrier per K block.
-template <int NW, int U>
-__global__ __launch_bounds__(256) void segconv_tile_kernel(const SegGroupArgs grp)
-{
-    int bx, by, bz;
-    if (!seg_block(grp, bx, by, bz)) return;  // block-uniform
-    const SegArgs &a = grp.a[bz];
-    // U K blocks per step (= per barrier): with one wave per SIMD - what these launches have - the phases of a step (wait,
-    // LDS write, split, loads, LDS reads, MFMAs, barrier) run one after the other, ~1300 cycles per K block at U = 1 for 192
-    // cycles of MFMAs (SQ counters, round 5); a longer step amortises the waits and lets the LDS reads of one K block sit
-    // under the MFMAs of the one before.  P steps in flight per wave.
-    constexpr int MW = 4, P = 2;
-    __shared__ f32x4 wtile[2][U][MW * 2 * 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int ct0 = by * MW;
-    const int pt0 = (bx * 4 + wave) * NW;
-    const int n_pix = a.B * a.Ho * a.Wo;
-    const int col = lane & 15, kg = lane >> 4;
-    const int n_kb = a.n_kb;
-
-    int iy0[NW], ix0[NW], img0[NW];
-    bool live[NW];
-#pragma unroll
-    for (int n = 0; n < NW; ++n) {
-        const int p = (pt0 + n) * 16 + col;
-        live[n] = p < n_pix;
-        const int b = p / (a.Ho * a.Wo), q = p - b * (a.Ho * a.Wo);  // image, pixel inside it
-        const int oy = q / a.Wo, ox = q - oy * a.Wo;
-        iy0[n] = oy * a.stride - a.pad;
-        ix0[n] = ox * a.stride - a.pad;
-        img0[n] = b * a.H * a.W;
-    }
-    int tap = kg / a.c8, cg = kg - tap * a.c8;
-    int ty = tap / a.ksize, tx = tap - ty * a.ksize;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.in), 0, a.in_bytes, 0x00020000);
-
-    f32x4 rvs[MW], bvs[MW];
-    seg_vectors<MW>(a, ct0, kg, rvs, bvs);
-    f32x4 acc[MW][NW];
-#pragma unroll
-    for (int m = 0; m < MW; ++m)
-#pragma unroll
-        for (int n = 0; n < NW; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // wave w stages chunks w and w + 4 of the 8 one-KB chunks (channel tile m, half h) of a K block
-    const f32x4 *wsrc[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const int c = wave + 4 * r, m = c >> 1, h = c & 1;
-        wsrc[r] = a.wp + (size_t)(ct0 + m) * n_kb * 128 + h * 64 + lane;
-    }
-    f32x4 wr[P][U][2], xa[P][U][NW], xb[P][U][NW];
-    auto issue = [&](int kb0, f32x4 (&fw)[U][2], f32x4 (&fa)[U][NW], f32x4 (&fb)[U][NW]) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {  // all weight chunks of the step first: they are wanted one step earlier than the pixels
-            const int kb = kb0 + u, kbc = kb < n_kb ? kb : n_kb - 1;  // past the end: the last block again (multiplied by zeros)
-            fw[u][0] = wsrc[0][(size_t)kbc * 128];
-            fw[u][1] = wsrc[1][(size_t)kbc * 128];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int kb = kb0 + u;
-            const int dy = ty * a.dil, dx = tx * a.dil;
-            const bool in_range = kb < n_kb;
-#pragma unroll
-            for (int n = 0; n < NW; ++n) {
-                const int iy = iy0[n] + dy, ix = ix0[n] + dx;
-                const bool ok = in_range && live[n] && ty < a.ksize && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-                const unsigned off = ok ? (unsigned)(((img0[n] + iy * a.W + ix) * a.in_stride + cg * 8) * 4) : 0xfffffff0u;
-                fa[u][n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
-                fb[u][n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? off + 16u : 0xfffffff0u, 0, 0));
-            }
-            cg += 4;
-            while (cg >= a.c8) {
-                cg -= a.c8;
-                if (++tx == a.ksize) {
-                    tx = 0;
-                    ++ty;
-                }
-            }
-        }
-    };
-    auto stage = [&](int buf, const f32x4 (&fw)[U][2]) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            wtile[buf][u][wave * 64 + lane] = fw[u][0];
-            wtile[buf][u][(wave + 4) * 64 + lane] = fw[u][1];
-        }
-    };
-    constexpr int kW = 2 * U, kX = 2 * NW * U;  // memory operations of one step per wave, in issue order: weight chunks, then pixels
-#pragma unroll
-    for (int s = 0; s < P; ++s) issue(s * U, wr[s], xa[s], xb[s]);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((P - 1) * (kW + kX) + kX) : "memory");  // the weight chunks of step 0
-    stage(0, wr[0]);
-    __syncthreads();
-    const int steps = (n_kb + U - 1) / U, rounds = (steps + P - 1) / P;
-    for (int r = 0; r < rounds; ++r) {
-#pragma unroll
-        for (int s = 0; s < P; ++s) {
-            // here: steps i .. i + P - 1 are in flight (i = r P + s); wanted: the pixels of i, the weight chunks of i + 1
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"((P - 2) * (kW + kX) + kX) : "memory");
-            stage((s + 1) & 1, wr[(s + 1) % P]);
-            f16x8 xh[U][NW], xl[U][NW];
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int n = 0; n < NW; ++n) split8(xa[s][u][n], xb[s][u][n], xh[u][n], xl[u][n]);
-            issue((r * P + s + P) * U, wr[s], xa[s], xb[s]);  // (the registers of step i are free: its chunks sit in LDS, its pixels are split)
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int m = 0; m < MW; ++m) {
-                    const f32x4 wh = wtile[s & 1][u][(m * 2) * 64 + lane], wl = wtile[s & 1][u][(m * 2 + 1) * 64 + lane];
-#pragma unroll
-                    for (int n = 0; n < NW; ++n) acc[m][n] = mfma3(wh, wl, xh[u][n], xl[u][n], acc[m][n]);
-                }
-            __syncthreads();  // step i + 1's chunks are visible; nobody reads slot i & 1 any more
-        }
-    }
-    if (pt0 * 16 >= n_pix) return;
-    seg_epilogue<MW, NW>(a, acc, ct0, pt0, n_pix, col, kg, rvs, bvs);
-}
-
 // GEMM-shaped form for layers with enough pixels to tile both ways (round 5: the frames of several scenes / a look-ahead
 // chunk as one [B, H, W, C] pass, the 60x80 decoder layers): block = WM x WN waves (WN = 4 / WM), wave = MT channel tiles x
 // NT pixel tiles (accumulators MT x NT x 4 registers), block tile 16 WM MT channels x 16 WN NT pixels.  BOTH operands go
@@ -706,7 +567,6 @@ __global__ __launch_bounds__(256, 2) void segconv_gemm_kernel(const SegGroupArgs
     const int H = a.H, W = a.W, HoWo = a.Ho * a.Wo, Wo = a.Wo, c8 = a.c8, ksize = a.ksize, dil = a.dil, in_stride = a.in_stride;
     const int n_pix = a.B * HoWo, n_kb = a.n_kb, n_ct = a.n_ct;
     const int col = lane & 15, kg = lane >> 4;
-    constexpr int abl = OJF_GEMM_ABL;  // build-time ablation (tools/r5_run24.sh, r5_run36.sh): 1 no MFMA, 2 no LDS operand reads, 4 no global loads, 8 no staging, 16 no barrier, 32 weight walk rotated per pixel block, 64 taps inner, 128 no fp16 split of the pixel operands
 
     // producer side: this wave's PT pixel tiles (tiles wave * PT .. of the block) and CW weight chunks
     int iy0[PT], ix0[PT], img0[PT];
@@ -752,8 +612,6 @@ __global__ __launch_bounds__(256, 2) void segconv_gemm_kernel(const SegGroupArgs
     f32x4 wr[P][CW], xa[P][PT], xb[P][PT];  // P K blocks in flight per wave
     auto issue = [&](int kb, f32x4 (&fw)[CW], f32x4 (&fa)[PT], f32x4 (&fb)[PT]) {
         int kbc = kb < n_kb ? kb : n_kb - 1;  // past the end: the last block again (multiplied by zeros)
-        if (abl & 32) kbc = (kbc + bx * 5) % n_kb;  // (timing only, wrong sums) every pixel block of a channel block on another weight line at any time
-        if (abl & 4) return;
 #pragma unroll
         for (int r = 0; r < CW; ++r)
             if (!kShortW || wave * CW + r < 2 * MB) fw[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, woff[r], kbc * 2048, 0));
@@ -767,10 +625,7 @@ __global__ __launch_bounds__(256, 2) void segconv_gemm_kernel(const SegGroupArgs
                 fa[n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
                 fb[n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? off + 16u : 0xfffffff0u, 0, 0));
             }
-            if (abl & 64) {  // (timing only, wrong sums) taps inner, channel groups outer: a K block's pixel lines are the previous block's, shifted
-                if (++tap_s == ksize * ksize) { tap_s = 0; ++cgb_s; }
-                tap_offsets(tap_s);
-            } else if (++cgb_s == n_cgb) {  // (uniform) next tap; past the last one every tile is out of range: zeros
+            if (++cgb_s == n_cgb) {  // (uniform) next tap; past the last one every tile is out of range: zeros
                 cgb_s = 0;
                 tap_offsets(++tap_s);
             }
@@ -796,15 +651,7 @@ __global__ __launch_bounds__(256, 2) void segconv_gemm_kernel(const SegGroupArgs
             }
         }
     };
-    f32x4 sink{0.f, 0.f, 0.f, 0.f};
     auto stage = [&](int st, const f32x4 (&fw)[CW], const f32x4 (&fa)[PT], const f32x4 (&fb)[PT]) {
-        if (abl & 8) {  // (the loads stay alive: their sum goes into an accumulator)
-#pragma unroll
-            for (int r = 0; r < CW; ++r) sink += fw[r];
-#pragma unroll
-            for (int n = 0; n < PT; ++n) sink += fa[n] + fb[n];
-            return;
-        }
 #pragma unroll
         for (int r = 0; r < CW; ++r) {
             const int c = wave * CW + r;
@@ -813,11 +660,6 @@ __global__ __launch_bounds__(256, 2) void segconv_gemm_kernel(const SegGroupArgs
 #pragma unroll
         for (int n = 0; n < PT; ++n) {
             if (kShortPix && wave * PT + n >= NB) continue;
-            if (abl & 128) {  // (timing only, wrong sums) as if the producer had stored the activations as fp16 halves: no split
-                Bs[st][wave * PT + n][0][lane] = fa[n];
-                Bs[st][wave * PT + n][1][lane] = fb[n];
-                continue;
-            }
             f16x8 xh, xl;
             split8(fa[n], fb[n], xh, xl);
             Bs[st][wave * PT + n][0][lane] = __builtin_bit_cast(f32x4, xh);
@@ -882,11 +724,11 @@ __global__ __launch_bounds__(256, 2) void segconv_gemm_kernel(const SegGroupArgs
             f32x4 bh[NT], bl[NT], ah[2], al[2];
 #pragma unroll
             for (int n = 0; n < NT; ++n) {
-                bh[n] = (abl & 2) ? xa[0][0] : Bs[u & 1][wn * NT + n][0][lane];
-                bl[n] = (abl & 2) ? xb[0][0] : Bs[u & 1][wn * NT + n][1][lane];
+                bh[n] = Bs[u & 1][wn * NT + n][0][lane];
+                bl[n] = Bs[u & 1][wn * NT + n][1][lane];
             }
-            ah[0] = (abl & 2) ? wr[0][0] : As[u & 1][wm * MT][0][lane];
-            al[0] = (abl & 2) ? wr[1 % P][0] : As[u & 1][wm * MT][1][lane];
+            ah[0] = As[u & 1][wm * MT][0][lane];
+            al[0] = As[u & 1][wm * MT][1][lane];
             __builtin_amdgcn_sched_barrier(0);
             wait_landed();  // block i + 1 has landed
             stage((u + 1) & 1, wr[(u + 1) % P], xa[(u + 1) % P], xb[(u + 1) % P]);
@@ -895,358 +737,8 @@ __global__ __launch_bounds__(256, 2) void segconv_gemm_kernel(const SegGroupArgs
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
                 if (m + 1 < MT) {  // the next channel tile's weight fragments while this one's MFMAs run
-                    ah[(m + 1) & 1] = (abl & 2) ? wr[0][0] : As[u & 1][wm * MT + m + 1][0][lane];
-                    al[(m + 1) & 1] = (abl & 2) ? wr[1 % P][0] : As[u & 1][wm * MT + m + 1][1][lane];
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if (!(abl & 1)) {
-#pragma unroll
-                    for (int n = 0; n < NT; ++n)
-                        acc[m][n] = mfma3(ah[m & 1], al[m & 1], __builtin_bit_cast(f16x8, bh[n]), __builtin_bit_cast(f16x8, bl[n]), acc[m][n]);
-                } else {
-#pragma unroll
-                    for (int n = 0; n < NT; ++n) acc[m][n][0] += ah[m & 1][0] * bh[n][0] + al[m & 1][1] * bl[n][1];  // (keeps the operands alive)
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (!(abl & 16)) __syncthreads();  // the other stage is complete for the next K block; nobody reads this one any more
-        }
-    }
-    if (abl & 8) acc[0][0] += sink;
-    if (ctw >= n_ct || ptw * 16 >= n_pix) return;
-    f32x4 rvs[MT], bvs[MT];
-    seg_vectors<MT>(a, ctw, kg, rvs, bvs);
-    seg_epilogue<MT, NT, DROP>(a, acc, ctw, ptw, n_pix, col, kg, rvs, bvs);
-}
-
-// Producer / consumer form of the GEMM-shaped kernel (round 6).  What round 5's ablations said about segconv_gemm_kernel: with
-// the SAME four waves fetching, splitting, staging and multiplying, the pieces of a K block ADD - loads + split + ds_write + barrier
-// cost 42 us on top of the 60 us of LDS reads + MFMAs of the 60x80 256 -> 256 layer - because a wave is in one phase at a time and a
-// SIMD holds one such wave.  Here the phases belong to DIFFERENT waves of one block: waves 0 .. 3 (one per SIMD, 2 x 2 over the block
-// tile) only read operands from LDS and issue MFMAs; waves 4 .. 7 (one per SIMD, beside a consumer) only move data - plain 16-byte
-// loads of the packed weight chunks and of the fp32 pixel rows, P K blocks in flight in registers, the fp16 split of the pixel
-// operands, ds_write_b128 into the other LDS stage.  A SIMD's MFMA pipe runs the consumer's 16-cycle instructions while its VALU /
-// memory ports take the producer's; one block-wide barrier per K block hands a finished stage over.  Same K order and the same
-// arithmetic as segconv_gemm_kernel (one accumulator walks the K blocks in order): the same bits.
-template <int MT, int NT, bool DROP, bool ALIGNED, int P = 3>
-__global__ __launch_bounds__(512) void segconv_ws_kernel(const SegGroupArgs grp)
-{
-    int bx, by, bz;
-    if (!seg_block(grp, bx, by, bz)) return;  // block-uniform
-    const SegArgs &a = grp.a[bz];
-    constexpr int WM = 2, WN = 2;
-    constexpr int MB = WM * MT, NB = WN * NT;  // channel / pixel tiles of the block
-    static_assert(NB % 4 == 0 && (2 * MB) % 4 == 0, "every producer wave moves the same share");
-    constexpr int PT = NB / 4;                 // pixel tiles a producer wave fetches and splits per K block
-    constexpr int CW = 2 * MB / 4;             // one-KB weight chunks (channel tile, half) a producer wave fetches per K block
-    __shared__ f32x4 As[2][MB][2][64];
-    __shared__ f32x4 Bs[2][NB][2][64];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int ct0 = by * MB, pt0 = bx * NB;
-    const int n_kb = a.n_kb, n_ct = a.n_ct;
-    const int col = lane & 15, kg = lane >> 4;
-
-    if (wave >= 4) {
-        // ---------------- producer ----------------
-        const int pw = wave - 4;
-        const int H = a.H, W = a.W, HoWo = a.Ho * a.Wo, Wo = a.Wo, c8 = a.c8, ksize = a.ksize, dil = a.dil, in_stride = a.in_stride;
-        const int n_pix = a.B * HoWo;
-        int iy0[PT], ix0[PT], img0[PT];
-        bool live[PT];
-#pragma unroll
-        for (int n = 0; n < PT; ++n) {
-            const int p = (pt0 + pw * PT + n) * 16 + col;
-            live[n] = p < n_pix;
-            const int b = p / HoWo, q = p - b * HoWo;
-            const int oy = q / Wo, ox = q - oy * Wo;
-            iy0[n] = oy * a.stride - a.pad;
-            ix0[n] = ox * a.stride - a.pad;
-            img0[n] = b * H * W;
-        }
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.in), 0, a.in_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rw =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<f32x4 *>(a.wp), 0, (unsigned)((size_t)n_ct * n_kb * 2048), 0x00020000);
-        unsigned woff[CW];
-#pragma unroll
-        for (int r = 0; r < CW; ++r) {
-            const int c = pw * CW + r, m = c >> 1, h = c & 1;
-            int ct = ct0 + m;
-            ct = ct < n_ct ? ct : n_ct - 1;  // (a block past the layer's last channel tile: any valid tile, results unused)
-            woff[r] = (unsigned)(((ct * n_kb) * 128 + h * 64 + lane) * 16);
-        }
-        const int n_cgb = c8 >> 2;
-        int tap_s = 0, cgb_s = 0;
-        unsigned toff[PT];
-        int tap = kg / c8, cg = kg - tap * c8;
-        int ty = tap / ksize, tx = tap - ty * ksize;
-        auto tap_offsets = [&](int t) {
-            const int y = t / ksize, x = t - y * ksize;
-#pragma unroll
-            for (int n = 0; n < PT; ++n) {
-                const int iy = iy0[n] + y * dil, ix = ix0[n] + x * dil;
-                const bool ok = live[n] && y < ksize && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
-                toff[n] = ok ? (unsigned)(((img0[n] + iy * W + ix) * in_stride + kg * 8) * 4) : 0xfffffff0u;
-            }
-        };
-        if constexpr (ALIGNED) tap_offsets(0);
-        f32x4 wr[P][CW], xa[P][PT], xb[P][PT];
-        auto issue = [&](int kb, f32x4 (&fw)[CW], f32x4 (&fa)[PT], f32x4 (&fb)[PT]) {
-            const int kbc = kb < n_kb ? kb : n_kb - 1;  // past the end: the last block again (never staged)
-#pragma unroll
-            for (int r = 0; r < CW; ++r) fw[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, woff[r], kbc * 2048, 0));
-            if constexpr (ALIGNED) {
-                const unsigned step = (unsigned)cgb_s * 128u;
-#pragma unroll
-                for (int n = 0; n < PT; ++n) {
-                    const bool ok = toff[n] != 0xfffffff0u;
-                    const unsigned off = ok ? toff[n] + step : 0xfffffff0u;
-                    fa[n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
-                    fb[n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? off + 16u : 0xfffffff0u, 0, 0));
-                }
-                if (++cgb_s == n_cgb) {
-                    cgb_s = 0;
-                    tap_offsets(++tap_s);
-                }
-            } else {
-                const int dy = ty * dil, dx = tx * dil;
-                const bool in_range = kb < n_kb;
-#pragma unroll
-                for (int n = 0; n < PT; ++n) {
-                    const int iy = iy0[n] + dy, ix = ix0[n] + dx;
-                    const bool ok = in_range && live[n] && ty < ksize && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
-                    const unsigned off = ok ? (unsigned)(((img0[n] + iy * W + ix) * in_stride + cg * 8) * 4) : 0xfffffff0u;
-                    fa[n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
-                    fb[n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? off + 16u : 0xfffffff0u, 0, 0));
-                }
-                cg += 4;
-                while (cg >= c8) {
-                    cg -= c8;
-                    if (++tx == ksize) {
-                        tx = 0;
-                        ++ty;
-                    }
-                }
-            }
-        };
-        auto stage = [&](int st, const f32x4 (&fw)[CW], const f32x4 (&fa)[PT], const f32x4 (&fb)[PT]) {
-#pragma unroll
-            for (int r = 0; r < CW; ++r) {
-                const int c = pw * CW + r;
-                As[st][c >> 1][c & 1][lane] = fw[r];
-            }
-#pragma unroll
-            for (int n = 0; n < PT; ++n) {
-                f16x8 xh, xl;
-                split8(fa[n], fb[n], xh, xl);
-                Bs[st][pw * PT + n][0][lane] = __builtin_bit_cast(f32x4, xh);
-                Bs[st][pw * PT + n][1][lane] = __builtin_bit_cast(f32x4, xl);
-            }
-        };
-        constexpr int kOps = CW + 2 * PT;  // memory operations of one K block of a producer wave
-#pragma unroll
-        for (int q = 0; q < P; ++q) issue(q, wr[q], xa[q], xb[q]);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((P - 1) * kOps) : "memory");
-        stage(0, wr[0], xa[0], xb[0]);
-        issue(P, wr[0], xa[0], xb[0]);
-        __syncthreads();  // stage 0 is complete
-        // at iteration i: K blocks i + 1 .. i + P are in flight, block j in register slot j % P; block i + 1 goes into stage (i + 1) & 1
-        const int rounds = (n_kb + 2 * P - 1) / (2 * P);
-        for (int r = 0; r < rounds; ++r) {
-#pragma unroll
-            for (int u = 0; u < 2 * P; ++u) {  // (2 P: a common period of the LDS stage and the register slot)
-                const int i = r * 2 * P + u;
-                if (i >= n_kb) break;  // (uniform; only in the last round)
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"((P - 1) * kOps) : "memory");  // block i + 1 has landed
-                if (i + 1 < n_kb) stage((u + 1) & 1, wr[(u + 1) % P], xa[(u + 1) % P], xb[(u + 1) % P]);
-                issue(i + 1 + P, wr[(u + 1) % P], xa[(u + 1) % P], xb[(u + 1) % P]);
-                __syncthreads();  // stage (i + 1) & 1 is complete; the consumers are done with stage i & 1
-            }
-        }
-        return;
-    }
-
-    // ---------------- consumer ----------------
-    const int wm = wave % WM, wn = wave / WM;
-    f32x4 acc[MT][NT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int n = 0; n < NT; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int ctw = ct0 + wm * MT, ptw = pt0 + wn * NT;  // this wave's accumulator tiles
-    __syncthreads();  // stage 0 is complete
-    for (int i = 0; i < n_kb; ++i) {
-        const int st = i & 1;
-        f32x4 bh[NT], bl[NT], ah[2], al[2];
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-            bh[n] = Bs[st][wn * NT + n][0][lane];
-            bl[n] = Bs[st][wn * NT + n][1][lane];
-        }
-        ah[0] = As[st][wm * MT][0][lane];
-        al[0] = As[st][wm * MT][1][lane];
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            if (m + 1 < MT) {  // the next channel tile's weight fragments while this one's MFMAs run
-                ah[(m + 1) & 1] = As[st][wm * MT + m + 1][0][lane];
-                al[(m + 1) & 1] = As[st][wm * MT + m + 1][1][lane];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int n = 0; n < NT; ++n)
-                acc[m][n] = mfma3(ah[m & 1], al[m & 1], __builtin_bit_cast(f16x8, bh[n]), __builtin_bit_cast(f16x8, bl[n]), acc[m][n]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        __syncthreads();  // the other stage is complete for the next K block; nobody reads this one any more
-    }
-    const int n_pix = a.B * a.Ho * a.Wo;
-    if (ctw >= n_ct || ptw * 16 >= n_pix) return;
-    f32x4 rvs[MT], bvs[MT];
-    seg_vectors<MT>(a, ctw, kg, rvs, bvs);
-    seg_epilogue<MT, NT, DROP>(a, acc, ctw, ptw, n_pix, col, kg, rvs, bvs);
-}
-
-// WINDOW form (round 6) for 3x3 / stride 1 / dilation 1 / padding 1 layers whose channel groups come in fours (c_in % 32 == 0).  What
-// this round's gate measured (profiles/r06_seg_ws_gate.txt): the GEMM-shaped launches sit on an L2 -> CU plateau of ~8 TB/s because every
-// (tap, channel block) of a K walk re-fetches its pixel rows - nine times per 3x3 layer - and every pixel block re-fetches the weights.
-// Here the K walk is (32-channel chunk) outer, (tap) inner: the chunk's pixels of the block's TH x 16 output tile PLUS its one-pixel halo
-// are fetched ONCE, split into fp16 halves once, and stay in LDS for all nine taps, which read them at shifted positions (pixel pitch 144
-// bytes: the 16 lanes of an operand read hit 16 different 16-byte bank groups).  The weights of a (tap, chunk) K block stream through a
-// two-stage LDS buffer, two K blocks in flight in registers, one barrier per K block, the next chunk's window loads ride along (issued at
-// tap 0, written at tap 3).  Block = 2 x 2 waves over (2 MT channel tiles) x (TH rows of 16 pixels).  K blocks are added chunk-major
-// instead of tap-major: the same products, another rounding order than the other forms (like every change of form: include/ojf.h).
-template <int MT, int TH, bool DROP = false>
-__global__ __launch_bounds__(256) void segconv_win_kernel(const SegGroupArgs grp)
-{
-    int bx, by, bz;
-    if (!seg_block(grp, bx, by, bz)) return;  // block-uniform
-    const SegArgs &a = grp.a[bz];
-    constexpr int MB = 2 * MT, NT = TH / 2, WW = 18, WH = TH + 2, WPIX = WW * WH, PIXB = 144;
-    constexpr int WI = (WPIX * 4 + 255) / 256;  // window items (pixel, 8-channel group) per thread
-    constexpr int CW = 2 * MB / 4;              // one-KB weight chunks per wave and K block
-    static_assert(TH % 2 == 0 && (2 * MB) % 4 == 0, "tile");
-    extern __shared__ __attribute__((aligned(16))) unsigned char win_lds[];
-    unsigned char *Ws = win_lds;                                             // [2][WPIX * PIXB]
-    f32x4 *As = reinterpret_cast<f32x4 *>(win_lds + 2 * WPIX * PIXB);        // [2][MB][2][64]
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm = wave & 1, wn = wave >> 1;
-    const int col = lane & 15, kg = lane >> 4;
-    const int H = a.H, W = a.W, in_stride = a.in_stride, n_kb = a.n_kb, n_ct = a.n_ct;
-    const int n_chunks = a.c8 >> 2, total = 9 * n_chunks;
-    const int tiles_x = (W + 15) >> 4, tiles_y = (H + TH - 1) / TH;
-    const int img = bx / (tiles_x * tiles_y), rb = bx - img * (tiles_x * tiles_y);
-    const int tyb = rb / tiles_x, txb = rb - tyb * tiles_x;
-    const int y0 = tyb * TH, x0 = txb * 16;
-    const int ct0 = by * MB;
-
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.in), 0, a.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<f32x4 *>(a.wp), 0, (unsigned)((size_t)n_ct * n_kb * 2048), 0x00020000);
-    unsigned woff[CW];
-#pragma unroll
-    for (int r = 0; r < CW; ++r) {
-        const int c = wave * CW + r, m = c >> 1, h = c & 1;
-        int ct = ct0 + m;
-        ct = ct < n_ct ? ct : n_ct - 1;  // (a block past the layer's last channel tile: any valid tile, results unused)
-        woff[r] = (unsigned)(((ct * n_kb) * 128 + h * 64 + lane) * 16);
-    }
-    // this thread's window items: global byte offset of channel group 0 of its pixel (or the out-of-range sentinel), LDS byte offset
-    unsigned goff[WI], loff[WI];
-#pragma unroll
-    for (int j = 0; j < WI; ++j) {
-        const int item = (int)threadIdx.x + 256 * j;
-        const int wp = item >> 2, q = item & 3;
-        const int wy = wp / WW, wx = wp - wy * WW;
-        const int iy = y0 - 1 + wy, ix = x0 - 1 + wx;
-        const bool ok = item < WPIX * 4 && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
-        goff[j] = ok ? (unsigned)((((img * H + iy) * W + ix) * in_stride + q * 8) * 4) : 0xfffffff0u;
-        loff[j] = item < WPIX * 4 ? (unsigned)(wp * PIXB + q * 32) : 0xffffffffu;
-    }
-    f32x4 wa[WI], wb[WI];
-    auto issue_window = [&](int chunk) {  // (a chunk past the last one: zeros, no traffic)
-        const unsigned step = (unsigned)chunk * 128u;
-#pragma unroll
-        for (int j = 0; j < WI; ++j) {
-            const bool ok = goff[j] != 0xfffffff0u && chunk < n_chunks;
-            const unsigned off = ok ? goff[j] + step : 0xfffffff0u;
-            wa[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
-            wb[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? off + 16u : 0xfffffff0u, 0, 0));
-        }
-    };
-    auto stage_window = [&](int st) {
-#pragma unroll
-        for (int j = 0; j < WI; ++j) {
-            if (loff[j] == 0xffffffffu) continue;
-            f16x8 xh, xl;
-            split8(wa[j], wb[j], xh, xl);
-            unsigned char *dst = Ws + st * (WPIX * PIXB) + loff[j];
-            *reinterpret_cast<f32x4 *>(dst) = __builtin_bit_cast(f32x4, xh);
-            *reinterpret_cast<f32x4 *>(dst + 16) = __builtin_bit_cast(f32x4, xl);
-        }
-    };
-    // the K block of step s = (chunk c, tap t) sits at index t * n_chunks + c of the layer's packed K blocks
-    f32x4 wr[2][CW];
-    int it = 0, ic = 0;  // (tap, chunk) of the next weight K block to request
-    auto issue_weights = [&](f32x4 (&fw)[CW]) {
-        const int kb = ic < n_chunks ? it * n_chunks + ic : n_kb - 1;  // past the end: the last block again (never used)
-#pragma unroll
-        for (int r = 0; r < CW; ++r) fw[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, woff[r], kb * 2048, 0));
-        if (++it == 9) { it = 0; ++ic; }
-    };
-    auto stage_weights = [&](int st, const f32x4 (&fw)[CW]) {
-#pragma unroll
-        for (int r = 0; r < CW; ++r) {
-            const int c = wave * CW + r;
-            As[((st * MB + (c >> 1)) * 2 + (c & 1)) * 64 + lane] = fw[r];
-        }
-    };
-
-    f32x4 acc[MT][NT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int n = 0; n < NT; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // prologue: window of chunk 0, weights of steps 0 (staged), 1 and 2 (in flight)
-    issue_window(0);
-    issue_weights(wr[0]);
-    issue_weights(wr[1]);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CW) : "memory");
-    stage_window(0);
-    stage_weights(0, wr[0]);
-    issue_weights(wr[0]);
-    __syncthreads();
-    // this lane's operand position in the window: output pixel (row wn * NT + n, column col) reads window pixel (row + ky, col + kx)
-    const unsigned bbase = (unsigned)(((wn * NT) * WW + col) * PIXB + kg * 32);
-    int t = 0, c = 0;
-    for (int s2 = 0; s2 < total; s2 += 2) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int s = s2 + u;
-            if (s >= total) break;  // (uniform; only in the last round)
-            // weights of step s sit in As stage u (= s & 1: s2 is even), of step s + 1 in register slot (u + 1) & 1
-            const unsigned char *wsrc = Ws + (c & 1) * (WPIX * PIXB) + bbase + (unsigned)(((t / 3) * WW + (t % 3)) * PIXB);
-            f32x4 bh[NT], bl[NT], ah[2], al[2];
-#pragma unroll
-            for (int n = 0; n < NT; ++n) {
-                bh[n] = *reinterpret_cast<const f32x4 *>(wsrc + n * (WW * PIXB));
-                bl[n] = *reinterpret_cast<const f32x4 *>(wsrc + n * (WW * PIXB) + 16);
-            }
-            ah[0] = As[((u * MB + wm * MT) * 2 + 0) * 64 + lane];
-            al[0] = As[((u * MB + wm * MT) * 2 + 1) * 64 + lane];
-            __builtin_amdgcn_sched_barrier(0);
-            // landed: the weights of step s + 1 (and, at tap 3, the next chunk's window, requested at tap 0 behind tap 0's weights)
-            if (t == 1 || t == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CW + 2 * WI) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CW) : "memory");
-            stage_weights((u + 1) & 1, wr[(u + 1) & 1]);
-            if (t == 3) stage_window((c + 1) & 1);
-            issue_weights(wr[(u + 1) & 1]);
-            if (t == 0) issue_window(c + 1);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int m = 0; m < MT; ++m) {
-                if (m + 1 < MT) {
-                    ah[(m + 1) & 1] = As[((u * MB + wm * MT + m + 1) * 2 + 0) * 64 + lane];
-                    al[(m + 1) & 1] = As[((u * MB + wm * MT + m + 1) * 2 + 1) * 64 + lane];
+                    ah[(m + 1) & 1] = As[u & 1][wm * MT + m + 1][0][lane];
+                    al[(m + 1) & 1] = As[u & 1][wm * MT + m + 1][1][lane];
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -1254,21 +746,13 @@ __global__ __launch_bounds__(256) void segconv_win_kernel(const SegGroupArgs grp
                     acc[m][n] = mfma3(ah[m & 1], al[m & 1], __builtin_bit_cast(f16x8, bh[n]), __builtin_bit_cast(f16x8, bl[n]), acc[m][n]);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            __syncthreads();
-            if (++t == 9) { t = 0; ++c; }
+            __syncthreads();  // the other stage is complete for the next K block; nobody reads this one any more
         }
     }
-    const int ctw = ct0 + wm * MT;
-    if (ctw >= n_ct) return;
-    int pidx[NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n) {
-        const int y = y0 + wn * NT + n, x = x0 + col;
-        pidx[n] = (y < H && x < W) ? (img * H + y) * W + x : -1;
-    }
+    if (ctw >= n_ct || ptw * 16 >= n_pix) return;
     f32x4 rvs[MT], bvs[MT];
     seg_vectors<MT>(a, ctw, kg, rvs, bvs);
-    seg_epilogue_px<MT, NT, DROP>(a, acc, ctw, pidx, kg, rvs, bvs);
+    seg_epilogue<MT, NT, DROP>(a, acc, ctw, ptw, n_pix, col, kg, rvs, bvs);
 }
 
 inline float pow2_row_scale(float row_max)
@@ -1443,17 +927,41 @@ int seg_fill(const ojf_segconv *c, int batch, const float *in, int in_stride, fl
 // 1-D launch geometry of the logical grid X x Y x Z (see SegMap)
 unsigned seg_map(SegMap &m, int X, int Y, int Z)
 {
-    static const int xcd = getenv("OJF_SEG_XCD") ? atoi(getenv("OJF_SEG_XCD")) : 1;  // A/B switch (0: plain numbering)
     m.X = X; m.Y = Y; m.Z = Z;
-    if (!xcd) {
-        m.S = 0; m.chunk = X; m.V = Y * Z;
-        return (unsigned)(X * Y * Z);
-    }
     const int Q = Y * Z;
     int S = 1;
     while (S < 8 && (Q * S) % 8 != 0 && (X + 2 * S - 1) / (2 * S) >= 2) S *= 2;  // chunks of >= 2 pixel blocks
     m.S = S; m.chunk = (X + S - 1) / S; m.V = Q * S;
     return (unsigned)((m.V + 7) / 8 * 8 * m.chunk);
+}
+
+// Thresholds of the form choice, shared by seg_launch and seg_launch_multi (each is the measured default of its round's A/B runs:
+// profiles/r05_seg_experiments.txt)
+constexpr int kWideMinKb = 6;         // the wide form's three-stage weight ring wants at least this many K blocks ...
+constexpr int kWideMinBlocks = 256;   // ... and 64 channels x 128 pixels must give this many blocks
+constexpr int kPlainMinWaves = 1024;  // waves of (64 channels, 2 pixel tiles) from which every wave owns its pair: >= 4 per CU hide the operand latency
+constexpr int kSplitKMinKb = 8;       // below this many K blocks the in-block K split is not worth its LDS reduction
+constexpr int kSplitKMinBlocks = 150; // split-K launches take as many channel tiles per block as leave this many blocks
+constexpr int kNw2MinKb = 32;         // two pixel tiles per split-K wave from this many K blocks on ...
+constexpr int kNw2MaxBlocks = 400;    // ... where that still leaves kSplitKMinBlocks .. this many blocks
+constexpr int kPlainNw1Min = 50;      // one pixel tile per wave in the plain form from 50 pixel tiles on (twice the waves in flight for layers that are all latency: -1.4 % of the frame)
+constexpr int kGemmMin = 256;         // 128 x 128 tile alone gives this many blocks
+constexpr int kGemm22Min = 128;       // ... or the 64 x 64 tile this many
+constexpr int kGemmMinKb = 4;
+
+bool seg_trace_on()
+{
+    static const bool on = getenv("OJF_SEG_TRACE") ? atoi(getenv("OJF_SEG_TRACE")) != 0 : false;  // one line per launch (tools/, tests/test_segconv_dropout_gpu.py)
+    return on;
+}
+
+// the trace line of a launch of seg_launch; `width` pads the form name (12 for the GEMM-shaped forms, 10 for the others)
+void seg_trace(const char *variant, int width, int n, const SegArgs &a, const SegMap &m)
+{
+    if (!seg_trace_on()) return;
+    fprintf(stderr, "segconv %-*s n %d  c_in %4d c_out %4d k %d s %d d %2d  in %3dx%3d out %3dx%3d  n_kb %4d  grid %dx%dx%d S %d%s%s%s\n", width, variant, n,
+            a.c8 * 8, a.c_out, a.ksize, a.stride, a.dil, a.H, a.W, a.Ho, a.Wo, a.n_kb, m.X, m.Y, m.Z, m.S,
+            a.res ? " +res" : "", a.mul ? " *mul" : "", a.up > 1 ? " deconv" : "");
 }
 
 // n members of one shape (the first one's n_kb / n_ct / output size decide the launch)
@@ -1463,54 +971,26 @@ int seg_launch(SegGroupArgs &g, int n, hipStream_t st)
     for (int i = 1; i < n; ++i)
         if (g.a[i].rng_bump) return fail("ojf_segconv launch: only member 0 of a grouped launch may advance the frame counter");
     g.het.n = 0;
-    static const int abl = getenv("OJF_SEG_ABL") ? atoi(getenv("OJF_SEG_ABL")) : 0;  // tuning only
-    g.abl = abl;
     const SegArgs &a = g.a[0];
     const int n_pt = (a.B * a.Ho * a.Wo + 15) / 16, groups = a.n_ct / kMW;  // pixel tiles, 64-channel groups
     // Enough independent waves (>= 4 per CU) to hide the operand latency: waves own their (channels, pixels) pair.
     // Otherwise the four waves of a block split K (when K is long enough to be worth the LDS reduction).
     const long waves2 = (long)groups * ((n_pt + 1) / 2) * n;
-    static const int force_mw = getenv("OJF_SEG_MW") ? atoi(getenv("OJF_SEG_MW")) : 0;  // tuning only
-    static const int no_wide = getenv("OJF_SEG_NO_WIDE") ? atoi(getenv("OJF_SEG_NO_WIDE")) : 0;  // tuning only
-    static const int wide_min = getenv("OJF_SEG_WIDE_MIN") ? atoi(getenv("OJF_SEG_WIDE_MIN")) : 256;  // tuning only
-    static const int trace = getenv("OJF_SEG_TRACE") ? atoi(getenv("OJF_SEG_TRACE")) : 0;  // tuning only: one line per launch
-    static const int wide1_min = getenv("OJF_SEG_WIDE1_MIN") ? atoi(getenv("OJF_SEG_WIDE1_MIN")) : (1 << 30);  // tuning only
-    static const int splitk_nw2_min = getenv("OJF_SEG_SPLITK_NW2_MIN") ? atoi(getenv("OJF_SEG_SPLITK_NW2_MIN")) : (1 << 30);  // tuning only
-    static const int nw2_min_kb = getenv("OJF_SEG_NW2_MIN_KB") ? atoi(getenv("OJF_SEG_NW2_MIN_KB")) : 32;  // tuning only
-    static const int nw2_max_blocks = getenv("OJF_SEG_NW2_MAX_BLOCKS") ? atoi(getenv("OJF_SEG_NW2_MAX_BLOCKS")) : 400;  // tuning only (0: never)
-    static const int plain_nw1_min = getenv("OJF_SEG_PLAIN_NW1_MIN") ? atoi(getenv("OJF_SEG_PLAIN_NW1_MIN")) : 50;  // one pixel tile per wave in the plain form from 50 pixel tiles on (twice the waves in flight for layers that are all latency: -1.4 % of the frame)
-    static const int splitk_min_kb = getenv("OJF_SEG_SPLITK_MIN_KB") ? atoi(getenv("OJF_SEG_SPLITK_MIN_KB")) : 8;  // tuning only
-    static const int tile_u = getenv("OJF_SEG_TILE_U") ? atoi(getenv("OJF_SEG_TILE_U")) : 1;  // tuning only: K blocks per barrier of the tile kernel
-    static const int use_tile = getenv("OJF_SEG_TILE") ? atoi(getenv("OJF_SEG_TILE")) : 0;  // tuning only: register-staged tile kernel
-    static const int wide_depth = getenv("OJF_SEG_WIDE_DEPTH") ? atoi(getenv("OJF_SEG_WIDE_DEPTH")) : 3;  // tuning only: 3 | 6 | 8
     const char *variant;
     // GEMM-shaped form (segconv_gemm_kernel) where both the channels and the pixels tile: the 128 x 128 tile when that alone
-    // gives gemm_min blocks (measured 118 vs 176 us at 300 blocks, but 68 vs 51 at 75), else the 64 x 64 tile from gemm22_min
+    // gives kGemmMin blocks (measured 118 vs 176 us at 300 blocks, but 68 vs 51 at 75), else the 64 x 64 tile from kGemm22Min
     // blocks on (30 vs 38 us at 152 blocks, 23 vs 28 at 640; 53 vs 33 at 76).  A launch's time is a step function of its
     // block count (120 .. 256 blocks of one layer 29 .. 31 us, 260 .. 512 blocks 43 .. 54 us, 520 blocks 69 us), so the
     // 128 x 160 tile takes over where it saves a round of 256 blocks (four frames of a 60x80 map: 240 blocks for 300, 94 vs
     // 103 us).  Measured and not in the menu: 64 x 80 / 64 x 96 / 64 x 160 tiles (44 / 46 / 65 us against 46 for 64 x 64 on the
     // 60x80 256 -> 256 3x3 layer of one frame, although 240 / 200 / 120 blocks instead of 300: a block with more work per K
     // block is slower by more than its share), the 64 x 128 tile (never won a layer).
-    static const int gemm_min = getenv("OJF_SEG_GEMM_MIN") ? atoi(getenv("OJF_SEG_GEMM_MIN")) : 256;  // 128 x 128 tile alone gives this many blocks (1 << 30: off)
-    static const int gemm22_min = getenv("OJF_SEG_GEMM22_MIN") ? atoi(getenv("OJF_SEG_GEMM22_MIN")) : 128;  // ... or the 64 x 64 tile this many
-    static const int gemm_min_kb = getenv("OJF_SEG_GEMM_MIN_KB") ? atoi(getenv("OJF_SEG_GEMM_MIN_KB")) : 4;
-    static const int gemm_shape = getenv("OJF_SEG_GEMM_SHAPE") ? atoi(getenv("OJF_SEG_GEMM_SHAPE")) : -1;  // tuning: force menu entry
-    static const int gemm_menu = getenv("OJF_SEG_GEMM_MENU") ? atoi(getenv("OJF_SEG_GEMM_MENU")) : 0xff;  // tuning: bit 2 = the 128 x 160 tile allowed, bit 3 = the long-K model
     {
         bool drop_all = true, drop_any = false;
         for (int i = 0; i < n; ++i) { drop_any = drop_any || g.a[i].rng; drop_all = drop_all && g.a[i].rng; }
         const long b44 = (long)((a.n_ct + 7) / 8) * ((n_pt + 7) / 8) * n, b22 = (long)((a.n_ct + 3) / 4) * ((n_pt + 3) / 4) * n;
         bool aligned = true;  // every member's channel groups come in fours: the scalar tap walk
         for (int i = 0; i < n; ++i) aligned = aligned && (g.a[i].c8 % 4) == 0;
-#define OJF_WS_LAUNCH(MT_, NT_, GRID_)                                                                                                \
-    do {                                                                                                                             \
-        const dim3 grid__ = GRID_;                                                                                                   \
-        if (drop_any && aligned) hipLaunchKernelGGL((segconv_ws_kernel<MT_, NT_, true, true>), grid__, dim3(512), 0, st, g);          \
-        else if (drop_any) hipLaunchKernelGGL((segconv_ws_kernel<MT_, NT_, true, false>), grid__, dim3(512), 0, st, g);               \
-        else if (aligned) hipLaunchKernelGGL((segconv_ws_kernel<MT_, NT_, false, true>), grid__, dim3(512), 0, st, g);                \
-        else hipLaunchKernelGGL((segconv_ws_kernel<MT_, NT_, false, false>), grid__, dim3(512), 0, st, g);                            \
-    } while (0)
 #define OJF_GEMM_LAUNCH(MT_, NT_, WM_, GRID_)                                                                                         \
     do {                                                                                                                             \
         const dim3 grid__ = GRID_;                                                                                                   \
@@ -1519,42 +999,12 @@ int seg_launch(SegGroupArgs &g, int n, hipStream_t st)
         else if (aligned) hipLaunchKernelGGL((segconv_gemm_kernel<MT_, NT_, false, true, WM_>), grid__, dim3(256), 0, st, g);         \
         else hipLaunchKernelGGL((segconv_gemm_kernel<MT_, NT_, false, false, WM_>), grid__, dim3(256), 0, st, g);                     \
     } while (0)
-        // WINDOW form (segconv_win_kernel): 3x3 / stride 1 / dilation 1 layers with c_in % 32 == 0 and rows of >= 40 pixels (or a multiple of 16)
-        static const int win = getenv("OJF_SEG_WIN") ? atoi(getenv("OJF_SEG_WIN")) : 0;  // 0 off | 1 by block count | 2 force 64 ch x 4 rows | 3 force 128 ch x 8 rows
-        if (win && a.ksize == 3 && a.stride == 1 && a.dil == 1 && a.pad == 1 && aligned && !drop_any && a.c8 >= 8 && (a.W % 16 == 0 || a.W >= 40)) {
-            const int tx = (a.W + 15) / 16;
-            const long blocksB = (long)a.B * ((a.H + 7) / 8) * tx * ((a.n_ct + 7) / 8) * n, blocksA = (long)a.B * ((a.H + 3) / 4) * tx * ((a.n_ct + 3) / 4) * n;
-            const int pick = win == 2 ? 0 : (win == 3 ? 1 : (blocksB >= 192 ? 1 : (blocksA >= 128 ? 0 : -1)));
-            if (pick >= 0) {
-                g.het.n = 0;
-                static bool configured = false;
-                constexpr int ldsA = 2 * (18 * 6) * 144 + 2 * 4 * 2 * 64 * 16, ldsB = 2 * (18 * 10) * 144 + 2 * 8 * 2 * 64 * 16;
-                if (!configured) {
-                    if (int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void *>(&segconv_win_kernel<4, 8, false>),
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize, ldsB), "segconv_win_kernel LDS")) return rc;
-                    if (int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void *>(&segconv_win_kernel<2, 4, false>),
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize, ldsA), "segconv_win_kernel LDS")) return rc;
-                    configured = true;
-                }
-                if (pick) {
-                    variant = "win 128x(8x16)";
-                    hipLaunchKernelGGL((segconv_win_kernel<4, 8, false>), dim3(seg_map(g.map, a.B * ((a.H + 7) / 8) * tx, (a.n_ct + 7) / 8, n)), dim3(256), ldsB, st, g);
-                } else {
-                    variant = "win 64x(4x16)";
-                    hipLaunchKernelGGL((segconv_win_kernel<2, 4, false>), dim3(seg_map(g.map, a.B * ((a.H + 3) / 4) * tx, (a.n_ct + 3) / 4, n)), dim3(256), ldsA, st, g);
-                }
-                if (trace)
-                    fprintf(stderr, "segconv %-14s n %d  c_in %4d c_out %4d k 3  in %3dx%3d B %d  n_kb %4d  grid %dx%dx%d%s\n", variant, n, a.c8 * 8, a.c_out, a.H, a.W, a.B,
-                            a.n_kb, g.map.X, g.map.Y, g.map.Z, a.up > 1 ? " deconv" : "");
-                return check_hip(hipGetLastError(), "segconv_win_kernel launch");
-            }
-        }
         struct Shape { int a, b; const char *name; };  // channel / pixel tiles of the block
         static const Shape menu[] = {{4, 4, "gemm 64x64"}, {8, 8, "gemm 128x128"}, {8, 10, "gemm 128x160"}, {8, 5, "gemm 128x80"}};
-        const bool big = b44 >= gemm_min && a.n_ct >= 8;
-        if (a.n_kb >= gemm_min_kb && (drop_all || !drop_any) && (big || b22 >= gemm22_min)) {
+        const bool big = b44 >= kGemmMin && a.n_ct >= 8;
+        if (a.n_kb >= kGemmMinKb && (drop_all || !drop_any) && (big || b22 >= kGemm22Min)) {
             int best = big ? 1 : 0;
-            if (big && ((gemm_menu >> 2) & 1)) {
+            if (big) {
                 const long b810 = (long)((a.n_ct + 7) / 8) * ((n_pt + 9) / 10) * n;
                 if (b810 >= 200 && (b810 + 255) / 256 < (b44 + 255) / 256) best = 2;
             }
@@ -1563,7 +1013,7 @@ int seg_launch(SegGroupArgs &g, int n, hipStream_t st)
             // in rounds of 256 (two blocks share a CU at 1.65x the time of one: 1, 1.65, 2.65, 3.3, 4.3 ... for 1, 2, 3, 4, 5
             // rounds).  Checked against the layers it re-decides (profiles/r05_seg_experiments.txt): 60x80 256 -> 256 at 2 / 4
             // frames 128x80 (57 against 70 us, 87 against 94), 15x20 512 -> 512 of both encoders at 8 frames 128x80 (108 against 127).
-            if (a.n_kb >= 64 && ((gemm_menu >> 3) & 1)) {
+            if (a.n_kb >= 64) {
                 static const double alone[4] = {28.0, 59.5, 94.5, 51.0};
                 double best_t = 0.0;
                 int pick = -1;
@@ -1577,34 +1027,18 @@ int seg_launch(SegGroupArgs &g, int n, hipStream_t st)
                 }
                 if (pick >= 0) best = pick;
             }
-            if (gemm_shape >= 0) best = gemm_shape > 3 ? 3 : gemm_shape;
-            if (best >= 0) {
-                g.het.n = 0;
-                const Shape &sh = menu[best];
-                variant = sh.name;
-                const dim3 grid(seg_map(g.map, (n_pt + sh.b - 1) / sh.b, (a.n_ct + sh.a - 1) / sh.a, n));
-                static const int ws = getenv("OJF_SEG_WS") ? atoi(getenv("OJF_SEG_WS")) : 0;  // producer / consumer form (round 6)
-                if (ws && best <= 1) {
-                    variant = best ? "ws 128x128" : "ws 64x64";
-                    if (best) OJF_WS_LAUNCH(4, 4, grid); else OJF_WS_LAUNCH(2, 2, grid);
-                    if (trace)
-                        fprintf(stderr, "segconv %-12s n %d  c_in %4d c_out %4d k %d  in %3dx%3d  n_kb %4d  grid %dx%dx%d\n", variant, n, a.c8 * 8, a.c_out, a.ksize,
-                                a.H, a.W, a.n_kb, g.map.X, g.map.Y, g.map.Z);
-                    return check_hip(hipGetLastError(), "segconv_ws_kernel launch");
-                }
-                switch (best) {
-                case 0: OJF_GEMM_LAUNCH(2, 2, 2, grid); break;
-                case 1: OJF_GEMM_LAUNCH(4, 4, 2, grid); break;
-                case 2: OJF_GEMM_LAUNCH(4, 5, 2, grid); break;
-                default: OJF_GEMM_LAUNCH(2, 5, 4, grid); break;
-                }
-                if (trace)
-                    fprintf(stderr, "segconv %-12s n %d  c_in %4d c_out %4d k %d s %d d %2d  in %3dx%3d out %3dx%3d  n_kb %4d  grid %dx%dx%d S %d%s%s%s\n", variant, n,
-                            a.c8 * 8, a.c_out, a.ksize, a.stride, a.dil, a.H, a.W, a.Ho, a.Wo, a.n_kb, g.map.X, g.map.Y, g.map.Z, g.map.S,
-                            a.res ? " +res" : "", a.mul ? " *mul" : "", a.up > 1 ? " deconv" : "");
-                return check_hip(hipGetLastError(), "segconv_gemm_kernel launch");
+            const Shape &sh = menu[best];
+            const dim3 grid(seg_map(g.map, (n_pt + sh.b - 1) / sh.b, (a.n_ct + sh.a - 1) / sh.a, n));
+            switch (best) {
+            case 0: OJF_GEMM_LAUNCH(2, 2, 2, grid); break;
+            case 1: OJF_GEMM_LAUNCH(4, 4, 2, grid); break;
+            case 2: OJF_GEMM_LAUNCH(4, 5, 2, grid); break;
+            default: OJF_GEMM_LAUNCH(2, 5, 4, grid); break;
             }
+            seg_trace(sh.name, 12, n, a, g.map);
+            return check_hip(hipGetLastError(), "segconv_gemm_kernel launch");
         }
+#undef OJF_GEMM_LAUNCH
     }
     // a layer with the always-on dropout in its epilogue (the last convolution of a multi-scale unit): the DROP instantiation of
     // the same kernel - the plain ones do not carry the generator's code (it cost every launch ~0.6 us)
@@ -1614,32 +1048,19 @@ int seg_launch(SegGroupArgs &g, int n, hipStream_t st)
         for (int i = 0; i < n; ++i)
             if (!g.a[i].rng) return fail("ojf_segconv_forward_group: dropout on some members only");
         int mw = 4;
-        while (mw > 1 && (long)n_pt * (a.n_ct / mw) * n < 150) mw /= 2;
+        while (mw > 1 && (long)n_pt * (a.n_ct / mw) * n < kSplitKMinBlocks) mw /= 2;
         if (mw == 1) hipLaunchKernelGGL((segconv_kernel<1, 1, 1, 4, 3, true>), dim3(seg_map(g.map, n_pt, a.n_ct, n)), dim3(256), 0, st, g);
         else if (mw == 2) hipLaunchKernelGGL((segconv_kernel<2, 1, 1, 4, 3, true>), dim3(seg_map(g.map, n_pt, a.n_ct / 2, n)), dim3(256), 0, st, g);
         else hipLaunchKernelGGL((segconv_kernel<4, 1, 1, 4, 3, true>), dim3(seg_map(g.map, n_pt, groups, n)), dim3(256), 0, st, g);
         variant = mw == 1 ? "<1,1,1,4> drop" : (mw == 2 ? "<2,1,1,4> drop" : "<4,1,1,4> drop");
-    } else if (!no_wide && a.n_kb >= 6 && (long)groups * ((n_pt + 7) / 8) * n >= wide_min) {
-        variant = use_tile ? "tile<2>" : "wide<2>";
-        if (use_tile && tile_u == 4) hipLaunchKernelGGL((segconv_tile_kernel<2, 4>), dim3(seg_map(g.map, (n_pt + 7) / 8, groups, n)), dim3(256), 0, st, g);
-        else if (use_tile && tile_u == 2) hipLaunchKernelGGL((segconv_tile_kernel<2, 2>), dim3(seg_map(g.map, (n_pt + 7) / 8, groups, n)), dim3(256), 0, st, g);
-        else if (use_tile) hipLaunchKernelGGL((segconv_tile_kernel<2, 1>), dim3(seg_map(g.map, (n_pt + 7) / 8, groups, n)), dim3(256), 0, st, g);
-        else if (wide_depth == 3) hipLaunchKernelGGL((segconv_wide_kernel<2, 3>), dim3(seg_map(g.map, (n_pt + 7) / 8, groups, n)), dim3(256), 0, st, g);
-        else if (wide_depth == 8) hipLaunchKernelGGL((segconv_wide_kernel<2, 8>), dim3(seg_map(g.map, (n_pt + 7) / 8, groups, n)), dim3(256), 0, st, g);
-        else hipLaunchKernelGGL((segconv_wide_kernel<2, 6>), dim3(seg_map(g.map, (n_pt + 7) / 8, groups, n)), dim3(256), 0, st, g);
-    } else if (!no_wide && a.n_kb >= 6 && (long)groups * ((n_pt + 3) / 4) * n >= wide1_min) {
-        variant = use_tile ? "tile<1>" : "wide<1>";
-        if (use_tile && tile_u == 4) hipLaunchKernelGGL((segconv_tile_kernel<1, 4>), dim3(seg_map(g.map, (n_pt + 3) / 4, groups, n)), dim3(256), 0, st, g);
-        else if (use_tile && tile_u == 2) hipLaunchKernelGGL((segconv_tile_kernel<1, 2>), dim3(seg_map(g.map, (n_pt + 3) / 4, groups, n)), dim3(256), 0, st, g);
-        else if (use_tile) hipLaunchKernelGGL((segconv_tile_kernel<1, 1>), dim3(seg_map(g.map, (n_pt + 3) / 4, groups, n)), dim3(256), 0, st, g);
-        else if (wide_depth == 3) hipLaunchKernelGGL((segconv_wide_kernel<1, 3>), dim3(seg_map(g.map, (n_pt + 3) / 4, groups, n)), dim3(256), 0, st, g);
-        else if (wide_depth == 8) hipLaunchKernelGGL((segconv_wide_kernel<1, 8>), dim3(seg_map(g.map, (n_pt + 3) / 4, groups, n)), dim3(256), 0, st, g);
-        else hipLaunchKernelGGL((segconv_wide_kernel<1, 6>), dim3(seg_map(g.map, (n_pt + 3) / 4, groups, n)), dim3(256), 0, st, g);
-    } else if (waves2 >= 1024 || a.n_kb < splitk_min_kb) {
+    } else if (a.n_kb >= kWideMinKb && (long)groups * ((n_pt + 7) / 8) * n >= kWideMinBlocks) {
+        variant = "wide<2>";
+        hipLaunchKernelGGL((segconv_wide_kernel<2>), dim3(seg_map(g.map, (n_pt + 7) / 8, groups, n)), dim3(256), 0, st, g);
+    } else if (waves2 >= kPlainMinWaves || a.n_kb < kSplitKMinKb) {
         if (groups == 1) {
             variant = "<4,2,1,1>";
             hipLaunchKernelGGL((segconv_kernel<4, 2, 1, 1, 3>), dim3(seg_map(g.map, (n_pt + 7) / 8, 1, n)), dim3(256), 0, st, g);
-        } else if (n_pt >= plain_nw1_min) {
+        } else if (n_pt >= kPlainNw1Min) {
             variant = "<4,1,2,1>";
             hipLaunchKernelGGL((segconv_kernel<4, 1, 2, 1, 3>), dim3(seg_map(g.map, (n_pt + 1) / 2, (groups + 1) / 2, n)), dim3(256), 0, st, g);
         } else {
@@ -1652,15 +1073,15 @@ int seg_launch(SegGroupArgs &g, int n, hipStream_t st)
         // small layers want many small blocks; cross-block K splitting is not an option - the device-scope fence it
         // needs writes back the whole L2 and doubled the frame time)
         int mw = 4;
-        while (mw > 1 && (long)n_pt * (a.n_ct / mw) * n < 150) mw /= 2;
-        if (force_mw) mw = force_mw;
+        while (mw > 1 && (long)n_pt * (a.n_ct / mw) * n < kSplitKMinBlocks) mw /= 2;
+        const long blocks_nw2 = (long)((n_pt + 1) / 2) * groups * n;
         if (mw == 1) {
             variant = "<1,1,1,4>";
             hipLaunchKernelGGL((segconv_kernel<1, 1, 1, 4, 3>), dim3(seg_map(g.map, n_pt, a.n_ct, n)), dim3(256), 0, st, g);
         } else if (mw == 2) {
             variant = "<2,1,1,4>";
             hipLaunchKernelGGL((segconv_kernel<2, 1, 1, 4, 3>), dim3(seg_map(g.map, n_pt, a.n_ct / 2, n)), dim3(256), 0, st, g);
-        } else if (n_pt >= splitk_nw2_min || (a.n_kb >= nw2_min_kb && (long)((n_pt + 1) / 2) * groups * n >= 150 && (long)((n_pt + 1) / 2) * groups * n < nw2_max_blocks)) {
+        } else if (a.n_kb >= kNw2MinKb && blocks_nw2 >= kSplitKMinBlocks && blocks_nw2 < kNw2MaxBlocks) {
             // two pixel tiles per wave (each weight fragment feeds twice the MFMAs) where that still leaves 150 .. 400 blocks:
             // measured per layer (round 5): -1 .. -3.4 us on the 30x40 3x3 layers, layer4's 3x3 and 2048 -> 512, the first
             // transposed convolution; slower with fewer blocks (15x20 maps of 256 channels) and with many (60x80 maps)
@@ -1671,10 +1092,7 @@ int seg_launch(SegGroupArgs &g, int n, hipStream_t st)
             hipLaunchKernelGGL((segconv_kernel<4, 1, 1, 4, 3>), dim3(seg_map(g.map, n_pt, groups, n)), dim3(256), 0, st, g);
         }
     }
-    if (trace)
-        fprintf(stderr, "segconv %-10s n %d  c_in %4d c_out %4d k %d s %d d %2d  in %3dx%3d out %3dx%3d  n_kb %4d  grid %dx%dx%d S %d%s%s%s\n", variant, n,
-                a.c8 * 8, a.c_out, a.ksize, a.stride, a.dil, a.H, a.W, a.Ho, a.Wo, a.n_kb, g.map.X, g.map.Y, g.map.Z, g.map.S,
-                a.res ? " +res" : "", a.mul ? " *mul" : "", a.up > 1 ? " deconv" : "");
+    seg_trace(variant, 10, n, a, g.map);
     return check_hip(hipGetLastError(), "segconv_kernel launch");
 }
 
@@ -1686,8 +1104,6 @@ int seg_launch(SegGroupArgs &g, int n, hipStream_t st)
 // launches (the forms differ in what a block is).  Launches cost ~4.7 us each before any work: 17 fewer per frame.
 int seg_launch_multi(SegGroupArgs &g, int n, hipStream_t st)
 {
-    static const int no_multi = getenv("OJF_SEG_NO_MULTI") ? atoi(getenv("OJF_SEG_NO_MULTI")) : 0;  // A/B switch
-    static const int trace = getenv("OJF_SEG_TRACE") ? atoi(getenv("OJF_SEG_TRACE")) : 0;
     int n_split = 0, n_plain = 0, X1 = 0, Y1 = 0, X2 = 0, Y2 = 0;
     long sk_blocks4 = 0;
     bool special = false;
@@ -1706,15 +1122,15 @@ int seg_launch_multi(SegGroupArgs &g, int n, hipStream_t st)
         for (int j = 0; j < n; ++j) same += same_shape(i, j) ? 1 : 0;
         special = special || a.rng != nullptr || a.rng_bump != nullptr;
         const long waves2 = (long)groups * ((n_pt + 1) / 2) * same;
-        if (a.n_kb >= 6 && (long)groups * ((n_pt + 7) / 8) * same >= 256) special = true;  // (a wide-kernel layer: with its own group)
-        if (waves2 >= 1024 || a.n_kb < 8) ++n_plain; else ++n_split;
+        if (a.n_kb >= kWideMinKb && (long)groups * ((n_pt + 7) / 8) * same >= kWideMinBlocks) special = true;  // (a wide-kernel layer: with its own group)
+        if (waves2 >= kPlainMinWaves || a.n_kb < kSplitKMinKb) ++n_plain; else ++n_split;
         X1 = n_pt > X1 ? n_pt : X1;
         Y1 = a.n_ct > Y1 ? a.n_ct : Y1;
         X2 = (n_pt + 3) / 4 > X2 ? (n_pt + 3) / 4 : X2;
         Y2 = (groups + 1) / 2 > Y2 ? (groups + 1) / 2 : Y2;
         sk_blocks4 += (long)n_pt * groups;
     }
-    if (no_multi || special || (n_split && n_plain)) {  // the natural groups, one launch each
+    if (special || (n_split && n_plain)) {  // the natural groups, one launch each
         bool done[kSegGroup] = {};
         for (int i = 0; i < n; ++i) {
             if (done[i]) continue;
@@ -1730,7 +1146,7 @@ int seg_launch_multi(SegGroupArgs &g, int n, hipStream_t st)
     const char *variant;
     int mw = 4;
     if (!n_plain)
-        while (mw > 1 && sk_blocks4 * (4 / mw) < 150) mw /= 2;
+        while (mw > 1 && sk_blocks4 * (4 / mw) < kSplitKMinBlocks) mw /= 2;
     g.het.n = n;
     g.het.off[0] = 0;
     for (int i = 0; i < n; ++i) {
@@ -1746,7 +1162,7 @@ int seg_launch_multi(SegGroupArgs &g, int n, hipStream_t st)
     else if (mw == 1) { variant = "multi<1,1,1,4>"; hipLaunchKernelGGL((segconv_kernel<1, 1, 1, 4, 3>), grid, dim3(256), 0, st, g); }
     else if (mw == 2) { variant = "multi<2,1,1,4>"; hipLaunchKernelGGL((segconv_kernel<2, 1, 1, 4, 3>), grid, dim3(256), 0, st, g); }
     else { variant = "multi<4,1,1,4>"; hipLaunchKernelGGL((segconv_kernel<4, 1, 1, 4, 3>), grid, dim3(256), 0, st, g); }
-    if (trace)
+    if (seg_trace_on())
         for (int i = 0; i < n; ++i) {
             const SegArgs &a = g.a[i];
             fprintf(stderr, "segconv %-14s member %d/%d  c_in %4d c_out %4d k %d s %d d %2d  in %3dx%3d out %3dx%3d  n_kb %4d  grid %dx%dx%d S %d%s%s\n", variant, i, n,

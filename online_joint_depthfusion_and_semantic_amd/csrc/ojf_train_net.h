@@ -564,7 +564,6 @@ struct ojf_trainer {
     std::vector<hipEvent_t> fork_ev;
     hipEvent_t join_ev = nullptr;
     size_t next_fork = 0;
-    bool use_side = true;
     int fwd_arith = OJF_ARITH_F16X3;  // arithmetic of the forward AND backward-data convolutions (ojf_trainer_set_arithmetic)
     // power-of-two factors the dy tensors are stored with (one per unit; the four entries of a VortexPooling share one),
     // written by every backward pass's own BatchNorm-backward launches before their consumers read them
@@ -746,13 +745,11 @@ struct TCtx {
     hipStream_t st;
 };
 
-// stream of the weight-gradient launches of one unit group: the side stream (after a fork from the main stream, whose
-// dy is what they read) or the main stream itself
+// stream of the weight-gradient launches of one unit group: the side stream, after a fork from the main stream, whose
+// dy is what they read
 static int t_wgrad_stream(TCtx &c, hipStream_t *ws)
 {
     ojf_trainer *t = c.t;
-    *ws = c.st;
-    if (!t->use_side || !t->side) return 0;
     hipEvent_t e = t->fork_ev[t->next_fork++ % t->fork_ev.size()];
     OJF_HIP(hipEventRecord(e, c.st));
     OJF_HIP(hipStreamWaitEvent(t->side, e, 0));
@@ -1025,13 +1022,6 @@ static int t_units_forward(TCtx &c, const int *ids, int n, bool conv = true)
 
 // backward of up to four units: BatchNorm / activation backward (dy, d gamma, d beta, d bias); then - unless `tail` is
 // false (stacked entry: the caller pools dy first) - the weight gradient and backward-data
-// weight gradients in split-fp16: with the forward arithmetic, from the pass on whose dy carries measured factors
-static inline bool t_wgrad_f16(const ojf_trainer *t)
-{
-    static const bool off = getenv("OJF_TRAIN_WGRAD16") && atoi(getenv("OJF_TRAIN_WGRAD16")) == 0;  // A/B switch
-    return !off && t_bwd_f16(t);
-}
-
 static int t_units_backward(TCtx &c, const int *ids, int n, bool tail = true)
 {
     ojf_trainer *t = c.t;
@@ -1081,7 +1071,7 @@ static int t_units_backward(TCtx &c, const int *ids, int n, bool tail = true)
         wg.tiles = tiles;
         hipStream_t ws;
         if (t_wgrad_stream(c, &ws)) return -2;
-        if (t_wgrad_f16(t))
+        if (t_bwd_f16(t))
             hipLaunchKernelGGL(train_wgrad_mfma_kernel<true>, dim3(u0.wplan.slabs, tiles * n, taps), dim3(64), 0, ws, wg,
                                div_magic(t->w, (uint64_t)t->npix + 2 * kWgChunk));
         else
@@ -1165,7 +1155,7 @@ static int t_vortex_backward(TCtx &c, TVortex &v)
         hipStream_t ws;
         hipLaunchKernelGGL(train_pyramid_kernel, dim3(tiles, 4 * v.sl4), dim3(256), 0, c.st, pa);
         if (t_wgrad_stream(c, &ws)) return -2;
-        if (t_wgrad_f16(t))
+        if (t_bwd_f16(t))
             hipLaunchKernelGGL(train_wgrad_mfma_kernel<true>, dim3(a.slabs, wt, 1), dim3(64), 0, ws, WgradGroup{{a, a, a, a}, wt},
                                div_magic(t->w, (uint64_t)t->npix + 2 * kWgChunk));
         else
@@ -1288,10 +1278,9 @@ static int t_backward_net(TCtx &c)
             if (t_units_backward(c, &id, 1)) return -2;
         }
     }
-    if (t->use_side && t->side) {  // the gradient tensors are complete for whatever the caller enqueues next
-        OJF_HIP(hipEventRecord(t->join_ev, t->side));
-        OJF_HIP(hipStreamWaitEvent(c.st, t->join_ev, 0));
-    }
+    // the gradient tensors are complete for whatever the caller enqueues next
+    OJF_HIP(hipEventRecord(t->join_ev, t->side));
+    OJF_HIP(hipStreamWaitEvent(c.st, t->join_ev, 0));
     OJF_HIP(hipMemsetAsync(t->bnd_pool, 0, t->bnd_words * 4, c.st));  // (behind every launch that read this pass's bounds)
     ++t->launches;
     return check_hip(hipGetLastError(), "ojf_trainer_backward");
@@ -1309,7 +1298,7 @@ static inline unsigned long long t_addr(const void *p) { return (unsigned long l
 static unsigned long long t_pass_key(const ojf_trainer *t, const ojf_train_layer *L, int backward)
 {
     unsigned long long h = 1469598103934665603ull;
-    t_mix(h, (unsigned long long)backward * 4 + (unsigned long long)t->fwd_arith * 2 + (unsigned long long)t->bwd_arith * 16 + (t->use_side ? 1 : 0));
+    t_mix(h, (unsigned long long)backward * 4 + (unsigned long long)t->fwd_arith * 2 + (unsigned long long)t->bwd_arith * 16 + 1);  // (+ 1: the side stream, once a switch; kept so that recorded plan hashes do not move)
     for (int i = 0; i < t->n_layers; ++i) {
         const ojf_train_layer &l = L[i];
         const void *ptrs[] = {l.weight, l.bias, l.gamma, l.beta, l.running_mean, l.running_var, l.drop_scale};
@@ -1473,21 +1462,15 @@ OJF_API int ojf_trainer_create(ojf_trainer **out, int version, int n_points, int
     };
     rc = build();
     if (!rc) {
-        static const bool no_side = getenv("OJF_TRAIN_SIDE") && atoi(getenv("OJF_TRAIN_SIDE")) == 0;  // A/B switch
-        t->use_side = !no_side;
-        if (t->use_side) {
-            rc = check_hip(hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking), "trainer side stream");
-            for (int i = 0; i < 48 && !rc; ++i) {
-                hipEvent_t e = nullptr;
-                rc = check_hip(hipEventCreateWithFlags(&e, event_flags()), "trainer fork event");
-                if (!rc) t->fork_ev.push_back(e);
-            }
-            if (!rc) rc = check_hip(hipEventCreateWithFlags(&t->join_ev, event_flags()), "trainer join event");
+        rc = check_hip(hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking), "trainer side stream");
+        for (int i = 0; i < 48 && !rc; ++i) {
+            hipEvent_t e = nullptr;
+            rc = check_hip(hipEventCreateWithFlags(&e, event_flags()), "trainer fork event");
+            if (!rc) t->fork_ev.push_back(e);
         }
+        if (!rc) rc = check_hip(hipEventCreateWithFlags(&t->join_ev, event_flags()), "trainer join event");
     }
     if (rc) { ojf_trainer_destroy(t); return rc; }
-    static const bool graph_env = getenv("OJF_TRAIN_GRAPH") && atoi(getenv("OJF_TRAIN_GRAPH")) != 0;  // A/B switch
-    t->graph_on = graph_env;
     *out = t;
     return 0;
 }

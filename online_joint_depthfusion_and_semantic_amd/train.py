@@ -270,7 +270,7 @@ class HipTrainNet:
         self._masks = {}
         self.graph = bool(graph)  # capture forward / backward into device graphs (falls back to eager launches if a capture fails)
         # executor passes replayed as device graphs inside the library (ojf_trainer_set_graph): None = the library's default
-        # (off; OJF_TRAIN_GRAPH=1 in the environment), True / False = set per trainer
+        # (off), True / False = set per trainer
         self.replay = replay
         self._graphs = {}
         # overlap (FUSION_MODEL.train_overlap; needs executor + inplace_grads): the backward pass of frame k runs on a stream of its

@@ -1,4 +1,5 @@
-"""Profiling helper (not a test): times ojf_integrate's accumulate stage under OJF_ABLATE / OJF_INTEGRATE_DIRECT."""
+"""Profiling helper (not a test): times ojf_integrate's accumulate stage with and without OJF_INTEGRATE_WAVE_COMBINE
+(the one accumulate switch the library reads)."""
 import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -21,4 +22,4 @@ torch.cuda.synchronize()
 t0 = time.perf_counter()
 for i in range(80): run(i)
 torch.cuda.synchronize()
-print('ABLATE=%s DIRECT=%s: %.1f us per integrate call' % (os.environ.get('OJF_ABLATE'), os.environ.get('OJF_INTEGRATE_DIRECT'), (time.perf_counter() - t0) / 80 * 1e6))
+print('WAVE_COMBINE=%s: %.1f us per integrate call' % (os.environ.get('OJF_INTEGRATE_WAVE_COMBINE'), (time.perf_counter() - t0) / 80 * 1e6))

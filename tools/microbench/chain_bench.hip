@@ -61,7 +61,7 @@ int main(int argc, char **argv)
         ConvBuilder ba((i + 1) * cs, cs, 3, 1), bb(cs, cs, 3, 1);
         ba.add(la, 0, (i + 1) * c, slot_map((i + 1) * c, c, cs), 0, true);
         bb.add(lb, 0, c, slot_map(c, c, cs), 0, true);
-        if (finish_pair(ba, bb, pairs[i], pair_cfg_for(h, w, cs))) { printf("pack failed: %s\n", ojf_last_error()); return 1; }
+        if (finish_pair(ba, bb, pairs[i], pair_cfg_for(h, w))) { printf("pack failed: %s\n", ojf_last_error()); return 1; }
         bas.push_back(ba);
         bbs.push_back(bb);
     }

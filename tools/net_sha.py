@@ -1,5 +1,5 @@
 """Profiling helper (not a test): sha256 of the HIP fusion net's output at a frame size + its time per forward pass and the per-kernel
-profile (python tools/net_sha.py [h w [sem]]): A/B of switches that must not change a bit (OJF_CONV_ROW_PERM, OJF_NO_XCD_BAND, ...)."""
+profile (python tools/net_sha.py [h w [sem]]): A/B of two builds (or of a test-only switch) that must not change a bit."""
 import hashlib, os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from online_joint_depthfusion_and_semantic_amd.config import default_config
