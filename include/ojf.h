@@ -586,6 +586,30 @@ int ojf_track_associate(const float *depth_dev, const uint8_t *mask_dev, int h, 
                         double *pose_dev, double *sums_dev, float *jr_dev, uint8_t *reason_dev, int *status_dev,
                         ojf_stream_t stream);
 
+/* ---- PROJECTIVE (classical voxel-projective TSDF fusion, no network; no counterpart in the reference) ----------------
+ * ojf_fuse_projective: fuses n depth views (1 <= n <= OJF_PROJECTIVE_MAX_VIEWS, one h x w for all) into the fp16 volumes
+ *   tsdf_dev / weights_dev [X,Y,Z] in place, Curless-Levoy / KinectFusion style: every voxel centre (origin +
+ *   (i+0.5)*resolution, the frame of extract / integrate / render) is projected into each view in turn (pixel =
+ *   floor(projection + 0.5)); with d the depth there (finite, > 0, mask_dev NULL or non-zero) and zc > near the voxel's
+ *   camera depth, s = d - zc; a voxel with -trunc <= s <= trunc (carve == 1: every s >= -trunc, the free space in front of
+ *   the surface is pulled to +trunc) takes T = (W*T + min(s, trunc)) / (W + 1), W = min(W + 1, max_weight), rounded to fp16
+ *   after every view.  With ids_dev u8 / scores_dev fp16 [X,Y,Z] and labels_dev u8[n,h,w] (all given or all NULL), a
+ *   voxel inside the band takes the pixel's label when its score (label_scores_dev f32[n,h,w], NULL: 1.0; rounded to
+ *   fp16) is greater than the stored one.  K_host f64[n][9] pinhole intrinsics (entries other than fx, fy, cx, cy must be
+ *   0,0,0,0,1), E_host f64[n][12] camera-to-world (rigid; its transpose serves as the inverse).  trunc > 0,
+ *   1 <= max_weight <= 2048, near >= 0, carve 0 | 1.  Bad arguments are refused before any HIP call.  Every voxel is
+ *   owned by one lane, which walks the views in order: no atomics, no workspace, the same bits on every run, and n views
+ *   in one call give the bits of n calls of one view.  Volume pointers that are not 16-byte (ids: 8-byte) aligned are
+ *   served by element-wise accesses.  Enqueues one kernel on `stream` and never waits.  The exact fp32 operation order
+ *   is in csrc/ojf_projective.hip. */
+#define OJF_PROJECTIVE_MAX_VIEWS 32
+int ojf_fuse_projective(uint16_t *tsdf_dev, uint16_t *weights_dev, uint8_t *ids_dev, uint16_t *scores_dev,
+                        int X, int Y, int Z, const double *origin_host, double resolution, int n,
+                        const double *K_host /* f64[n][9] */, const double *E_host /* f64[n][12] */,
+                        const float *depth_dev /* f32[n,h,w] */, const uint8_t *mask_dev /* u8[n,h,w] or NULL */,
+                        const uint8_t *labels_dev /* u8[n,h,w] or NULL */, const float *label_scores_dev /* or NULL */,
+                        int h, int w, float trunc, float max_weight, float near, int carve, ojf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,7 @@ RENDER_MAX_VIEWS = 64  # include/ojf.h OJF_RENDER_MAX_VIEWS
 TRACK_MAX_LEVELS = 4  # include/ojf.h OJF_TRACK_MAX_LEVELS
 TRACK_MAX_ITERATIONS = 128  # include/ojf.h OJF_TRACK_MAX_ITERATIONS
 TRACK_TERMS = 29  # include/ojf.h OJF_TRACK_TERMS
+PROJECTIVE_MAX_VIEWS = 32  # include/ojf.h OJF_PROJECTIVE_MAX_VIEWS
 
 
 class ExtractJob(ctypes.Structure):
@@ -159,6 +160,9 @@ SIGNATURES = {
     # workspace, workspace_bytes, pose, sums, jr, reason, status, stream
     'ojf_track_associate': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _vp, _sz, _vp, _vp, _vp,
                                  _vp, _vp, _vp]),
+    # tsdf, weights, ids, scores, X, Y, Z, origin, resolution, n, K, E, depth, mask, labels, label scores, h, w, trunc,
+    # max_weight, near, carve, stream
+    'ojf_fuse_projective': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _i, _vp]),
 }
 
 _LIB = None

@@ -281,6 +281,27 @@ class Database(torch.utils.data.Dataset):
                                     depth=depth, intrinsics=intrinsics, extrinsics=extrinsics,
                                     reference_extrinsics=reference_extrinsics, **kw)
 
+    def integrate_depth(self, scene_id, depth, intrinsics, extrinsics, mask=None, labels=None, label_scores=None, **kw):
+        """Fuse one or more depth maps into the resident volumes of a scene by classical projective TSDF averaging
+        (projective.py, no network): depth [h,w] / [n,h,w], poses as for ``render``; ``labels`` (u8, with optional
+        ``label_scores``) also update ids_est / scores when the database has semantics; ``kw`` goes to
+        ``projective.integrate_depth`` (truncation - default: the initial value -, max_weight, near, carve)."""
+        from . import projective
+        tsdf, w = self.scenes_est[scene_id].volume, self.fusion_weights[scene_id]
+        if not (_is_dev(tsdf) and _is_dev(w)):
+            raise ValueError('Database.integrate_depth: the volumes of {!r} are not resident on the device (to_torch())'.format(scene_id))
+        kw.setdefault('truncation', self.initial_value)
+        sem = bool(self.semantics) and labels is not None
+
+        def dev(x):
+            return None if x is None else torch.as_tensor(x).to(tsdf.device)
+        projective.integrate_depth(tsdf, w, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]),
+                                   depth=dev(depth), intrinsics=intrinsics, extrinsics=extrinsics, mask=dev(mask),
+                                   ids=self.ids_est[scene_id].volume if sem else None,
+                                   scores=self.scores[scene_id].volume if sem else None,
+                                   labels=dev(labels) if sem else None, label_scores=dev(label_scores) if sem else None, **kw)
+        self.state[scene_id] = True
+
     def save_to_workspace(self, workspace, mode, save_mode='ply'):
         """database.py:141-177: every scene that holds integrated frames goes to the workspace's output directory as
         ``<scene>.tsdf_<mode>.hf5`` / ``.weights_<mode>.hf5`` / ``.semantic_<mode>.hf5`` ('tsdf'), ``<scene>_<mode>.ply``
