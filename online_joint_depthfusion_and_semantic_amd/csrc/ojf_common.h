@@ -12,6 +12,7 @@ namespace ojf {
 
 void set_error(const std::string &msg);
 int fail(const std::string &msg);
+inline int refuse(const char *who, const char *what) { return fail(std::string(who) + ": " + what); }  // "<entry point>: <what>"
 int check_hip(hipError_t e, const char *what);
 
 #define OJF_HIP(call)                                  \

@@ -264,6 +264,73 @@ __global__ __launch_bounds__(256) void extract_kernel(ExtractArgs a, Camera cam)
     extract_item(a, n, k, cv, dir, pw);
 }
 
+// ---- host side: every entry point describes its scenes as ojf_extract_job and goes through extract_fill + launch_tiles ----
+struct ExtractDebug { int64_t *idx = nullptr; double *w = nullptr; double *pts = nullptr; float *pcl = nullptr; };  // ojf_extract only
+
+// the dimensions all jobs of a call share; max_points: kMaxTilePoints for a call that has no extract_kernel to fall back to, 0 = any
+static int extract_check_dims(const char *who, int X, int Y, int Z, int h, int w, int n_points, int max_points)
+{
+    if (X <= 0 || Y <= 0 || Z <= 0 || h <= 0 || w <= 0) return refuse(who, "non-positive volume or frame size");
+    if (n_points < 1 || (n_points & 1) == 0 || (max_points && n_points > max_points)) return refuse(who, max_points ? "n_points must be odd, 1..16" : "n_points must be odd and >= 1");
+    if ((int64_t)h * w * n_points > 0x7fffffffLL) return refuse(who, "frame too large");
+    return 0;
+}
+
+// One scene's description -> the kernels' arguments, with every per-job check (before any HIP call).  `who`: the entry point, for the
+// messages.  n_tiles is left to the caller: it follows the LAUNCH's tile shape, which ojf_extract_many takes from its first job.
+static int extract_fill(const char *who, const ojf_extract_job &j, const ExtractDebug &dbg, int X, int Y, int Z, int h, int w, int n_points,
+                        float pad_value, ExtractArgs &a, Camera &cam)
+{
+    if (!j.depth_dev || !j.Kinv_host || !j.E_host || !j.origin_host || !j.tsdf_dev || !j.weights_dev) return refuse(who, "null pointer argument");
+    if (!(j.resolution > 0.0)) return refuse(who, "resolution must be > 0");
+    a = ExtractArgs{};
+    a.depth = j.depth_dev; a.tsdf = j.tsdf_dev; a.wgt = j.weights_dev;
+    a.X = X; a.Y = Y; a.Z = Z; a.h = h; a.w = w; a.n_points = n_points;
+    a.pad_value = pad_value;
+    if (j.net) {
+        NetInputSlot slot;
+        if (net_input_slot(j.net, &slot)) return refuse(who, "this net takes a semantic channel or has two heads: hand over sample planes + ojf_net_prepare_input");
+        if (slot.h != h || slot.w != w || slot.P != n_points) return refuse(who, "frame size / n_points differ from the net's");
+        if (n_points > kMaxTilePoints || 4 * slot.cs4 > kNetPitch || 2 * n_points + 1 > 4 * slot.cs4) return refuse(who, "unsupported n_points / slot width");
+        a.out_stride = h * w; a.out_layout = 2;
+        a.net_x0 = reinterpret_cast<float4 *>(slot.x0); a.net_cs4 = slot.cs4; a.ovf = slot.ovf; a.net_split = slot.split;
+    } else {
+        if (!j.out_values_dev || !j.out_weights_dev) return refuse(who, "null pointer argument (a net or both output buffers)");
+        if (j.out_layout != 0 && j.out_layout != 1) return refuse(who, "out_layout must be 0 (rows) or 1 (sample planes)");
+        if (j.out_layout == 0 ? j.out_stride < n_points : j.out_stride < h * w) return refuse(who, "output stride too small (rows: n_points, planes: h*w)");
+        a.out_values = j.out_values_dev; a.out_weights = j.out_weights_dev; a.out_stride = j.out_stride; a.out_layout = j.out_layout;
+        a.dbg_idx = dbg.idx; a.dbg_w = dbg.w; a.dbg_pts = dbg.pts; a.dbg_pcl = dbg.pcl;
+    }
+    cam = make_camera(j.Kinv_host, j.E_host, j.origin_host, j.resolution);
+    return 0;
+}
+
+// Launch of extract_tile_kernel (scenes = 1, args = ExtractArgs, Camera) or extract_tile_many_kernel (args = ExtractMany) in the tile
+// shape `cols` picks: n_tiles rounded up to a multiple of 8 (XCD bands) x scenes blocks of extract_block_waves(n_points) waves
+template <typename... A>
+static void launch_tiles(void (*columns)(A...), void (*rows)(A...), bool cols, int n_tiles, int scenes, int n_points, ojf_stream_t stream, const A &...args)
+{
+    hipLaunchKernelGGL(cols ? columns : rows, dim3((n_tiles + 7) / 8 * 8, scenes), dim3(64 * extract_block_waves(n_points)), 0, as_stream(stream), args...);
+}
+
+static int extract_one(const char *who, const ojf_extract_job &j, const ExtractDebug &dbg, int X, int Y, int Z, int h, int w, int n_points,
+                       float pad_value, ojf_stream_t stream)
+{
+    if (int rc = extract_check_dims(who, X, Y, Z, h, w, n_points, j.net ? kMaxTilePoints : 0)) return rc;
+    ExtractArgs a;
+    Camera cam;
+    if (int rc = extract_fill(who, j, dbg, X, Y, Z, h, w, n_points, pad_value, a, cam)) return rc;
+    const bool cols = extract_columns(j.E_host);
+    a.n_tiles = extract_tiles(h, w, cols);
+    if (n_points <= kMaxTilePoints) {
+        launch_tiles(extract_tile_kernel<4, 16>, extract_tile_kernel<16, 4>, cols, a.n_tiles, 1, n_points, stream, a, cam);
+    } else {
+        hipLaunchKernelGGL(extract_kernel, dim3((h * w * n_points + 255) / 256), dim3(256), 0, as_stream(stream), a, cam);
+    }
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : check_hip(e, (std::string(who) + " launch").c_str());
+}
+
 }  // namespace ojf
 
 OJF_API int ojf_extract(const float *depth, const float *Ki, const float *E, const double *origin,
@@ -272,54 +339,21 @@ OJF_API int ojf_extract(const float *depth, const float *Ki, const float *E, con
                         float *out_weights, int out_stride, int out_layout, int64_t *dbg_idx, double *dbg_w,
                         double *dbg_pts, float *dbg_pcl, ojf_stream_t stream)
 {
-    using namespace ojf;
-    if (!depth || !Ki || !E || !origin || !tsdf || !wgt || !out_values || !out_weights)
-        return fail("ojf_extract: null pointer argument");
-    if (X <= 0 || Y <= 0 || Z <= 0 || h <= 0 || w <= 0)
-        return fail("ojf_extract: non-positive volume or frame size");
-    if (n_points < 1 || (n_points & 1) == 0) return fail("ojf_extract: n_points must be odd and >= 1");
-    if (out_layout != 0 && out_layout != 1) return fail("ojf_extract: out_layout must be 0 (rows) or 1 (sample planes)");
-    if (out_layout == 0 && out_stride < n_points) return fail("ojf_extract: out_stride < n_points");
-    if (out_layout == 1 && out_stride < h * w) return fail("ojf_extract: plane stride < h*w");
-    if ((int64_t)h * w * n_points > 0x7fffffffLL) return fail("ojf_extract: frame too large");
-    if (!(res > 0.0)) return fail("ojf_extract: resolution must be > 0");
-    ExtractArgs a{depth, tsdf, wgt, out_values, out_weights, dbg_idx, dbg_w, dbg_pts, dbg_pcl,
-                  X, Y, Z, h, w, n_points, out_stride, out_layout, pad_value, nullptr, 0, nullptr, 0};
-    const bool cols = extract_columns(E);
-    a.n_tiles = extract_tiles(h, w, cols);
-    const Camera cam = make_camera(Ki, E, origin, res);
-    if (n_points <= kMaxTilePoints) {
-        if (cols) hipLaunchKernelGGL((extract_tile_kernel<4, 16>), dim3((a.n_tiles + 7) / 8 * 8), dim3(64 * extract_block_waves(n_points)), 0, as_stream(stream), a, cam);
-        else hipLaunchKernelGGL((extract_tile_kernel<16, 4>), dim3((a.n_tiles + 7) / 8 * 8), dim3(64 * extract_block_waves(n_points)), 0, as_stream(stream), a, cam);
-    } else {
-        const int items = h * w * n_points;
-        hipLaunchKernelGGL(extract_kernel, dim3((items + 255) / 256), dim3(256), 0, as_stream(stream), a, cam);
-    }
-    return check_hip(hipGetLastError(), "ojf_extract launch");
+    ojf_extract_job j{};
+    j.depth_dev = depth; j.Kinv_host = Ki; j.E_host = E; j.origin_host = origin; j.resolution = res; j.tsdf_dev = tsdf; j.weights_dev = wgt;
+    j.out_values_dev = out_values; j.out_weights_dev = out_weights; j.out_stride = out_stride; j.out_layout = out_layout;
+    const ojf::ExtractDebug dbg{dbg_idx, dbg_w, dbg_pts, dbg_pcl};
+    return ojf::extract_one("ojf_extract", j, dbg, X, Y, Z, h, w, n_points, pad_value, stream);
 }
 
 OJF_API int ojf_extract_to_net(const float *depth, const float *Ki, const float *E, const double *origin, double res,
                                const uint16_t *tsdf, const uint16_t *wgt, int X, int Y, int Z, int h, int w, int n_points,
                                float pad_value, ojf_net *net, ojf_stream_t stream)
 {
-    using namespace ojf;
-    if (!depth || !Ki || !E || !origin || !tsdf || !wgt || !net) return fail("ojf_extract_to_net: null pointer argument");
-    if (X <= 0 || Y <= 0 || Z <= 0 || h <= 0 || w <= 0) return fail("ojf_extract_to_net: non-positive volume or frame size");
-    if (!(res > 0.0)) return fail("ojf_extract_to_net: resolution must be > 0");
-    NetInputSlot slot;
-    if (net_input_slot(net, &slot))
-        return fail("ojf_extract_to_net: this net takes a semantic channel or has two heads: use ojf_extract + ojf_net_prepare_input");
-    if (slot.h != h || slot.w != w || slot.P != n_points) return fail("ojf_extract_to_net: frame size / n_points differ from the net's");
-    if (n_points < 1 || (n_points & 1) == 0 || n_points > kMaxTilePoints || 4 * slot.cs4 > kNetPitch || 2 * n_points + 1 > 4 * slot.cs4)
-        return fail("ojf_extract_to_net: unsupported n_points / slot width");
-    ExtractArgs a{depth, tsdf, wgt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                  X, Y, Z, h, w, n_points, h * w, 2, pad_value, reinterpret_cast<float4 *>(slot.x0), slot.cs4, slot.ovf, slot.split};
-    const bool cols = extract_columns(E);
-    a.n_tiles = extract_tiles(h, w, cols);
-    const Camera cam = make_camera(Ki, E, origin, res);
-    if (cols) hipLaunchKernelGGL((extract_tile_kernel<4, 16>), dim3((a.n_tiles + 7) / 8 * 8), dim3(64 * extract_block_waves(n_points)), 0, as_stream(stream), a, cam);
-    else hipLaunchKernelGGL((extract_tile_kernel<16, 4>), dim3((a.n_tiles + 7) / 8 * 8), dim3(64 * extract_block_waves(n_points)), 0, as_stream(stream), a, cam);
-    return check_hip(hipGetLastError(), "ojf_extract_to_net launch");
+    ojf_extract_job j{};  // (no output buffers: a NULL net is refused as a job with nowhere to write)
+    j.depth_dev = depth; j.Kinv_host = Ki; j.E_host = E; j.origin_host = origin; j.resolution = res; j.tsdf_dev = tsdf; j.weights_dev = wgt;
+    j.net = net;
+    return ojf::extract_one("ojf_extract_to_net", j, ojf::ExtractDebug{}, X, Y, Z, h, w, n_points, pad_value, stream);
 }
 
 // One frame of each of n scenes (1 <= n <= OJF_MAX_SCENES) of ONE frame size and sample count as a single launch.
@@ -327,41 +361,22 @@ OJF_API int ojf_extract_many(int n, const ojf_extract_job *jobs, int X, int Y, i
                              ojf_stream_t stream)
 {
     using namespace ojf;
-    if (n < 1 || n > OJF_MAX_SCENES || !jobs) return fail("ojf_extract_many: 1..OJF_MAX_SCENES jobs");
-    if (X <= 0 || Y <= 0 || Z <= 0 || h <= 0 || w <= 0) return fail("ojf_extract_many: non-positive volume or frame size");
-    if (n_points < 1 || (n_points & 1) == 0 || n_points > kMaxTilePoints) return fail("ojf_extract_many: n_points must be odd, 1..16");
-    if ((int64_t)h * w * n_points > 0x7fffffffLL) return fail("ojf_extract_many: frame too large");
+    const char *who = "ojf_extract_many";
+    if (n < 1 || n > OJF_MAX_SCENES || !jobs) return refuse(who, "1..OJF_MAX_SCENES jobs");
+    if (int rc = extract_check_dims(who, X, Y, Z, h, w, n_points, kMaxTilePoints)) return rc;
     ExtractMany m;
     for (int i = 0; i < n; ++i) {
         const ojf_extract_job &j = jobs[i];
-        if (!j.depth_dev || !j.Kinv_host || !j.E_host || !j.origin_host || !j.tsdf_dev || !j.weights_dev) return fail("ojf_extract_many: null pointer in a job");
-        if (!(j.resolution > 0.0)) return fail("ojf_extract_many: resolution must be > 0");
+        if (int rc = extract_fill(who, j, ExtractDebug{}, X, Y, Z, h, w, n_points, pad_value, m.a[i], m.cam[i])) return rc;
         for (int k = 0; k < i; ++k)
             if ((j.net && j.net == jobs[k].net) || (j.out_values_dev && j.out_values_dev == jobs[k].out_values_dev))
-                return fail("ojf_extract_many: two jobs write the same output");
-        if (j.net) {
-            NetInputSlot slot;
-            if (net_input_slot(j.net, &slot))
-                return fail("ojf_extract_many: this net takes a semantic channel or has two heads: hand over sample planes instead");
-            if (slot.h != h || slot.w != w || slot.P != n_points) return fail("ojf_extract_many: frame size / n_points differ from the net's");
-            if (4 * slot.cs4 > kNetPitch || 2 * n_points + 1 > 4 * slot.cs4) return fail("ojf_extract_many: unsupported slot width");
-            m.a[i] = ExtractArgs{j.depth_dev, j.tsdf_dev, j.weights_dev, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                 X, Y, Z, h, w, n_points, h * w, 2, pad_value, reinterpret_cast<float4 *>(slot.x0), slot.cs4, slot.ovf, slot.split};
-        } else {
-            if (!j.out_values_dev || !j.out_weights_dev) return fail("ojf_extract_many: a job needs a net or output buffers");
-            if (j.out_layout != 0 && j.out_layout != 1) return fail("ojf_extract_many: out_layout must be 0 (rows) or 1 (sample planes)");
-            if (j.out_layout == 0 ? j.out_stride < n_points : j.out_stride < h * w) return fail("ojf_extract_many: output stride too small");
-            m.a[i] = ExtractArgs{j.depth_dev, j.tsdf_dev, j.weights_dev, j.out_values_dev, j.out_weights_dev, nullptr, nullptr, nullptr, nullptr,
-                                 X, Y, Z, h, w, n_points, j.out_stride, j.out_layout, pad_value, nullptr, 0, nullptr, 0};
-        }
-        m.cam[i] = make_camera(j.Kinv_host, j.E_host, j.origin_host, j.resolution);
+                return refuse(who, "two jobs write the same output");
     }
     // one tile shape per launch: the first scene's camera decides (any shape computes the same; the scenes of a call are usually filmed alike)
     const bool cols = extract_columns(jobs[0].E_host);
-    for (int i = 0; i < n; ++i) m.a[i].n_tiles = extract_tiles(h, w, cols);
-    const dim3 grid((extract_tiles(h, w, cols) + 7) / 8 * 8, n);
-    if (cols) hipLaunchKernelGGL((extract_tile_many_kernel<4, 16>), grid, dim3(64 * extract_block_waves(n_points)), 0, as_stream(stream), m);
-    else hipLaunchKernelGGL((extract_tile_many_kernel<16, 4>), grid, dim3(64 * extract_block_waves(n_points)), 0, as_stream(stream), m);
+    const int n_tiles = extract_tiles(h, w, cols);
+    for (int i = 0; i < n; ++i) m.a[i].n_tiles = n_tiles;
+    launch_tiles(extract_tile_many_kernel<4, 16>, extract_tile_many_kernel<16, 4>, cols, n_tiles, n, n_points, stream, m);
     return check_hip(hipGetLastError(), "ojf_extract_many launch");
 }
 

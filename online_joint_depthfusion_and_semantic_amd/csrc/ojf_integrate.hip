@@ -614,6 +614,58 @@ namespace ojf {
 // other: rounds 1-3 kept the phase on the host per workspace address, which is why the call refused stream capture): the
 // call sequence is the same every time and can be captured into a HIP graph.  Any phase is valid on a zeroed header
 // (fresh workspace, ojf_integrate_workspace_init, the entry-list and PARITY paths, which zero the header themselves).
+
+// ---- host side of the frame path: every entry point describes its scenes as ojf_integrate_job and goes through integrate_fill ----
+// the dimensions all jobs of a call share
+static int integrate_check_dims(const char *who, int n_points, int n_tail, int X, int Y, int Z, int h, int w)
+{
+    if (X <= 0 || Y <= 0 || Z <= 0 || h <= 0 || w <= 0) return refuse(who, "non-positive size");
+    if (n_points < 1 || (n_points & 1) == 0) return refuse(who, "n_points must be odd and >= 1");
+    if (n_tail < 1 || n_tail > n_points) return refuse(who, "need 1 <= n_tail <= n_points");
+    if ((uint64_t)X * Y * Z >= 0xffffffffull) return refuse(who, "volume has >= 2^32 voxels");
+    if ((uint64_t)h * w * n_tail * 8 >= 0xffffffffull) return refuse(who, "frame too large");
+    return 0;
+}
+
+// One scene's description -> the kernels' arguments, with every per-job check (before any HIP call).  `who`: the entry point, for the
+// messages.  The workspace is the header alone here (PARITY uses the rest its own way): FAST callers carve it with carve_workspace.
+static int integrate_fill(const char *who, const ojf_integrate_job &j, int n_points, int n_tail, float trunc, int X, int Y, int Z, int h, int w,
+                          int mode, uint32_t *stats, IntegrateArgs &a, Camera &cam)
+{
+    if (!j.depth_dev || !j.Kinv_host || !j.E_host || !j.origin_host || !j.est_dev || !j.tsdf_dev || !j.weights_dev || !j.workspace_dev)
+        return refuse(who, "null pointer argument");
+    if (j.est_stride < n_tail) return refuse(who, "est_stride < n_tail");
+    if (!(j.resolution > 0.0)) return refuse(who, "resolution must be > 0");
+    const int n_sem = (j.sem_ids_dev != nullptr) + (j.sem_scores_dev != nullptr) + (j.id_vol_dev != nullptr) + (j.score_vol_dev != nullptr);
+    if (n_sem != 0 && n_sem != 4) return refuse(who, "sem_ids, sem_scores, id_vol, score_vol must be all set or all NULL");
+    const size_t need = ojf_integrate_workspace_bytes(X, Y, Z, h, w, n_tail, mode);
+    if (need == 0) return refuse(who, "unknown mode");
+    if (j.workspace_bytes < need) return refuse(who, "workspace too small");
+    a = IntegrateArgs{};
+    a.depth = j.depth_dev; a.mask = j.mask_dev; a.est = j.est_dev; a.tsdf = j.tsdf_dev; a.wgt = j.weights_dev;
+    a.sem_ids = j.sem_ids_dev; a.sem_scores = j.sem_scores_dev; a.id_vol = j.id_vol_dev; a.score_vol = j.score_vol_dev;
+    a.counters = static_cast<unsigned int *>(j.workspace_dev);
+    a.guard = const_cast<int *>(range_guard_if_any());
+    a.stats = stats;
+    a.X = X; a.Y = Y; a.Z = Z; a.h = h; a.w = w; a.n_points = n_points; a.n_tail = n_tail;
+    a.est_stride = j.est_stride; a.trunc = trunc;
+    cam = make_camera(j.Kinv_host, j.E_host, j.origin_host, j.resolution);
+    return 0;
+}
+
+// FAST workspace: header | head table [nvox] | n_recs records | first-touch list | tile counts [tiles] (the frame path: a first-touch
+// list of n_recs elements; the entry-list path has no tiles and nothing behind its list)
+static void carve_workspace(IntegrateArgs &a, void *ws, size_t nvox, size_t n_recs, int tiles)
+{
+    char *q = static_cast<char *>(ws) + kHeaderBytes;
+    a.head = reinterpret_cast<unsigned int *>(q); q += nvox * sizeof(unsigned int);
+    a.recs = reinterpret_cast<VoxelRec *>(q); q += n_recs * sizeof(VoxelRec);
+    a.touched = reinterpret_cast<unsigned int *>(q);
+    a.tile_new = tiles ? a.touched + n_recs : nullptr;
+    a.n_tiles = tiles;
+    a.list_base = (unsigned int)tiles * kSlots;
+}
+
 }  // namespace ojf
 
 OJF_API size_t ojf_integrate_workspace_bytes(int X, int Y, int Z, int h, int w, int n_tail, int mode)
@@ -656,35 +708,18 @@ OJF_API int ojf_integrate_masked(const float *depth_filtered, const uint8_t *mas
                                  size_t ws_bytes, uint32_t *stats, ojf_stream_t stream)
 {
     using namespace ojf;
-    if (!depth_filtered || !Ki || !E || !origin || !est || !tsdf || !wgt || !ws)
-        return fail("ojf_integrate: null pointer argument");
-    if (X <= 0 || Y <= 0 || Z <= 0 || h <= 0 || w <= 0) return fail("ojf_integrate: non-positive size");
-    if (n_points < 1 || (n_points & 1) == 0) return fail("ojf_integrate: n_points must be odd and >= 1");
-    if (n_tail < 1 || n_tail > n_points) return fail("ojf_integrate: need 1 <= n_tail <= n_points");
-    if (est_stride < n_tail) return fail("ojf_integrate: est_stride < n_tail");
-    if (!(res > 0.0)) return fail("ojf_integrate: resolution must be > 0");
-    if ((uint64_t)X * Y * Z >= 0xffffffffull) return fail("ojf_integrate: volume has >= 2^32 voxels");
-    if ((uint64_t)h * w * n_tail * 8 >= 0xffffffffull) return fail("ojf_integrate: frame too large");
-    const int n_sem = (sem_ids != nullptr) + (sem_scores != nullptr) + (id_vol != nullptr) + (score_vol != nullptr);
-    if (n_sem != 0 && n_sem != 4)
-        return fail("ojf_integrate: sem_ids, sem_scores, id_vol, score_vol must be all set or all NULL");
-    const size_t need = ojf_integrate_workspace_bytes(X, Y, Z, h, w, n_tail, mode);
-    if (need == 0) return fail("ojf_integrate: unknown mode");
-    if (ws_bytes < need) return fail("ojf_integrate: workspace too small");
+    ojf_integrate_job j{};
+    j.depth_dev = depth_filtered; j.mask_dev = mask; j.Kinv_host = Ki; j.E_host = E; j.origin_host = origin; j.resolution = res;
+    j.est_dev = est; j.est_stride = est_stride; j.tsdf_dev = tsdf; j.weights_dev = wgt;
+    j.sem_ids_dev = sem_ids; j.sem_scores_dev = sem_scores; j.id_vol_dev = id_vol; j.score_vol_dev = score_vol;
+    j.workspace_dev = ws; j.workspace_bytes = ws_bytes;
+    if (int rc = integrate_check_dims("ojf_integrate", n_points, n_tail, X, Y, Z, h, w)) return rc;
+    IntegrateArgs a;
+    Camera cam;
+    if (int rc = integrate_fill("ojf_integrate", j, n_points, n_tail, trunc, X, Y, Z, h, w, mode, stats, a, cam)) return rc;
 
     hipStream_t st = as_stream(stream);
     char *base = static_cast<char *>(ws);
-    IntegrateArgs a;
-    a.depth = depth_filtered; a.mask = mask; a.est = est; a.tsdf = tsdf; a.wgt = wgt;
-    a.sem_ids = sem_ids; a.sem_scores = sem_scores; a.id_vol = id_vol; a.score_vol = score_vol;
-    a.counters = reinterpret_cast<unsigned int *>(base);
-    a.counters_next = nullptr; a.phased = 0;
-    a.guard = const_cast<int *>(range_guard_if_any());
-    a.head = nullptr; a.recs = nullptr; a.touched = nullptr; a.tile_new = nullptr; a.list_base = 0; a.n_tiles = 0; a.stats = stats;
-    a.X = X; a.Y = Y; a.Z = Z; a.h = h; a.w = w; a.n_points = n_points; a.n_tail = n_tail;
-    a.est_stride = est_stride; a.trunc = trunc;
-    const Camera cam = make_camera(Ki, E, origin, res);
-
     if (mode == OJF_MODE_PARITY) {
         OJF_HIP(hipMemsetAsync(a.counters, 0, kHeaderBytes, st));
         return integrate_parity(a, cam, base + kHeaderBytes, ws_bytes - kHeaderBytes, st);
@@ -692,16 +727,7 @@ OJF_API int ojf_integrate_masked(const float *depth_filtered, const uint8_t *mas
     a.phased = 1;  // (a.counters = the header)
 
     const int tiles = (int)tile_count(h, w);
-    {
-        const size_t nvox = (size_t)X * Y * Z, cap = list_capacity(h, w, n_tail);
-        char *q = base + kHeaderBytes;
-        a.head = reinterpret_cast<unsigned int *>(q); q += nvox * sizeof(unsigned int);
-        a.recs = reinterpret_cast<VoxelRec *>(q); q += cap * sizeof(VoxelRec);
-        a.touched = reinterpret_cast<unsigned int *>(q); q += cap * sizeof(unsigned int);
-        a.tile_new = reinterpret_cast<unsigned int *>(q);
-        a.n_tiles = tiles;
-        a.list_base = (unsigned int)tiles * kSlots;
-    }
+    carve_workspace(a, ws, (size_t)X * Y * Z, list_capacity(h, w, n_tail), tiles);
     if (stats) OJF_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(uint32_t), st));
     static const bool wcomb = getenv("OJF_INTEGRATE_WAVE_COMBINE") != nullptr;  // measured slower: see the kernel
     if (id_vol && wcomb) hipLaunchKernelGGL((integrate_accumulate_tiled_kernel<true, true>), dim3(tiles), dim3(kAccThreads), 0, st, a, cam);
@@ -719,52 +745,25 @@ OJF_API int ojf_integrate_many(int n, const ojf_integrate_job *jobs, int n_point
                                int w, ojf_stream_t stream)
 {
     using namespace ojf;
-    if (n < 1 || n > OJF_MAX_SCENES || !jobs) return fail("ojf_integrate_many: 1..OJF_MAX_SCENES jobs");
-    if (X <= 0 || Y <= 0 || Z <= 0 || h <= 0 || w <= 0) return fail("ojf_integrate_many: non-positive size");
-    if (n_points < 1 || (n_points & 1) == 0) return fail("ojf_integrate_many: n_points must be odd and >= 1");
-    if (n_tail < 1 || n_tail > n_points) return fail("ojf_integrate_many: need 1 <= n_tail <= n_points");
-    if ((uint64_t)X * Y * Z >= 0xffffffffull) return fail("ojf_integrate_many: volume has >= 2^32 voxels");
-    if ((uint64_t)h * w * n_tail * 8 >= 0xffffffffull) return fail("ojf_integrate_many: frame too large");
-    const size_t need = fast_workspace_bytes(X, Y, Z, h, w, n_tail);
+    const char *who = "ojf_integrate_many";
+    if (n < 1 || n > OJF_MAX_SCENES || !jobs) return refuse(who, "1..OJF_MAX_SCENES jobs");
+    if (int rc = integrate_check_dims(who, n_points, n_tail, X, Y, Z, h, w)) return rc;
     const int tiles = (int)tile_count(h, w);
-    const size_t nvox = (size_t)X * Y * Z, cap = list_capacity(h, w, n_tail);
     IntegrateMany m;
     FinalizeMany f;
     int n_with_sem = 0;
     for (int i = 0; i < n; ++i) {
         const ojf_integrate_job &j = jobs[i];
-        if (!j.depth_dev || !j.Kinv_host || !j.E_host || !j.origin_host || !j.est_dev || !j.tsdf_dev || !j.weights_dev || !j.workspace_dev)
-            return fail("ojf_integrate_many: null pointer in a job");
-        if (j.est_stride < n_tail) return fail("ojf_integrate_many: est_stride < n_tail");
-        if (!(j.resolution > 0.0)) return fail("ojf_integrate_many: resolution must be > 0");
-        const int n_sem = (j.sem_ids_dev != nullptr) + (j.sem_scores_dev != nullptr) + (j.id_vol_dev != nullptr) + (j.score_vol_dev != nullptr);
-        if (n_sem != 0 && n_sem != 4) return fail("ojf_integrate_many: sem_ids, sem_scores, id_vol, score_vol must be all set or all NULL");
-        n_with_sem += n_sem == 4;
-        if (j.workspace_bytes < need) return fail("ojf_integrate_many: workspace too small");
+        if (int rc = integrate_fill(who, j, n_points, n_tail, trunc, X, Y, Z, h, w, OJF_MODE_FAST, nullptr, m.a[i], m.cam[i])) return rc;
         for (int k = 0; k < i; ++k)
             if (jobs[k].workspace_dev == j.workspace_dev || jobs[k].tsdf_dev == j.tsdf_dev || jobs[k].weights_dev == j.weights_dev)
-                return fail("ojf_integrate_many: two jobs share a workspace or a volume (one frame per SCENE, one workspace per job)");
-        IntegrateArgs &a = m.a[i];
-        char *base = static_cast<char *>(j.workspace_dev);
-        a.depth = j.depth_dev; a.mask = j.mask_dev; a.est = j.est_dev; a.tsdf = j.tsdf_dev; a.wgt = j.weights_dev;
-        a.sem_ids = j.sem_ids_dev; a.sem_scores = j.sem_scores_dev; a.id_vol = j.id_vol_dev; a.score_vol = j.score_vol_dev;
-        a.counters = reinterpret_cast<unsigned int *>(base);
-        a.counters_next = nullptr; a.phased = 1;
-        a.guard = const_cast<int *>(range_guard_if_any());
-        char *q = base + kHeaderBytes;
-        a.head = reinterpret_cast<unsigned int *>(q); q += nvox * sizeof(unsigned int);
-        a.recs = reinterpret_cast<VoxelRec *>(q); q += cap * sizeof(VoxelRec);
-        a.touched = reinterpret_cast<unsigned int *>(q); q += cap * sizeof(unsigned int);
-        a.tile_new = reinterpret_cast<unsigned int *>(q);
-        a.n_tiles = tiles;
-        a.list_base = (unsigned int)tiles * kSlots;
-        a.stats = nullptr;
-        a.X = X; a.Y = Y; a.Z = Z; a.h = h; a.w = w; a.n_points = n_points; a.n_tail = n_tail;
-        a.est_stride = j.est_stride; a.trunc = trunc;
-        m.cam[i] = make_camera(j.Kinv_host, j.E_host, j.origin_host, j.resolution);
-        f.a[i] = a;
+                return refuse(who, "two jobs share a workspace or a volume (one frame per SCENE, one workspace per job)");
+        m.a[i].phased = 1;
+        carve_workspace(m.a[i], j.workspace_dev, (size_t)X * Y * Z, list_capacity(h, w, n_tail), tiles);
+        n_with_sem += j.id_vol_dev != nullptr;
+        f.a[i] = m.a[i];
     }
-    if (n_with_sem != 0 && n_with_sem != n) return fail("ojf_integrate_many: semantics for all jobs or for none");
+    if (n_with_sem != 0 && n_with_sem != n) return refuse(who, "semantics for all jobs or for none");
     hipStream_t st = as_stream(stream);
     if (n_with_sem) hipLaunchKernelGGL((integrate_accumulate_many_kernel<true>), dim3(tiles, n), dim3(kAccThreads), 0, st, m);
     else hipLaunchKernelGGL((integrate_accumulate_many_kernel<false>), dim3(tiles, n), dim3(kAccThreads), 0, st, m);
@@ -792,19 +791,16 @@ OJF_API int ojf_integrate_entries(const float *values, const int64_t *indices, c
                         (entries < nvox ? entries : nvox) * sizeof(unsigned int);
     if (ws_bytes < need) return fail("ojf_integrate_entries: workspace too small");
     hipStream_t st = as_stream(stream);
-    char *base = static_cast<char *>(ws);
-    IntegrateArgs a;
-    a.depth = nullptr; a.mask = nullptr; a.est = nullptr; a.tsdf = tsdf; a.wgt = wgt;
+    IntegrateArgs a{};
+    a.tsdf = tsdf; a.wgt = wgt;
     a.sem_ids = row_ids; a.sem_scores = row_scores; a.id_vol = id_vol; a.score_vol = score_vol;
-    a.counters = reinterpret_cast<unsigned int *>(base);
-    a.head = reinterpret_cast<unsigned int *>(base + kHeaderBytes);
-    a.recs = reinterpret_cast<VoxelRec *>(base + kHeaderBytes + nvox * sizeof(unsigned int));
-    a.touched = reinterpret_cast<unsigned int *>(base + kHeaderBytes + nvox * sizeof(unsigned int) + entries * sizeof(VoxelRec));
-    a.stats = stats; a.tile_new = nullptr; a.list_base = 0; a.n_tiles = 0; a.counters_next = nullptr; a.phased = 0;
+    a.counters = static_cast<unsigned int *>(ws);
+    carve_workspace(a, ws, nvox, entries, 0);
+    a.stats = stats;
     a.guard = const_cast<int *>(range_guard_if_any());
-    a.X = X; a.Y = Y; a.Z = Z; a.h = 1; a.w = 1; a.n_points = 1; a.est_stride = 0; a.trunc = 0.0f;
+    a.X = X; a.Y = Y; a.Z = Z; a.h = 1; a.w = 1; a.n_points = 1;
     a.n_tail = 1;  // finalize maps entry id -> row as (id - 1) / (n_tail * 8)
-    OJF_HIP(hipMemsetAsync(base, 0, kHeaderBytes, st));
+    OJF_HIP(hipMemsetAsync(ws, 0, kHeaderBytes, st));
     // (the header was zeroed above: both counter sets clean, phase 0 - the frame path may share this workspace)
     if (stats) OJF_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(uint32_t), st));
     if (n_rows > 0) {

@@ -37,6 +37,28 @@ def _vol16(t):
     return t
 
 
+# ---- argument checks shared by the extract / integrate front-ends (AssertionError, before any pointer is taken) ----
+def _check_f32(t, shape=None):  # a depth frame (of the call's frame shape) or est rows
+    assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and (shape is None or tuple(t.shape) == shape)
+    return t.shape
+
+
+def _check_volumes(tsdf, weights, shape=None):
+    assert _vol16(weights).shape == _vol16(tsdf).shape and (shape is None or tsdf.shape == shape)
+    return tsdf.shape
+
+
+def _check_semantics(sem_ids, sem_scores, id_vol, score_vol, n, shape):
+    assert sem_ids.dtype == torch.uint8 and sem_ids.is_contiguous() and sem_ids.numel() == n
+    assert sem_scores.dtype == torch.float32 and sem_scores.is_contiguous() and sem_scores.numel() == n
+    assert id_vol.dtype == torch.uint8 and id_vol.is_contiguous() and id_vol.shape == shape
+    assert score_vol.dtype == torch.float16 and score_vol.is_contiguous() and score_vol.shape == shape
+
+
+def _check_mask(mask, n):
+    assert mask.is_cuda and mask.dtype == torch.bool and mask.is_contiguous() and mask.numel() == n
+
+
 def extract(depth, Ki, E, origin, resolution, tsdf, weights, n_points=9, pad_value=-0.1,
             out_values=None, out_weights=None, out_stride=None, debug=False, planes=False):
     """Gather along the depth rays.  depth: cuda f32 [h,w] (or [1,h,w]).  Returns a dict with
@@ -47,11 +69,9 @@ def extract(depth, Ki, E, origin, resolution, tsdf, weights, n_points=9, pad_val
     _lib.require_gpu()
     lib = _lib.load()
     depth = depth.reshape(depth.shape[-2], depth.shape[-1])
-    assert depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()
-    h, w = depth.shape
+    h, w = _check_f32(depth)
     N = h * w
-    X, Y, Z = _vol16(tsdf).shape
-    assert _vol16(weights).shape == tsdf.shape
+    X, Y, Z = _check_volumes(tsdf, weights)
     dev = depth.device
     if out_values is None:
         out_stride = N if planes else n_points
@@ -101,11 +121,10 @@ def extract_to_net(depth, Ki, E, origin, resolution, tsdf, weights, engine, *, p
     """``extract`` + ``engine.prepare_input`` in one launch (ojf_extract_to_net): the gathered values / weights and the raw
     depth land in the fusion net's input planes; nothing else is written.  Only for engines with ``fused_input``."""
     lib = _lib.load()
-    assert depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous()
-    h, w = depth.shape
-    X, Y, Z = _vol16(tsdf).shape
-    assert _vol16(weights).shape == tsdf.shape
-    rc = lib.ojf_extract_to_net(_lib.ptr(depth), _lib.ptr(Ki), _lib.ptr(E), _lib.ptr(_origin_array(origin)), float(resolution),
+    h, w = _check_f32(depth)
+    X, Y, Z = _check_volumes(tsdf, weights)
+    origin = _origin_array(origin)  # (a local: the array must outlive the call)
+    rc = lib.ojf_extract_to_net(_lib.ptr(depth), _lib.ptr(Ki), _lib.ptr(E), _lib.ptr(origin), float(resolution),
                                 _lib.ptr(tsdf), _lib.ptr(weights), X, Y, Z, h, w, int(engine.n_points), float(pad_value),
                                 engine.handle, _lib.stream_ptr(depth.device))
     _lib.check(rc, 'ojf_extract_to_net')
@@ -122,23 +141,18 @@ def integrate(depth_filtered, Ki, E, origin, resolution, est, tsdf, weights, wor
     _lib.require_gpu()
     lib = _lib.load()
     depth_filtered = depth_filtered.reshape(depth_filtered.shape[-2], depth_filtered.shape[-1])
-    assert depth_filtered.is_cuda and depth_filtered.dtype == torch.float32 and depth_filtered.is_contiguous()
-    h, w = depth_filtered.shape
-    X, Y, Z = _vol16(tsdf).shape
-    assert _vol16(weights).shape == tsdf.shape
-    assert est.is_cuda and est.dtype == torch.float32 and est.is_contiguous()
+    h, w = _check_f32(depth_filtered)
+    X, Y, Z = _check_volumes(tsdf, weights)
+    _check_f32(est)
     if est_stride is None:
         est_stride = est.shape[-1]
     if sem_ids is not None:
-        assert sem_ids.dtype == torch.uint8 and sem_ids.is_contiguous() and sem_ids.numel() == h * w
-        assert sem_scores.dtype == torch.float32 and sem_scores.is_contiguous() and sem_scores.numel() == h * w
-        assert id_vol.dtype == torch.uint8 and id_vol.is_contiguous() and id_vol.shape == tsdf.shape
-        assert score_vol.dtype == torch.float16 and score_vol.is_contiguous() and score_vol.shape == tsdf.shape
+        _check_semantics(sem_ids, sem_scores, id_vol, score_vol, h * w, tsdf.shape)
     assert workspace.key == ((X, Y, Z), h, w, n_tail, mode), 'workspace built for another configuration'
-    origin = _origin_array(origin)
+    origin = _origin_array(origin)  # (a local: the array must outlive the call)
     if mask is not None:
         mask = mask.reshape(h, w)
-        assert mask.is_cuda and mask.dtype == torch.bool and mask.is_contiguous()
+        _check_mask(mask, h * w)
     rc = lib.ojf_integrate_masked(_lib.ptr(depth_filtered), _lib.ptr(mask), _lib.ptr(Ki), _lib.ptr(E), _lib.ptr(origin),
                            float(resolution), _lib.ptr(est), int(est_stride), n_points, n_tail,
                            float(trunc), _lib.ptr(tsdf), _lib.ptr(weights), _lib.ptr(sem_ids),
@@ -148,35 +162,62 @@ def integrate(depth_filtered, Ki, E, origin, resolution, est, tsdf, weights, wor
     _lib.check(rc, 'ojf_integrate')
 
 
+def _fill_camera(a, j):  # (the _fill_* helpers return what must stay alive until the C call is back)
+    origin = _origin_array(j['origin'])
+    a.Kinv_host, a.E_host, a.origin_host, a.resolution = _lib.ptr(j['Ki']), _lib.ptr(j['E']), _lib.ptr(origin), float(j['resolution'])
+    a.tsdf_dev, a.weights_dev = _lib.ptr(j['tsdf']), _lib.ptr(j['weights'])
+    return [origin, j['Ki'], j['E']]
+
+
+def _fill_extract_job(a, j, n_points, frame_shape, grid_shape):
+    h, w = _check_f32(j['depth'], frame_shape)
+    _check_volumes(j['tsdf'], j['weights'], grid_shape)
+    a.depth_dev = _lib.ptr(j['depth'])
+    eng = j.get('engine')
+    if eng is not None:
+        assert eng.fused_input and int(eng.n_points) == n_points
+        a.net = eng.handle
+    else:
+        ov, ow = j['out_values'], j['out_weights']
+        assert ov.is_cuda and ov.dtype == torch.float32 and ov.is_contiguous() and tuple(ov.shape) == (n_points, h * w) == tuple(ow.shape)
+        a.out_values_dev, a.out_weights_dev, a.out_stride, a.out_layout = _lib.ptr(ov), _lib.ptr(ow), h * w, 1
+    return _fill_camera(a, j)
+
+
+def _fill_integrate_job(a, j, n_tail, frame_shape, grid_shape):
+    depth, est, ws, mask = j['depth'], j['est'], j['workspace'], j.get('mask')
+    h, w = _check_f32(depth, frame_shape)
+    _check_f32(est)
+    _check_volumes(j['tsdf'], j['weights'], grid_shape)
+    assert ws.key == (grid_shape, h, w, n_tail, MODE_FAST), 'workspace built for another configuration'
+    if mask is not None:
+        _check_mask(mask, h * w)
+    a.depth_dev, a.mask_dev = _lib.ptr(depth), _lib.ptr(mask)
+    a.est_dev, a.est_stride = _lib.ptr(est), int(est.shape[-1])
+    if j.get('sem_ids') is not None:
+        ids, sc, iv, sv = j['sem_ids'], j['sem_scores'], j['id_vol'], j['score_vol']
+        _check_semantics(ids, sc, iv, sv, h * w, j['tsdf'].shape)
+        a.sem_ids_dev, a.sem_scores_dev, a.id_vol_dev, a.score_vol_dev = _lib.ptr(ids), _lib.ptr(sc), _lib.ptr(iv), _lib.ptr(sv)
+    a.workspace_dev, a.workspace_bytes = _lib.ptr(ws.buf), ws.bytes
+    return _fill_camera(a, j)
+
+
+def _job_array(struct, jobs, fill, *args):
+    n = len(jobs)
+    assert 1 <= n <= _lib.MAX_SCENES
+    frame_shape, grid_shape = tuple(jobs[0]['depth'].shape), tuple(_vol16(jobs[0]['tsdf']).shape)
+    arr = (struct * n)()
+    keep = [fill(a, j, *args, frame_shape, grid_shape) for a, j in zip(arr, jobs)]
+    return n, arr, frame_shape, grid_shape, keep
+
+
 def extract_many(jobs, n_points=9, pad_value=-0.1):
     """One frame of each of several SCENES as a single launch (ojf_extract_many).  ``jobs``: dicts with depth (cuda f32 [h, w]),
     Ki, E (camera_arrays), origin, resolution, tsdf, weights and either ``engine`` (a FusionNetEngine with ``fused_input``: the
     results land in its input planes) or ``out_values`` / ``out_weights`` sample planes [n_points, h*w].  Bit for bit what the
     separate ``extract`` / ``extract_to_net`` calls write."""
     lib = _lib.load()
-    n = len(jobs)
-    assert 1 <= n <= _lib.MAX_SCENES
-    h, w = jobs[0]['depth'].shape
-    X, Y, Z = _vol16(jobs[0]['tsdf']).shape
-    arr = (_lib.ExtractJob * n)()
-    keep = []
-    for a, j in zip(arr, jobs):
-        depth = j['depth']
-        assert depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous() and tuple(depth.shape) == (h, w)
-        assert _vol16(j['tsdf']).shape == (X, Y, Z) and _vol16(j['weights']).shape == (X, Y, Z)
-        origin = _origin_array(j['origin'])
-        keep += [origin, j['Ki'], j['E']]
-        a.depth_dev, a.Kinv_host, a.E_host, a.origin_host = _lib.ptr(depth), _lib.ptr(j['Ki']), _lib.ptr(j['E']), _lib.ptr(origin)
-        a.resolution = float(j['resolution'])
-        a.tsdf_dev, a.weights_dev = _lib.ptr(j['tsdf']), _lib.ptr(j['weights'])
-        eng = j.get('engine')
-        if eng is not None:
-            assert eng.fused_input and int(eng.n_points) == n_points
-            a.net = eng.handle
-        else:
-            ov, ow = j['out_values'], j['out_weights']
-            assert ov.is_cuda and ov.dtype == torch.float32 and ov.is_contiguous() and tuple(ov.shape) == (n_points, h * w) == tuple(ow.shape)
-            a.out_values_dev, a.out_weights_dev, a.out_stride, a.out_layout = _lib.ptr(ov), _lib.ptr(ow), h * w, 1
+    n, arr, (h, w), (X, Y, Z), keep = _job_array(_lib.ExtractJob, jobs, _fill_extract_job, n_points)
     rc = lib.ojf_extract_many(n, arr, X, Y, Z, h, w, int(n_points), float(pad_value), _lib.stream_ptr(jobs[0]['depth'].device))
     _lib.check(rc, 'ojf_extract_many')
 
@@ -187,35 +228,7 @@ def integrate_many(jobs, n_points=9, n_tail=7, trunc=0.1):
     IntegrateWorkspace of its own per job) and optionally sem_ids, sem_scores, id_vol, score_vol (all jobs or none).  The
     volumes come out bit for bit as from the separate ``integrate`` calls."""
     lib = _lib.load()
-    n = len(jobs)
-    assert 1 <= n <= _lib.MAX_SCENES
-    h, w = jobs[0]['depth'].shape
-    X, Y, Z = _vol16(jobs[0]['tsdf']).shape
-    arr = (_lib.IntegrateJob * n)()
-    keep = []
-    for a, j in zip(arr, jobs):
-        depth, est, ws = j['depth'], j['est'], j['workspace']
-        assert depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous() and tuple(depth.shape) == (h, w)
-        assert est.is_cuda and est.dtype == torch.float32 and est.is_contiguous()
-        assert _vol16(j['tsdf']).shape == (X, Y, Z) and _vol16(j['weights']).shape == (X, Y, Z)
-        assert ws.key == ((X, Y, Z), h, w, n_tail, MODE_FAST), 'workspace built for another configuration'
-        mask = j.get('mask')
-        if mask is not None:
-            assert mask.is_cuda and mask.dtype == torch.bool and mask.is_contiguous() and mask.numel() == h * w
-        origin = _origin_array(j['origin'])
-        keep += [origin, j['Ki'], j['E']]
-        a.depth_dev, a.mask_dev = _lib.ptr(depth), _lib.ptr(mask)
-        a.Kinv_host, a.E_host, a.origin_host, a.resolution = _lib.ptr(j['Ki']), _lib.ptr(j['E']), _lib.ptr(origin), float(j['resolution'])
-        a.est_dev, a.est_stride = _lib.ptr(est), int(est.shape[-1])
-        a.tsdf_dev, a.weights_dev = _lib.ptr(j['tsdf']), _lib.ptr(j['weights'])
-        if j.get('sem_ids') is not None:
-            ids, sc, iv, sv = j['sem_ids'], j['sem_scores'], j['id_vol'], j['score_vol']
-            assert ids.dtype == torch.uint8 and ids.is_contiguous() and ids.numel() == h * w
-            assert sc.dtype == torch.float32 and sc.is_contiguous() and sc.numel() == h * w
-            assert iv.dtype == torch.uint8 and iv.is_contiguous() and iv.shape == j['tsdf'].shape
-            assert sv.dtype == torch.float16 and sv.is_contiguous() and sv.shape == j['tsdf'].shape
-            a.sem_ids_dev, a.sem_scores_dev, a.id_vol_dev, a.score_vol_dev = _lib.ptr(ids), _lib.ptr(sc), _lib.ptr(iv), _lib.ptr(sv)
-        a.workspace_dev, a.workspace_bytes = _lib.ptr(ws.buf), ws.bytes
+    n, arr, (h, w), (X, Y, Z), keep = _job_array(_lib.IntegrateJob, jobs, _fill_integrate_job, n_tail)
     rc = lib.ojf_integrate_many(n, arr, int(n_points), int(n_tail), float(trunc), X, Y, Z, h, w, _lib.stream_ptr(jobs[0]['depth'].device))
     _lib.check(rc, 'ojf_integrate_many')
 

@@ -395,13 +395,6 @@ class Pipeline(torch.nn.Module):
                     best, best_ms = cand, t
         return best
 
-    def _lookahead_stream_choice(self):
-        """SETTINGS.lookahead_stream (env OJF_LOOKAHEAD_STREAM for A/B runs): 'measured' - six candidate streams timed once against
-        the real work (round 5) | 'priority' - one high-priority stream (its own hardware-queue pool) | 'probe' - the first stream that
-        passes ojf_streams_overlap."""
-        import os
-        return os.environ.get('OJF_LOOKAHEAD_STREAM') or self.config.SETTINGS.get('lookahead_stream', 'measured')
-
     def _net_side_streams(self):
         """Raw handles of the fusion net's own side streams (the second head of the two-head net runs on one): the look-ahead
         pass must not share a hardware queue with them either (measured: 775 frames/s when it does, 930-1070 when not)."""
@@ -419,7 +412,8 @@ class Pipeline(torch.nn.Module):
             return
         cur = torch.cuda.current_stream(self.device)
         pf = self.__dict__.get('_prefetch')
-        how = self._lookahead_stream_choice()
+        # 'measured' (_measured_side_stream, round 5) | 'priority' (below) | 'probe': the first stream that passes ojf_streams_overlap
+        how = self.config.SETTINGS.get('lookahead_stream', 'measured')
         if pf is None:
             net_streams = self._net_side_streams()
             if how == 'priority':
@@ -538,6 +532,33 @@ class Pipeline(torch.nn.Module):
         filtered = torch.where(mask, frame, zero)  # pipeline.py:196; one launch (a python scalar costs a fill kernel)
         return frame[0], filtered[0]
 
+    def _prepare_frame(self, batch, database, filtered=False, frames=None):
+        """What every frame step needs of its batch: (scene id, the scene's volume dict, frame, mask, Ki, E, h, w).  ``filtered``: the
+        filtered frame instead of the mask (``_frames``; fuse_training); ``frames``: that pair where the caller holds it already (an
+        announced frame).  ``database=None`` (classical mode: one volume look-up per run, fp64 poses of its own): no volume, Ki, E."""
+        self._shape = batch['image'].shape
+        frame, mask = frames or self._frames(batch, filtered)
+        scene_id = batch['frame_id'][0].split('/')[0]
+        if database is None:
+            return (scene_id, None, frame, mask, None, None) + tuple(frame.shape)
+        Ki, E = ops.camera_arrays(batch['intrinsics'][0], batch['extrinsics'][0])
+        return (scene_id, database[scene_id], frame, mask, Ki, E) + tuple(frame.shape)
+
+    @staticmethod
+    def _commit_frame(database, scene_id, volume):
+        database.state[scene_id] = True  # volumes were updated in place (pipeline.py:239-244)
+        database.scenes_est[scene_id].volume = volume['current']
+        database.fusion_weights[scene_id] = volume['weights']
+
+    def _refuse_tripped_guard(self, who):
+        """The range-guard flag is process-wide and raised by EVERY split-fp16 executor (the 2-D engine's kernels always are, whatever
+        FUSION_MODEL.arithmetic says), while the integrate calls skip as long as it is set: a host read of the mapped word in front of
+        anything a frame enqueues keeps a tripped 2-D pass from dropping frames (or handing its labels to a volume) silently when the
+        fusion net itself runs fp32, whose forward call does not poll - or when there is no net."""
+        if self.device.type == 'cuda' and _lib.load().ojf_guard_poll():
+            raise _lib.OjfError(who + ': the split-fp16 range guard is set (fp16 range exceeded in a network pass since the last '
+                                'check()): the integrate calls skip until check() has reported it')
+
     # ---- range guard of the split-fp16 net: no frame of a tripped net reaches a volume --------------
     # (include/ojf.h ojf_net_check: while the flag is set the integrate calls skip, so nothing is corrupted; what is left
     # to decide is what happens to the skipped frames.)  FUSION_MODEL.guard_policy:
@@ -608,24 +629,12 @@ class Pipeline(torch.nn.Module):
     def _fuse_frame(self, batch, database, slot=0, semantics=None, fingerprint=None):
         """One frame step on the current stream with the device state of ``slot``; ``semantics`` = (sem_ids, scores) computed
         by the caller (fuse_many) instead of here."""
-        self._shape = batch['image'].shape
-        # The range-guard flag is process-wide and raised by EVERY split-fp16 executor (the 2-D engine's kernels always are,
-        # whatever FUSION_MODEL.arithmetic says), while the integrate calls skip as long as it is set: a host read of the mapped
-        # word here, in front of anything this frame enqueues, keeps a tripped 2-D pass from dropping frames silently when the
-        # fusion net itself runs fp32 (whose forward call does not poll).
-        if self.device.type == 'cuda' and _lib.load().ojf_guard_poll():
-            raise _lib.OjfError('Pipeline.fuse: the split-fp16 range guard is set (fp16 range exceeded in a network pass since '
-                                'the last check()): the integrate calls skip until check() has reported it')
+        self._refuse_tripped_guard('Pipeline.fuse')
         profiled = slot == 0 and semantics is None
         seg0 = self._mark_segmentation() if profiled else None
         sem_ids, scores = self._frame_semantics(batch) if semantics is None else semantics
-        frame, mask = self._frames(batch, filtered=False)
-        h, w = frame.shape
-
-        scene_id = batch['frame_id'][0].split('/')[0]
-        volume = database[scene_id]
+        scene_id, volume, frame, mask, Ki, E, h, w = self._prepare_frame(batch, database)
         tsdf, weights = volume['current'], volume['weights']
-        Ki, E = ops.camera_arrays(batch['intrinsics'][0], batch['extrinsics'][0])
 
         sl = self._get_slot(h, w, self.device, slot, fingerprint)
         eng = sl.engine
@@ -657,11 +666,7 @@ class Pipeline(torch.nn.Module):
                       id_vol=volume['ids_est'] if sem else None, score_vol=volume['scores'] if sem else None,
                       mode=self._integrate_mode, mask=mask)  # filtered frame of pipeline.py:196 formed in the kernels
         mark()
-
-        database.state[scene_id] = True  # volumes were updated in place (pipeline.py:239-244)
-        database.scenes_est[scene_id].volume = tsdf
-        database.fusion_weights[scene_id] = weights
-        return
+        self._commit_frame(database, scene_id, volume)
 
     # ---- FUSION_MODEL.name 'tsdf': classical projective TSDF averaging, no network (projective.py) -------------------------
     def _fuse_classical(self, batches, sems, database):
@@ -674,11 +679,7 @@ class Pipeline(torch.nn.Module):
         fm = self.config.FUSION_MODEL
         kw = dict(truncation=fm.get('truncation', None) or self.config.DATA.init_value,
                   max_weight=fm.get('max_weight', 128.0), carve=bool(fm.get('carve', False)))
-        # the 2-D engine runs split-fp16 with ``semantic_strategy: predict``: labels of a pass that tripped the range guard
-        # must not reach a volume (the learned frame step refuses in the same place)
-        if self.device.type == 'cuda' and _lib.load().ojf_guard_poll():
-            raise _lib.OjfError('Pipeline.fuse: the split-fp16 range guard is set (fp16 range exceeded in a network pass since '
-                                'the last check())')
+        self._refuse_tripped_guard('Pipeline.fuse')  # (the labels of a 2-D pass that tripped the guard must not reach a volume)
         sem = bool(self.config.DATA.semantics)
         run, run_key = [], None
 
@@ -687,24 +688,20 @@ class Pipeline(torch.nn.Module):
                 return
             scene_id = run_key[0]
             volume = database[scene_id]
-            tsdf, weights = volume['current'], volume['weights']
             projective.integrate_depth(
-                tsdf, weights, origin=volume['origin'], resolution=float(volume['resolution']),
+                volume['current'], volume['weights'], origin=volume['origin'], resolution=float(volume['resolution']),
                 depth=torch.stack([r[0] for r in run]), mask=torch.stack([r[1] for r in run]),
                 intrinsics=torch.stack([r[2] for r in run]), extrinsics=torch.stack([r[3] for r in run]),
                 ids=volume['ids_est'] if sem else None, scores=volume['scores'] if sem else None,
                 labels=torch.stack([r[4] for r in run]) if sem else None,
                 label_scores=torch.stack([r[5] for r in run]) if sem else None, **kw)
-            database.state[scene_id] = True  # volumes were updated in place (pipeline.py:239-244)
-            database.scenes_est[scene_id].volume = tsdf
-            database.fusion_weights[scene_id] = weights
+            self._commit_frame(database, scene_id, volume)
             del run[:]
 
         for b, s in zip(batches, sems):
-            self._shape = b['image'].shape
             sem_ids, scores = self._frame_semantics(b) if s is None else s
-            frame, mask = self._frames(b, filtered=False)
-            key = (b['frame_id'][0].split('/')[0], tuple(frame.shape))
+            scene_id, _, frame, mask = self._prepare_frame(b, None)[:4]
+            key = (scene_id, tuple(frame.shape))
             if key != run_key or len(run) == _lib.PROJECTIVE_MAX_VIEWS:
                 flush()
                 run_key = key
@@ -749,11 +746,10 @@ class Pipeline(torch.nn.Module):
             streams.append(self._side_stream([main] + streams))  # (a stream that runs beside the caller's and the other slots')
         enqueued = 0
         try:
-            import os
             # 'auto' (default): the joint launches for two scenes, per-slot launches from three on - measured on one box (round 6,
             # profiles/r06_many_scene_launches.txt): joint 2246 against 2220 frames/s at S = 2, 2650 against 2747 at S = 4 (the two joins -
             # every net waits for the gather of ALL scenes, the scatter for ALL nets - cost more than the shared launches save)
-            how = os.environ.get('OJF_FUSE_MANY') or self.config.SETTINGS.get('fuse_many_launches', 'auto')  # (env: A/B runs)
+            how = self.config.SETTINGS.get('fuse_many_launches', 'auto')
             if how == 'auto':
                 how = 'joint' if len(batches) <= 2 else 'slots'
             if self._integrate_mode == MODE_FAST and how == 'joint':
@@ -800,29 +796,23 @@ class Pipeline(torch.nn.Module):
         blocks wait, which S launches on S streams do not.  Per scene the same blocks run the same code as in ``fuse``: the
         volumes come out bit for bit the same.  Raises (the poll below, a net's forward call) before ANY integrate launch of
         the call has been enqueued: none of the call's frames is among the skipped ones."""
-        if _lib.load().ojf_guard_poll():
-            raise _lib.OjfError('Pipeline.fuse_many: the split-fp16 range guard is set (fp16 range exceeded in a network pass since '
-                                'the last check()): the integrate calls skip until check() has reported it')
+        self._refuse_tripped_guard('Pipeline.fuse_many')
         P, n_tail = self.n_points, self.config.FUSION_MODEL.n_tail_points
         use_sem, sem = self.config.FUSION_MODEL.use_semantics, bool(self.config.DATA.semantics)
         prep = []
         for i, (b, (sem_ids, scores)) in enumerate(zip(batches, sems)):
-            self._shape = b['image'].shape
-            frame, mask = self._frames(b, filtered=False)
-            h, w = frame.shape
-            scene_id = b['frame_id'][0].split('/')[0]
-            volume = database[scene_id]
-            Ki, E = ops.camera_arrays(b['intrinsics'][0], b['extrinsics'][0])
+            scene_id, volume, frame, mask, Ki, E, h, w = self._prepare_frame(b, database)
             sl = self._get_slot(h, w, self.device, i, fp)
             ws = self._get_workspace(volume['current'].shape, h, w, self.device, i)
-            prep.append(dict(scene=scene_id, frame=frame, mask=mask, volume=volume, Ki=Ki, E=E, slot=sl, ws=ws, sem_ids=sem_ids, scores=scores))
+            job = dict(depth=frame, Ki=Ki, E=E, origin=volume['origin'], resolution=volume['resolution'], tsdf=volume['current'], weights=volume['weights'])
+            if sem:
+                job.update(sem_ids=sem_ids, sem_scores=scores, id_vol=volume['ids_est'], score_vol=volume['scores'])  # (the gather ignores them)
+            prep.append(dict(scene=scene_id, frame=frame, volume=volume, slot=sl, sem_ids=sem_ids, job=job, scatter=dict(job, mask=mask, est=sl.est, workspace=ws)))
         if len({(p['frame'].shape, p['volume']['current'].shape) for p in prep}) != 1:
             raise ValueError('Pipeline.fuse_many: one frame size and one grid size per call')
         fused = prep[0]['slot'].engine.fused_input
         self._mark(first=True)  # (profile: four events per CALL - gather of all scenes | nets | scatter of all scenes)
-        ops.extract_many([dict(depth=p['frame'], Ki=p['Ki'], E=p['E'], origin=p['volume']['origin'], resolution=p['volume']['resolution'],
-                               tsdf=p['volume']['current'], weights=p['volume']['weights'],
-                               **(dict(engine=p['slot'].engine) if fused else dict(out_values=p['slot'].fv, out_weights=p['slot'].fw)))
+        ops.extract_many([dict(p['job'], **(dict(engine=p['slot'].engine) if fused else dict(out_values=p['slot'].fv, out_weights=p['slot'].fw)))
                           for p in prep], n_points=P)
         self._mark()
         for i, p in enumerate(prep):
@@ -836,18 +826,11 @@ class Pipeline(torch.nn.Module):
         for st in streams[:len(prep) - 1]:
             main.wait_stream(st)
         self._mark()
-        ops.integrate_many([dict(depth=p['frame'], mask=p['mask'], Ki=p['Ki'], E=p['E'], origin=p['volume']['origin'],
-                                 resolution=p['volume']['resolution'], est=p['slot'].est, tsdf=p['volume']['current'],
-                                 weights=p['volume']['weights'], workspace=p['ws'],
-                                 **(dict(sem_ids=p['sem_ids'], sem_scores=p['scores'], id_vol=p['volume']['ids_est'],
-                                         score_vol=p['volume']['scores']) if sem else {}))
-                            for p in prep], n_points=P, n_tail=n_tail, trunc=self.config.DATA.init_value)
+        ops.integrate_many([p['scatter'] for p in prep], n_points=P, n_tail=n_tail, trunc=self.config.DATA.init_value)
         self._mark()
         self._frames_fused += len(prep) - 1  # (the first mark counted one)
         for p in prep:
-            database.state[p['scene']] = True  # volumes were updated in place (pipeline.py:239-244)
-            database.scenes_est[p['scene']].volume = p['volume']['current']
-            database.fusion_weights[p['scene']] = p['volume']['weights']
+            self._commit_frame(database, p['scene'], p['volume'])
 
     def _training_forward(self, inputs):
         """The net forward of pipeline.py:322 with a graph for ``loss.backward()``: on the libojf training kernels
@@ -942,21 +925,15 @@ class Pipeline(torch.nn.Module):
             raise RuntimeError('Pipeline.fuse_training: FUSION_MODEL.name "tsdf" is classical TSDF averaging - there is no '
                                'network to train (use "v2" or "v3")')
         self.device = torch.device(device)
-        self._shape = batch['image'].shape
         sem_ids, scores = self._frame_semantics(batch)
         ann = self.__dict__.pop('_announced', None)
         if ann is not None and ann[0] is batch and ann[1].device == self.device:
-            _, frame, filtered, valid_mask, count = ann  # (enqueued a frame ago: the count is on the host by now)
+            frames, valid_mask, count = ann[1:3], ann[3], ann[4]  # (enqueued a frame ago: the count is on the host by now)
         else:
-            frame, filtered = self._frames(batch)
-            valid_mask = count = None
-        h, w = frame.shape
+            frames = valid_mask = count = None
+        scene_id, volume, frame, filtered, Ki, E, h, w = self._prepare_frame(batch, database, filtered=True, frames=frames)
         n, P = h * w, self.n_points
-
-        scene_id = batch['frame_id'][0].split('/')[0]
-        volume = database[scene_id]
         tsdf, weights = volume['current'], volume['weights']
-        Ki, E = ops.camera_arrays(batch['intrinsics'][0], batch['extrinsics'][0])
 
         # The shapes [1, Nv, P] of the masked outputs (pipeline.py:125-131) need the number of valid rays on the host: the one
         # device -> host read of the frame step.  The count is REQUESTED here (one reduction + an asynchronous copy into
@@ -998,7 +975,5 @@ class Pipeline(torch.nn.Module):
         ops.integrate(filtered, Ki, E, volume['origin'], volume['resolution'], est_rows, tsdf, weights, ws,
                       n_points=P, n_tail=self.config.FUSION_MODEL.n_tail_points, trunc=init,
                       mode=self._integrate_mode)  # test=False: no semantic update (pipeline.py:357)
-        database.state[scene_id] = True
-        database.scenes_est[scene_id].volume = tsdf
-        database.fusion_weights[scene_id] = weights
+        self._commit_frame(database, scene_id, volume)
         return output

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .ops import _origin_array
 
 
 def _cameras(intrinsics, extrinsics, n):
@@ -89,9 +90,7 @@ def integrate_depth(tsdf, weights, *, origin, resolution, depth, intrinsics, ext
     mask = _images(mask, 'mask', torch.uint8, n, h, w, dev)
     labels = _images(labels, 'labels', torch.uint8, n, h, w, dev)
     label_scores = _images(label_scores, 'label_scores', torch.float32, n, h, w, dev)
-    if torch.is_tensor(origin):
-        origin = origin.detach().cpu().numpy()
-    org = np.ascontiguousarray(np.asarray(origin, dtype=np.float64).reshape(3))
+    org = _origin_array(origin)
     X, Y, Z = tsdf.shape
     stream = _lib.stream_ptr(dev)
     step = _lib.PROJECTIVE_MAX_VIEWS

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ops import camera_arrays
+from .ops import camera_arrays, _origin_array
 
 
 def _poses(intrinsics, extrinsics):
@@ -59,9 +59,7 @@ def render_views(tsdf, weights=None, ids=None, *, origin, resolution, intrinsics
     if n > _lib.RENDER_MAX_VIEWS:
         raise ValueError('render_views: at most {} views per call'.format(_lib.RENDER_MAX_VIEWS))
     h, w = int(shape[0]), int(shape[1])
-    if torch.is_tensor(origin):
-        origin = origin.detach().cpu().numpy()
-    org = np.ascontiguousarray(np.asarray(origin, dtype=np.float64).reshape(3))
+    org = _origin_array(origin)
     dev = tsdf.device
     depth = torch.empty((n, h, w), dtype=torch.float32, device=dev)
     nrm = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev) if normals else None

@@ -568,3 +568,36 @@ def test_extract_bit_exact_for_a_rolled_camera(cuda, h, w, grid):
         planes = ops.extract(_t(fi['depth'], cuda), fi['Ki'], E, st.origin, st.resolution, g_tsdf, g_wgt, planes=True)
         assert n_mismatch(planes['fusion_values'].t().contiguous().cpu().numpy(), ref['fusion_values']) == 0
         assert n_mismatch(planes['fusion_weights'].t().contiguous().cpu().numpy(), ref['fusion_weights']) == 0
+
+
+@pytest.mark.parametrize('rolled_first', [False, True])
+def test_many_scene_extract_with_mixed_tile_orientations(cuda, rolled_first):
+    """ojf_extract_many launches ONE tile shape for all its scenes - the first job's camera picks it - so every job's tile count has to
+    follow the launch's shape, not the job's own camera.  Two scenes of 13 x 20 pixels (5 column tiles, 8 row tiles: a job counted by
+    its own camera would leave pixels out, or run tiles that do not exist), one filmed upright and one with the camera rolled by 90
+    degrees (test_extract_bit_exact_for_a_rolled_camera), in both job orders: the sample planes bit for bit those of the separate
+    ops.extract calls, each of which picks its own shape."""
+    h, w, grid, P = 13, 20, 32, 9
+    roll = np.array([[0, -1, 0], [1, 0, 0], [0, 0, 1]], dtype=np.float32)
+    rng = np.random.default_rng(23)
+    jobs, refs = [], []
+    for s, rolled in enumerate([rolled_first, not rolled_first]):
+        st = make_stream(h, w, grid, scene='room_%d' % s, seed=1911 + 17 * s)
+        fi = frame_inputs(st, 1)
+        E = fi['E'].reshape(3, 4).copy()
+        if rolled:
+            E[:, :3] = E[:, :3] @ roll
+        assert (abs(E[2, 0]) > abs(E[2, 1])) == rolled  # rolled: the camera's x axis carries the volume's z (row tiles)
+        E = np.ascontiguousarray(E.reshape(12))
+        tsdf = _t(rng.uniform(-0.1, 0.1, (grid,) * 3).astype(np.float16), cuda)
+        wgt = _t(rng.uniform(0, 6, (grid,) * 3).astype(np.float16), cuda)
+        depth = _t(fi['depth'], cuda)
+        refs.append(ops.extract(depth, fi['Ki'], E, st.origin, st.resolution, tsdf, wgt, n_points=P, planes=True))
+        jobs.append(dict(depth=depth, Ki=fi['Ki'], E=E, origin=st.origin, resolution=st.resolution, tsdf=tsdf, weights=wgt,
+                         out_values=torch.full((P, h * w), np.nan, device=cuda), out_weights=torch.full((P, h * w), np.nan, device=cuda)))
+    ops.extract_many(jobs, n_points=P)
+    for s, (job, ref) in enumerate(zip(jobs, refs)):
+        assert torch.equal(ref['fusion_values'].view(torch.int32), job['out_values'].view(torch.int32)), s
+        assert torch.equal(ref['fusion_weights'].view(torch.int32), job['out_weights'].view(torch.int32)), s
+    assert not torch.equal(jobs[0]['out_values'], jobs[1]['out_values'])  # (the scenes differ)
+    assert float((jobs[0]['out_weights'] > 0).sum()) > 100
