@@ -165,6 +165,12 @@ int ojf_net_side_streams(ojf_net *net, ojf_stream_t stream, ojf_stream_t out[3])
  * stream.  Returns the number of entries (<= max_entries) or < 0.  For bench.py's per-kernel table; not a hot path. */
 int ojf_net_profile(ojf_net *net, float *est_dev, int est_stride, ojf_stream_t stream, char *names, int names_cap,
                     float *micros, int max_entries);
+/* The launches a forward pass of a net of this shape consists of, without a device: the kernel names ('\n'-separated, in
+ * host enqueue order - the format and order ojf_net_profile reports) into `names`; returns their count or < 0 (bad
+ * arguments, a buffer too small for all names).  The pass is planned from the shape alone when a net is created; this
+ * entry point runs the same planner with the reference's dilation rates (1, 3, 9, 27).  growth = growth_factor - 1. */
+int ojf_net_plan(int version, int n_points, int growth, int use_semantics, int h, int w, int arithmetic, char *names,
+                 int names_cap);
 /* Arithmetic used by nets created (and ojf_conv2d calls made) AFTER this call: OJF_ARITH_F32 | OJF_ARITH_F16X3.
  * A net keeps the arithmetic it was created with.  Not thread-safe against concurrent ojf_net_create. */
 int ojf_net_set_arithmetic(int arithmetic);

@@ -43,8 +43,11 @@
 //     instead of in_chs (114/228);
 //   * the global-average branch is constant over the image: it is reduced to a per-frame bias of
 //     the final 1x1 convolution (two tiny kernels on a side stream), removing its 114 input columns from that GEMM.
-// Launches of one forward pass (geometry-only v3, the default topology, frame width a multiple of 8; forward_launches /
-// run_vortex): dense_chain_kernel (all dense Blocks of the head), then per VortexPooling {pool pyramid (+ the global-average
+// Launches of one forward pass: decided ONCE, from the net's shape alone, by plan_forward in ojf_net_create (a ForwardPlan: the
+// dense stage, one VortexStep per VortexPooling, the head); forward_launches / run_vortex / run_dense only execute it, and
+// ojf_net_plan lists its launches without a device.  The shape predicates the planner uses (entry_tiles, fused_tail_form,
+// chain_dense_form, ...) also tell the packing code which forms to pack; a new variant starts there ("the forward plan" below).
+// Geometry-only v3, the default topology, frame width a multiple of 8: dense_chain_kernel (all dense Blocks of the head), then per VortexPooling {pool pyramid (+ the global-average
 // fold), two grouped launches of the four branches' dilated 3x3, fused tail}: the first VortexPooling's entry GEMM is a launch
 // of its own (entry1x1_kernel), its tail runs the second one's entry GEMM, and the last tail runs the 11-layer prediction
 // head: 10 launches on one stream.  The two-head (semantic) net runs its second head beside the first on a second stream, each
@@ -1637,19 +1640,32 @@ static int guard_take(int *skipped, bool clear)
 // Launch log of a forward pass: every launch site calls mark_launch(name, stream) right after its launch.  It counts the
 // launches (ojf_net_launch_count) and, in profile mode (ojf_net_profile), records a fence-free timing event behind the
 // launch, so that the time between consecutive marks of one stream is that kernel's duration as the stream sees it.
+// The names are one table: the launch sites pass an index, the forward plan (plan_launches / ojf_net_plan) lists the same indices.
+enum Launch {
+    L_DENSE_CHAIN, L_DENSE_PAIR, L_CONV_F16X3, L_CONV_F16X3_GROUPED, L_CONV_MFMA, L_COLSUM, L_GAVE_BIAS, L_ENTRY1X1, L_POOL_PYRAMID,
+    L_VORTEX_BRANCH, L_SUBCONV, L_TAIL, L_TAIL_ENTRY, L_TAIL_HALF_ENTRY, L_TAIL_HEAD, L_COUNT
+};
+static const char *const kLaunchNames[L_COUNT] = {
+    "dense_chain_kernel", "dense_pair_kernel", "conv_f16x3_kernel", "conv_f16x3_kernel (grouped)", "conv_mfma_kernel", "colsum_kernel",
+    "gave_bias_kernel", "entry1x1_kernel", "pool_pyramid_kernel", "vortex_branch_kernel", "subconv_kernel", "vortex_tail_kernel",
+    "vortex_tail_kernel (+ next entry GEMM)", "vortex_tail_kernel (+ half of the next entry GEMM)", "vortex_tail_kernel (+ prediction head)",
+};
+// a generic convolution launch of n (<= 4) problems (launch_conv_args)
+static inline Launch conv_launch(int arith, int n) { return arith != OJF_ARITH_F16X3 ? L_CONV_MFMA : n > 1 ? L_CONV_F16X3_GROUPED : L_CONV_F16X3; }
+
 struct LaunchMark { const char *name; hipStream_t st; hipEvent_t ev; };
 static thread_local int g_launches = 0;
 static thread_local bool g_profile = false;
 static thread_local std::vector<LaunchMark> g_marks;
 
-static inline void mark_launch(const char *name, hipStream_t st)
+static inline void mark_launch(Launch what, hipStream_t st)
 {
     ++g_launches;
     if (!g_profile) return;
     hipEvent_t e = nullptr;
     if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) return;
     (void)hipEventRecord(e, st);
-    g_marks.push_back(LaunchMark{name, st, e});
+    g_marks.push_back(LaunchMark{kLaunchNames[what], st, e});
 }
 
 // Fork / join events between streams of the same device: no timing and no system-scope fence - nothing here is read by
@@ -1884,7 +1900,7 @@ static int launch_pair_t(PairArgs &a, hipStream_t st)
     a.tiles_x = (a.w + TW - 1) / TW;
     const int tiles = a.tiles_x * ((a.h + TH - 1) / TH);
     hipLaunchKernelGGL((dense_pair_kernel<TW, TH>), dim3(tiles), dim3(G::THREADS), G::LDS_BYTES, st, a);
-    mark_launch("dense_pair_kernel", st);
+    mark_launch(L_DENSE_PAIR, st);
     return check_hip(hipGetLastError(), "dense_pair_kernel launch");
 }
 
@@ -2017,7 +2033,7 @@ static int launch_chain_t(ChainDenseArgs &a, hipStream_t st)
     // one block per CU (160 KB of LDS); the blocks draw (Block, tile) items until none is left
     const int grid = cus > 0 && cus < tiles ? cus : tiles;
     hipLaunchKernelGGL((dense_chain_kernel<TW, TH, WAVES>), dim3(grid), dim3(G::THREADS), G::LDS_BYTES, st, a);
-    mark_launch("dense_chain_kernel", st);
+    mark_launch(L_DENSE_CHAIN, st);
     return check_hip(hipGetLastError(), "dense_chain_kernel launch");
 }
 
@@ -2198,7 +2214,7 @@ static int launch_subconv(const PackedBranches &pb, const float *const *in, floa
     a.h = h; a.w_img = w; a.npix = h * w;
     a.ovf = overflow_flag();
     hipLaunchKernelGGL(subconv_kernel, dim3(pb.n_sub), dim3(256), kSubLdsBytes, st, a);
-    mark_launch("subconv_kernel", st);
+    mark_launch(L_SUBCONV, st);
     return check_hip(hipGetLastError(), "subconv_kernel launch");
 }
 
@@ -2220,7 +2236,7 @@ static int launch_branches(const PackedBranches &pb, const float *const *in, flo
     const int cus = device_cu_count();
     const int grid = cus > 0 && cus < pb.n_items ? cus : pb.n_items;
     hipLaunchKernelGGL(vortex_branch_kernel, dim3(grid), dim3(64 * kBranchWaves), kBranchLdsBytes, st, a);
-    mark_launch("vortex_branch_kernel", st);
+    mark_launch(L_VORTEX_BRANCH, st);
     return check_hip(hipGetLastError(), "vortex_branch_kernel launch");
 }
 
@@ -2317,7 +2333,7 @@ static int launch_conv_args(const ConvArgs *args, int n, int nt, hipStream_t st,
     }
 #undef OJF_LAUNCH32
 #undef OJF_LAUNCH16
-    mark_launch(arith == OJF_ARITH_F16X3 ? (n > 1 ? "conv_f16x3_kernel (grouped)" : "conv_f16x3_kernel") : "conv_mfma_kernel", st);
+    mark_launch(conv_launch(arith, n), st);
     return check_hip(hipGetLastError(), "conv kernel launch");
 }
 
@@ -2418,14 +2434,195 @@ static void append_chain_bias(std::vector<float> &dst, int arith, int nt_out, in
         for (int o = 0; o < nt_out * 16; ++o) dst[bb + (size_t)nt_out * 16 + o] = 1.0f / rs[o];
 }
 
+// ---- the forward plan -------------------------------------------------------------------------------------------------
+// Which launches a forward pass consists of depends on the net's shape alone.  plan_forward decides it once, in ojf_net_create
+// (and in ojf_net_plan, which needs no device); the packing code asks the same predicates which forms to pack, and
+// forward_launches / run_vortex only execute the plan.  A new variant starts here: a predicate for the shapes it serves, a value
+// of the step's enum, its case in plan_forward and plan_launches, its packing and its case in the executor.
+struct NetShape {
+    int version, P, gf, sem, h, w, arith;
+    bool same_dil[3];  // VortexPooling k: the two 3x3 of every branch share a dilation (the reference's do: 1, 3, 9, 27)
+    int c, cs, heads, pool_in, os, npix;  // derived (net_shape): channels of a Block and their padded slot, (gf+1)*c and its slot
+    int c_in_phys(int k) const { return k < 2 ? (gf + 1) * cs : heads * os; }  // input planes of VortexPooling k (2 = the last one)
+};
+
+// nullptr, or why the shape is refused (text after "<entry point>: ")
+static const char *net_shape(NetShape &s, int version, int n_points, int growth, int use_semantics, int h, int w, int arith)
+{
+    if (version != 2 && version != 3) return "version must be 2 or 3";
+    if (n_points < 1 || growth < 1 || h <= 0 || w <= 0) return "bad sizes";
+    s.version = version; s.P = n_points; s.gf = growth; s.sem = use_semantics ? 1 : 0; s.h = h; s.w = w; s.arith = arith;
+    s.same_dil[0] = s.same_dil[1] = s.same_dil[2] = true;
+    s.c = 2 * n_points + 1 + (version == 2 ? s.sem : 0);
+    s.cs = round_up(s.c, 4);
+    s.heads = (version == 3 && s.sem) ? 2 : 1;
+    s.pool_in = s.c * (growth + 1);
+    s.os = round_up(s.pool_in, 4);
+    s.npix = h * w;
+    if (s.heads * s.os > 256 || (growth + 1) * s.cs > 256) return "topology too wide";
+    return nullptr;
+}
+
+// The three test-only switches, read once per process (the tests that set them start child processes)
+struct NetSwitches { bool no_dense_chain, branch_kernel, subconv; };
+static const NetSwitches &net_switches()
+{
+    auto on = [](const char *name) { const char *v = getenv(name); return v != nullptr && atoi(v) != 0; };
+    static const NetSwitches sw = {getenv("OJF_NO_DENSE_CHAIN") != nullptr, on("OJF_BRANCH_KERNEL"), on("OJF_SUBCONV")};
+    return sw;
+}
+
+// Shape predicates: each form of the packing code exists exactly where its predicate holds.
+// input tiles of a VortexPooling's entry GEMM as one chain layer (entry1x1_kernel / the previous tail): 8, 16 (the two-head net's
+// last VortexPooling, 228 = 2 x 114 input channels), or 0 = no such form (generic stacked convolution)
+static int entry_tiles(int c_in_phys, int cs) { return c_in_phys <= 256 && 4 * cs <= 80 ? (c_in_phys <= 128 ? 8 : 16) : 0; }
+// ... split into one 8-tile layer per head, run by the two heads' tails
+static bool half_entry_form(int c_in_phys, int cs, int os) { return entry_tiles(c_in_phys, cs) == 16 && c_in_phys == 2 * os; }
+// fused tail (vortex_tail_kernel): 2 branch tiles, 8 output tiles
+static bool fused_tail_form(int cs, int os) { return (cs + 15) / 16 == 2 && (os + 15) / 16 == 8; }
+// chain flow of VortexPooling k: entry and tail both have their chain-layer forms
+static bool chain_flow_form(const NetShape &s, int k) { return entry_tiles(s.c_in_phys(k), s.cs) != 0 && fused_tail_form(s.cs, s.os); }
+// dense Blocks as dense_pair_kernel launches / as one dense_chain_kernel launch
+static bool pair_form(const NetShape &s) { return s.arith == OJF_ARITH_F16X3 && s.cs <= 24; }
+static bool chain_form(const NetShape &s) { return pair_form(s) && s.cs == 4 * kChainNG && s.gf <= kChainMaxLayers; }
+// both 3x3 of the four branches packed for vortex_branch_kernel / subconv_kernel (finish_branches; its item tables are never
+// empty for a frame of at least one pixel)
+static bool branch_form(const NetShape &s, int k)
+{
+    return s.arith == OJF_ARITH_F16X3 && s.cs == 4 * kChainNG && entry_tiles(s.c_in_phys(k), s.cs) != 0 && s.same_dil[k];
+}
+// growth channels of the prediction head as chain layers inside the last tail (19 / 20), 0 = layer by layer
+static int chain_kind_of(const NetShape &s) { return s.P == 9 && s.gf == 5 && (s.c == 19 || s.c == 20) ? s.c : 0; }
+// One dense_chain_kernel launch per head instead of gf dense_pair_kernel launches: the dense-growth buffers then hold split
+// planes, which only the chain-flow entry kernel reads.
+static bool chain_dense_form(const NetShape &s)
+{
+    if (s.arith != OJF_ARITH_F16X3 || net_switches().no_dense_chain) return false;
+    //  frames the chain kernel is not the right tool for fall back to one dense_pair_kernel launch per Block:
+    //  * more tiles than the flag array holds (frames beyond ~2.6 Mpixel used to fail in ojf_net_forward);
+    //  * w % 8 != 0: a 128-byte line of a plane is 8 pixels, so a line then straddles two image rows - pixels of tiles
+    //    whose flags a reader never checked - and only the slot of the Block just finished is read with sc1 loads: an
+    //    early reader could pull a not-yet-written pixel of an OLDER slot into its XCD's L2 and a later item read it stale.
+    const int big = ((s.w + 19) / 20) * ((s.h + 15) / 16);
+    const int tiles = big >= 200 ? big : ((s.w + 11) / 12) * ((s.h + 7) / 8);
+    if (tiles > kChainSyncInts - kChainFlags0 || (s.w % 8) != 0) return false;
+    return chain_form(s) && chain_flow_form(s, 0);  // (every head's VortexPooling has the shape of the first)
+}
+
+enum DenseKind { DENSE_CHAIN, DENSE_PAIRS, DENSE_CONVS };
+enum EntryKind { ENTRY_KERNEL, ENTRY_BY_PREV_TAIL, ENTRY_GENERIC };
+enum BranchKind { BRANCH_GROUPED, BRANCH_GROUPED_SIDE0, BRANCH_KERNEL, BRANCH_SUBCONV };
+enum TailKind { TAIL_UNFUSED, TAIL_ALONE, TAIL_ENTRY, TAIL_HALF_ENTRY, TAIL_HEAD };
+
+struct VortexStep {
+    int vortex, set;  // net->vortex[vortex] on net->sc[set]; steps 0 / 1 are heads 0 / 1 behind their dense Blocks, 2 is the last one
+    // Chain flow (no side stream, no events): entry GEMM + column sums in one chain-layer launch (or inside the previous
+    // tail), the global-average fold as one extra block of the pyramid launch, all four branches in the grouped launches.
+    // General flow (topologies whose entry or tail has no chain-layer form): generic convolutions, the global-average branch
+    // on the side stream.
+    bool chain_flow;
+    EntryKind entry;  // ENTRY_KERNEL: entry1x1_kernel with entry_ntin input tiles; ENTRY_GENERIC: + the two global-average kernels
+    int entry_ntin;
+    bool in_split;    // the input holds split planes (dense_chain_kernel's result)
+    // split planes between the branch-entry producers (entry GEMM: branch 0; pool pyramid: branches 1-3), the branches' first
+    // 3x3 and their second 3x3 (whose result the tail reads as plain fp32 planes)
+    bool split;
+    BranchKind branches;  // BRANCH_GROUPED_SIDE0: branch 0 needs no pooling, its 3x3 pair follows the global-average kernels on the side stream
+    TailKind tail;    // TAIL_UNFUSED: four 1x1 + the final convolution through Scratch::CAT; the others: vortex_tail_kernel and what rides along
+    int half;         // TAIL_HALF_ENTRY: which half of the last entry GEMM (channel sums into net->colsum3 at half * os)
+    bool z2;          // the pyramid adds the other head's partial entry planes (sc[1].Z) and forms branch 0 (Q0, bias0); channel sums: net->colsum3
+};
+
+struct ForwardPlan {
+    DenseKind dense;
+    int n_steps;         // 2, or 3 = two heads: step 0 (head 1, on its own stream), step 1 (head 0), step 2
+    VortexStep step[3];  // in host enqueue order
+    bool head_layers;    // the prediction head runs layer by layer afterwards (PA / PB)
+    int chain_kind;
+};
+
+// nullptr, or the refusal (ojf_net_create fails with it)
+static const char *plan_forward(const NetShape &s, ForwardPlan *plan)
+{
+    const NetSwitches &sw = net_switches();
+    const bool h16 = s.arith == OJF_ARITH_F16X3, two = s.heads == 2, fused = fused_tail_form(s.cs, s.os);
+    ForwardPlan &p = *plan;
+    p.dense = chain_dense_form(s) ? DENSE_CHAIN : pair_form(s) ? DENSE_PAIRS : DENSE_CONVS;
+    p.chain_kind = chain_kind_of(s);
+    p.n_steps = two ? 3 : 2;
+    // two heads: each head's tail runs ITS half of the last entry GEMM (the concatenation YY is then never written)
+    const bool halves = two && half_entry_form(s.c_in_phys(2), s.cs, s.os) && chain_flow_form(s, 0);
+    bool entry_done = false;
+    for (int i = 0; i < p.n_steps; ++i) {
+        VortexStep &v = p.step[i];
+        const bool last = i == p.n_steps - 1;
+        v.vortex = last ? 2 : two ? 1 - i : 0;
+        v.set = v.vortex == 1 ? 1 : 0;
+        v.chain_flow = chain_flow_form(s, v.vortex);
+        v.entry_ntin = entry_tiles(s.c_in_phys(v.vortex), s.cs);
+        v.entry = !v.chain_flow ? ENTRY_GENERIC : (last && entry_done) ? ENTRY_BY_PREV_TAIL : ENTRY_KERNEL;
+        v.in_split = !last && p.dense == DENSE_CHAIN;
+        v.split = h16 && v.chain_flow;
+        v.z2 = last && halves;
+        v.half = -1;
+        if (v.split && branch_form(s, v.vortex) && sw.branch_kernel) v.branches = BRANCH_KERNEL;
+        else if (v.split && branch_form(s, v.vortex) && sw.subconv) v.branches = BRANCH_SUBCONV;
+        else v.branches = v.chain_flow || s.npix < 32768 ? BRANCH_GROUPED : BRANCH_GROUPED_SIDE0;  // (small frames: the stream hand-over costs more than it hides)
+        if (!fused) v.tail = TAIL_UNFUSED;
+        else if (last) v.tail = p.chain_kind ? TAIL_HEAD : TAIL_ALONE;
+        else if (halves) { v.tail = TAIL_HALF_ENTRY; v.half = v.vortex; }
+        // single head: this tail runs the last VortexPooling's entry GEMM on its register-resident result
+        else if (!two && v.chain_flow && chain_flow_form(s, 2) && s.c_in_phys(2) == s.os) v.tail = TAIL_ENTRY;
+        else v.tail = TAIL_ALONE;
+        if (v.tail == TAIL_ENTRY || v.tail == TAIL_HALF_ENTRY) entry_done = true;
+        if (v.in_split && (!v.chain_flow || v.entry != ENTRY_KERNEL)) return "internal error (split-plane input without the entry kernel)";
+    }
+    p.head_layers = p.step[p.n_steps - 1].tail != TAIL_HEAD;
+    // (a net with a chain-form head - chain_kind - has fused tails, and the last one runs the head)
+    if (p.chain_kind && p.head_layers) return "internal error (the last tail did not run the prediction head)";
+    return nullptr;
+}
+
+// The launches of a planned pass in host enqueue order (what ojf_net_profile reports for it)
+static std::vector<Launch> plan_launches(const NetShape &s, const ForwardPlan &p)
+{
+    std::vector<Launch> out;
+    const Launch conv1 = conv_launch(s.arith, 1);
+    for (int i = 0; i < p.n_steps; ++i) {
+        const VortexStep &v = p.step[i];
+        if (v.vortex < 2) {
+            if (p.dense == DENSE_CHAIN) out.push_back(L_DENSE_CHAIN);
+            else if (p.dense == DENSE_PAIRS) out.insert(out.end(), s.gf, L_DENSE_PAIR);
+            else out.insert(out.end(), 2 * s.gf, conv1);
+        }
+        if (v.entry == ENTRY_GENERIC) out.insert(out.end(), {L_COLSUM, L_GAVE_BIAS, conv1});
+        else if (v.entry == ENTRY_KERNEL) out.push_back(L_ENTRY1X1);
+        out.push_back(L_POOL_PYRAMID);
+        switch (v.branches) {
+        case BRANCH_KERNEL: out.push_back(L_VORTEX_BRANCH); break;
+        case BRANCH_SUBCONV: out.insert(out.end(), 2, L_SUBCONV); break;
+        case BRANCH_GROUPED: out.insert(out.end(), 2, conv_launch(s.arith, 4)); break;
+        case BRANCH_GROUPED_SIDE0: out.insert(out.end(), 2, conv1); out.insert(out.end(), 2, conv_launch(s.arith, 3)); break;
+        }
+        switch (v.tail) {
+        case TAIL_UNFUSED: out.insert(out.end(), 5, conv1); break;
+        case TAIL_ALONE: out.push_back(L_TAIL); break;
+        case TAIL_ENTRY: out.push_back(L_TAIL_ENTRY); break;
+        case TAIL_HALF_ENTRY: out.push_back(L_TAIL_HALF_ENTRY); break;
+        case TAIL_HEAD: out.push_back(L_TAIL_HEAD); break;
+        }
+    }
+    if (p.head_layers) out.insert(out.end(), 2 * (s.gf - 1) + 3, conv1);
+    return out;
+}
+
 struct Vortex {
     int c_in = 0, c_in_phys = 0;
     PackedConv stacked, b3a[4], b3b[4], b1[4], fin;
     float *pool_bias[4] = {nullptr, nullptr, nullptr, nullptr};
     float *Wg = nullptr, *bg = nullptr, *Wfg = nullptr, *bf = nullptr, *bias_final = nullptr;
     float *tail_w = nullptr, *tail_b1 = nullptr, *tail_rinv = nullptr;  // fused tail (closing 1x1s + final conv), when supported
-    float *entry_w = nullptr, *entry_b = nullptr;  // the stacked entry GEMM as one chain layer (8 or 16 input tiles -> 5), when supported
-    int entry_ntin = 8;
+    float *entry_w = nullptr, *entry_b = nullptr;  // the stacked entry GEMM as one chain layer (entry_tiles() input tiles -> 5), when supported
     // two-head nets (round 6): the last VortexPooling's entry GEMM over the concatenation of the two heads' outputs splits into
     // one 8-tile -> 5 layer per head (columns [hd * os, (hd + 1) * os) of the stacked weights, no bias, no activation): each head's
     // tail runs ITS half on its register-resident result; the pool pyramid adds the halves (and forms branch 0)
@@ -2438,18 +2635,18 @@ struct Vortex {
 struct ojf_net {
     int version, P, c, cs, gf, sem, heads, h, w, npix;
     int arith;  // OJF_ARITH_* captured at creation
+    ojf::NetShape shape;    // the same, as the planner and the packing predicates read it
+    ojf::ForwardPlan plan;  // the launches of a forward pass, decided in ojf_net_create (plan_forward)
     int pool_in, os;  // (gf+1)*c and its padded slot
     float scale;
     int64_t macs_per_pixel;
     int last_launches = 0;  // kernel launches of the most recent ojf_net_forward (all streams)
     std::vector<ojf::PackedConv> dense[2];  // block0 / block2 (or v2's block): 2*gf convs each
     std::vector<ojf::PackedPair> pairs[2];  // split-fp16: the same layers packed for dense_pair_kernel (one launch per Block)
-    ojf::PackedChain chains[2];             // ... and for dense_chain_kernel (all Blocks of a head in one launch)
-    bool chain_dense = false;               // X[] hold split planes, run_dense = one dense_chain_kernel launch per head
+    ojf::PackedChain chains[2];             // ... and for dense_chain_kernel (all Blocks of a head in one launch; X[] then hold split planes)
     ojf::Vortex vortex[3];                  // v3: vortex0, vortex2, vortex3 ; v2: vortex, -, vortex_final
     std::vector<ojf::PackedConv> pred;
-    float *chain_w = nullptr, *chain_b = nullptr;  // fused prediction head (when the topology is supported)
-    int chain_kind = 0;                             // 0 = unfused, 19 / 20 = growth channels of the fused kernel
+    float *chain_w = nullptr, *chain_b = nullptr;  // fused prediction head (plan.chain_kind: 19 / 20 growth channels)
     // activation planes (C4 layout), sizes in channels
     float *X[2] = {nullptr, nullptr};  // dense-growth buffers, (gf+1)*cs
     // Scratch of one head's dense block + VortexPooling.  Two sets: with two heads (v3 + semantics) the second head runs
@@ -2460,7 +2657,7 @@ struct ojf_net {
         float *Q0 = nullptr;  // two-head nets: branch 0 of the last VortexPooling (the pyramid's level-0 pass)
         float *partial = nullptr;
         ojf::ColSums *colsum = nullptr;  // chain flow: fixed-point channel sums of the entry layer's input (zero between frames)
-        float *CAT = nullptr;  // 4*os, unfused tail only (allocated at first use)
+        float *CAT = nullptr;  // 4*os, unfused tail only (allocated when the plan has one on this set)
         hipStream_t side = nullptr;
         hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_entry = nullptr;
     } sc[2];
@@ -2475,7 +2672,7 @@ struct ojf_net {
     ojf::ColSums *colsum3 = nullptr;
     float *YY = nullptr;               // heads*os (vortex0 | vortex2 outputs)
     float *Y3 = nullptr;               // os
-    float *PA = nullptr, *PB = nullptr;  // pred ping-pong, os each
+    float *PA = nullptr, *PB = nullptr;  // pred ping-pong, os each (allocated when the plan runs the head layer by layer)
     // Optional (OJF_NET_GRAPH=1): the launch sequence of a forward pass captured once per output buffer and
     // replayed with hipGraphLaunch.  Measured on ROCm 7.2 / MI355X: host enqueue time of a forward 160 -> 87 us,
     // but the GPU runs the graph 3-8 % SLOWER than the plain launches (0.555 vs 0.538 ms at 320x240,
@@ -2500,8 +2697,8 @@ static int alloc_planes(float **p, size_t npix, int ch)
     OJF_HIP(hipMalloc(reinterpret_cast<void **>(&raw), (npix * ch + kPrefix) * sizeof(float)));
     OJF_HIP(hipMemset(raw, 0, (npix * ch + kPrefix) * sizeof(float)));
     // The fill runs on the null stream; the second head's stream and the side streams are hipStreamNonBlocking and do NOT
-    // order against it.  A buffer allocated at its first use inside a forward pass (ensure_planes) could be written by a
-    // convolution on such a stream and zeroed afterwards (round 5: one wrong output in ~8 suite runs of the generic two-head
+    // order against it: a convolution on such a stream could write the buffer before the fill zeroes it (round 5, when the
+    // fall-back buffers were still allocated inside a forward pass: one wrong output in ~8 suite runs of the generic two-head
     // topology, never in isolation).  The fill is therefore complete before anybody learns the pointer.
     OJF_HIP(hipStreamSynchronize(nullptr));
     *p = raw + kPrefix;
@@ -2513,15 +2710,10 @@ static void free_planes(float *p)
     if (p) (void)hipFree(p - kPrefix);
 }
 
-// buffers only the unfused fall-back paths need are allocated at their first use (synchronous, outside any capture)
-static int ensure_planes(float **p, size_t npix, int ch)
+static int build_vortex(ojf_net *net, int k, const ojf_conv_layer *L, int c_in, const std::vector<int> &in_map)
 {
-    return *p ? 0 : alloc_planes(p, npix, ch);
-}
-
-static int build_vortex(ojf_net *net, Vortex &v, const ojf_conv_layer *L, int c_in, const std::vector<int> &in_map,
-                        int c_in_phys)
-{
+    Vortex &v = net->vortex[k];
+    const int c_in_phys = net->shape.c_in_phys(k);
     // L[0] gave 1x1 | L[1+4b .. 4+4b] branch b: 1x1, 3x3, 3x3, 1x1 | L[17] final 1x1 (5*out -> out)
     const int c = net->c, cs = net->cs, out = net->pool_in, os = net->os;
     v.c_in = c_in;
@@ -2545,17 +2737,16 @@ static int build_vortex(ojf_net *net, Vortex &v, const ojf_conv_layer *L, int c_
             }
         }
         if (finish(b, v.stacked, net->arith)) return -2;
-        if (c_in_phys <= 256 && 4 * cs <= 80) {
+        if (const int ntin = entry_tiles(c_in_phys, cs)) {
             // chain-layer form (entry1x1_kernel / the previous tail): 8 input tiles -> 5; the two-head net's last VortexPooling
             // (228 = 2 x 114 input channels): 16 -> 5 (round 6: it ran the generic convolution + two side-stream kernels + three events)
-            v.entry_ntin = c_in_phys <= 128 ? 8 : 16;
             auto we = [&](int oc, int k) { return oc < 4 * cs && k < c_in_phys ? b.W[(size_t)oc * c_in_phys + k] : 0.0f; };
             const std::vector<float> re = chain_row_scales(net->arith, 5, c_in_phys, we);
             std::vector<float> ew, eb;
-            pack_chain_layer(ew, net->arith, 5, v.entry_ntin, re, we);
+            pack_chain_layer(ew, net->arith, 5, ntin, re, we);
             append_chain_bias(eb, net->arith, 5, 4 * cs, b.B.data(), re);
             if (upload(ew, &v.entry_w) || upload(eb, &v.entry_b)) return -2;
-            if (v.entry_ntin == 16 && c_in_phys == 2 * net->os) {
+            if (half_entry_form(c_in_phys, cs, os)) {
                 const std::vector<float> zero_bias(4 * cs, 0.0f);
                 for (int hd = 0; hd < 2; ++hd) {
                     auto wh = [&](int oc, int k) { return oc < 4 * cs && k < net->os ? b.W[(size_t)oc * c_in_phys + hd * net->os + k] : 0.0f; };
@@ -2585,9 +2776,7 @@ static int build_vortex(ojf_net *net, Vortex &v, const ojf_conv_layer *L, int c_
         bas.push_back(ba);
         bbs.push_back(bb);
     }
-    if (net->arith == OJF_ARITH_F16X3 && cs == 4 * kChainNG && v.entry_w && bas[0].dil == bbs[0].dil && bas[1].dil == bbs[1].dil &&
-        bas[2].dil == bbs[2].dil && bas[3].dil == bbs[3].dil && finish_branches(bas, bbs, net->h, net->w, v.branches))
-        return -2;
+    if (branch_form(net->shape, k) && finish_branches(bas, bbs, net->h, net->w, v.branches)) return -2;
     {   // final 1x1 over [gave | b0 | b1 | b2 | b3]; the gave columns become a per-frame bias
         const ojf_conv_layer &lf = L[17];
         ConvBuilder b(4 * os, os, 1, 1);
@@ -2604,7 +2793,7 @@ static int build_vortex(ojf_net *net, Vortex &v, const ojf_conv_layer *L, int c_
         std::vector<float> zero((size_t)v.fin.n_ot * 16, 0.0f);
         if (upload(zero, &v.bias_final)) return -2;
     }
-    if ((cs + 15) / 16 == 2 && (os + 15) / 16 == 8) {  // fused tail: [W1_b | Wf_b] fragments per branch
+    if (fused_tail_form(cs, os)) {  // fused tail: [W1_b | Wf_b] fragments per branch
         const int NV = 2, NO = 8;
         std::vector<float> tw, tb;
         const ojf_conv_layer &lf = L[17];
@@ -2659,78 +2848,56 @@ static GaveArgs gave_args(const ojf_net *net, const Vortex &v, const float *part
 
 static int chain_blocks(const ojf_net *net) { return ((net->npix + 15) / 16 + ojf::kChainWaves - 1) / ojf::kChainWaves; }  // blocks of the MT = 1 chain kernels
 
-// What a VortexPooling's launches share with its neighbours (all optional: see the call sites in forward_launches)
-struct VortexLinks {
-    const ChainArgs *head = nullptr;  // the prediction head: the last VortexPooling's tail runs it where it can ...
-    bool *head_done = nullptr;        // ... and reports it here
-    bool entry_done = false;          // the previous tail already left this one's entry planes (sc.Z) and column sums (sc.colsum)
-    const Vortex *next = nullptr;     // when given (and supported), this tail runs the NEXT VortexPooling's entry GEMM on its
-    bool *next_done = nullptr;        //     register-resident result instead of writing `out`; *next_done reports it
-    bool in_split = false;            // `in` holds split planes (dense_chain_kernel's result)
-    // two-head nets: this head's tail runs half `half` of `next`'s entry GEMM (partial sums into sc.Z, the channel sums of its
-    // result into next_colsum at channel half * os)
-    int half = -1;
-    ColSums *next_colsum = nullptr;
-    // the OTHER head's partial entry planes: this VortexPooling's pyramid adds them to sc.Z and forms branch 0 (entry_done must be set)
-    const float *z2 = nullptr;
-};
+// one launch of a chain-layer kernel template in the net's arithmetic: KERNEL<arithmetic, further template arguments>(ARGS)
+#define OJF_LAUNCH_BY_ARITH(KERNEL, ARGS, ...)                                                                              \
+    do {                                                                                                                     \
+        if (h16) hipLaunchKernelGGL((KERNEL<OJF_ARITH_F16X3, __VA_ARGS__>), grid, block, 0, st, ARGS);                      \
+        else hipLaunchKernelGGL((KERNEL<OJF_ARITH_F32, __VA_ARGS__>), grid, block, 0, st, ARGS);                            \
+    } while (0)
 
-// in: planes, window starting at group in_g0 (c_in_phys/4 groups); out: planes at group out_g0.
-static int run_vortex(ojf_net *net, Vortex &v, const float *in, int in_g0, float *out, int out_g0, hipStream_t st,
-                      ojf_net::Scratch &sc, const VortexLinks &l = VortexLinks())
+// One VortexPooling as its step of the plan says.  Steps 0 / 1 read their head's dense-growth buffer and write (where the tail
+// carries nothing along) their slot of YY; the last one reads YY and writes Y3.  `head`: the prediction head's arguments, for
+// the tail that runs it.
+static int run_vortex(ojf_net *net, const VortexStep &s, hipStream_t st, const ChainArgs &head)
 {
     const int h = net->h, w = net->w, c4 = net->cs / 4, o4 = net->os / 4;
     const bool h16 = net->arith == OJF_ARITH_F16X3;
-    // ---- what runs --------------------------------------------------------------------------------------------------
-    // Chain flow (no side stream, no events): entry GEMM + column sums in one chain-layer launch (or inside the previous
-    // tail), the global-average fold as one extra block of the pyramid launch, all four branches in the grouped launches.
-    // General flow (topologies whose entry or tail has no chain-layer form): generic convolutions, the global-average branch
-    // on the side stream.
-    const bool chain_flow = v.entry_w && v.tail_w;
-    // split planes between the branch-entry producers (entry GEMM: branch 0; pool pyramid: branches 1-3), the branches' first
-    // 3x3 and their second 3x3 (whose result the tail reads as plain fp32 planes)
-    const bool split = h16 && chain_flow;
-    // fused tail (the four branch-exit 1x1 and the final 1x1 in one launch), and what rides along with it
-    const bool fused = v.tail_w != nullptr;
-    enum { TAIL_ALONE, TAIL_HEAD, TAIL_HALF_ENTRY, TAIL_ENTRY } tail = TAIL_ALONE;
-    if (l.head && net->chain_kind) tail = TAIL_HEAD;  // last VortexPooling: the prediction head rides along
-    else if (chain_flow && l.next && l.half >= 0 && l.half < 2 && l.next->entry_wh[l.half] && l.next->tail_w && l.next_colsum) tail = TAIL_HALF_ENTRY;
-    else if (chain_flow && l.next && l.next->entry_w && l.next->tail_w && l.next->c_in_phys == net->os) tail = TAIL_ENTRY;
-    if (l.in_split && (!chain_flow || l.entry_done)) return fail("run_vortex: internal error (split-plane input without the entry kernel)");
-    if (!chain_flow && l.entry_done) return fail("run_vortex: internal error (entry planes without the chain flow)");
-    if (l.z2 && (!l.entry_done || !chain_flow || !sc.Q0 || !v.bias0)) return fail("run_vortex: internal error (partial entry sums without the chain flow)");
+    const bool last = s.vortex == 2;
+    const Vortex &v = net->vortex[s.vortex], &next = net->vortex[2];
+    ojf_net::Scratch &sc = net->sc[s.set];
+    const float *in = last ? net->YY : net->X[s.vortex];
+    float *out = last ? net->Y3 : net->YY;
+    const int in_g0 = 0, out_g0 = last ? 0 : s.vortex * o4;
+    const dim3 grid(chain_blocks(net)), block(ojf::kChainThreads);
 
     // ---- entry: the four branch-entry 1x1 as one GEMM into sc.Z, the global-average branch's column sums ----------------
-    if (!chain_flow) {
+    if (s.entry == ENTRY_GENERIC) {
         // global-average branch -> bias of the final conv, on the side stream (fork here, join before the tail)
         OJF_HIP(hipEventRecord(sc.ev_fork, st));
         OJF_HIP(hipStreamWaitEvent(sc.side, sc.ev_fork, 0));
         hipLaunchKernelGGL(colsum_kernel, dim3(kSumBlocks, v.c_in_phys / 4), dim3(256), 0, sc.side, planes(in), in_g0,
                            net->npix, sc.partial);
-        mark_launch("colsum_kernel", sc.side);
+        mark_launch(L_COLSUM, sc.side);
         OJF_HIP(hipGetLastError());
         hipLaunchKernelGGL(gave_bias_kernel, dim3(1), dim3(256), 0, sc.side, gave_args(net, v, sc.partial, kSumBlocks, 256));
-        mark_launch("gave_bias_kernel", sc.side);
+        mark_launch(L_GAVE_BIAS, sc.side);
         OJF_HIP(hipGetLastError());
         // branch entries: one GEMM, branch 0 gets bias + ReLU in the epilogue
         if (launch_conv(v.stacked, in, in_g0, sc.Z, 0, nullptr, OJF_ACT_RELU, net->cs, 1.0f, h, w, st)) return -2;
         OJF_HIP(hipEventRecord(sc.ev_entry, st));
-    } else if (!l.entry_done) {
+    } else if (s.entry == ENTRY_KERNEL) {
         ChainArgs ea;
         ea.in = planes(in); ea.w = planes(v.entry_w); ea.bias = v.entry_b; ea.out_rows = nullptr;
         ea.in_g0 = in_g0; ea.c4_in = v.c_in_phys / 4; ea.npix = net->npix; ea.rows_stride = 0; ea.rows_n = 0; ea.scale = 1.0f;
         ea.ovf = h16 ? overflow_flag() : nullptr;
         ea.out_planes = planes(sc.Z); ea.out_g0 = 0; ea.og_store = 4 * c4; ea.act_n = net->cs; ea.colsum = sc.colsum;
-        ea.split_groups = split ? c4 : 0;
-        ea.in_split = l.in_split ? 1 : 0;
-        const dim3 grid(chain_blocks(net)), block(ojf::kChainThreads);
+        ea.split_groups = s.split ? c4 : 0;
+        ea.in_split = s.in_split ? 1 : 0;
         // (two pixel tiles per wave - half the blocks, half the weight stream per pixel - measured 22.2 against 23.7 us and changes the
         // rounding of the channel sums: not kept, profiles/r06_fusion_net_experiments.txt)
-        if (v.entry_ntin == 16 && h16) hipLaunchKernelGGL((entry1x1_kernel<OJF_ARITH_F16X3, 1, 16, 5>), grid, block, 0, st, ea);
-        else if (v.entry_ntin == 16) hipLaunchKernelGGL((entry1x1_kernel<OJF_ARITH_F32, 1, 16, 5>), grid, block, 0, st, ea);
-        else if (h16) hipLaunchKernelGGL((entry1x1_kernel<OJF_ARITH_F16X3, 1, 8, 5>), grid, block, 0, st, ea);
-        else hipLaunchKernelGGL((entry1x1_kernel<OJF_ARITH_F32, 1, 8, 5>), grid, block, 0, st, ea);
-        mark_launch("entry1x1_kernel", st);
+        if (s.entry_ntin == 16) OJF_LAUNCH_BY_ARITH(entry1x1_kernel, ea, 1, 16, 5);
+        else OJF_LAUNCH_BY_ARITH(entry1x1_kernel, ea, 1, 8, 5);
+        mark_launch(L_ENTRY1X1, st);
         OJF_HIP(hipGetLastError());
     }
 
@@ -2742,23 +2909,21 @@ static int run_vortex(ojf_net *net, Vortex &v, const float *in, int in_g0, float
         for (int b = 0; b < 3; ++b) pa.bias[b] = v.pool_bias[b + 1];
         pa.h = h; pa.w = w; pa.c4 = c4;
         pa.tiles = ((w + kPoolTW - 1) / kPoolTW) * ((h + kPoolTH - 1) / kPoolTH);
-        pa.gave = gave_args(net, v, nullptr, 0, 0, (l.z2 && net->colsum3) ? net->colsum3 : sc.colsum);
-        pa.fold_gave = chain_flow ? 1 : 0;
-        pa.split_out = split ? 1 : 0;
-        if (l.z2) { pa.z2 = planes(l.z2); pa.q0 = planes(sc.Q0); pa.bias0 = v.bias0; }
+        pa.gave = gave_args(net, v, nullptr, 0, 0, s.z2 ? net->colsum3 : sc.colsum);
+        pa.fold_gave = s.chain_flow ? 1 : 0;
+        pa.split_out = s.split ? 1 : 0;
+        if (s.z2) { pa.z2 = planes(net->sc[1].Z); pa.q0 = planes(sc.Q0); pa.bias0 = v.bias0; }
         // grid.x: the tiles (+ the global-average block of the chain flow) rounded up to a multiple of 8 (XCD bands)
-        hipLaunchKernelGGL(pool_pyramid_kernel, dim3(round_up(pa.tiles + (chain_flow ? 1 : 0), 8), (l.z2 ? 4 : 3) * c4), dim3(256), 0, st, pa);
-        mark_launch("pool_pyramid_kernel", st);
+        hipLaunchKernelGGL(pool_pyramid_kernel, dim3(round_up(pa.tiles + (s.chain_flow ? 1 : 0), 8), (s.z2 ? 4 : 3) * c4), dim3(256), 0, st, pa);
+        mark_launch(L_POOL_PYRAMID, st);
         OJF_HIP(hipGetLastError());
     }
-    const float *bin[4] = {l.z2 ? sc.Q0 : sc.Z, sc.Q1, sc.Q2, sc.Q3};
-    // (measured equal to the two grouped launches, not faster - 82 against 79-80 us per frame, profiles/r04_pair_experiments.txt -
-    // so it is opt-in: OJF_BRANCH_KERNEL=1)
-    static const bool branch_kernel = getenv("OJF_BRANCH_KERNEL") != nullptr && atoi(getenv("OJF_BRANCH_KERNEL")) != 0;
-    static const bool subconv = getenv("OJF_SUBCONV") != nullptr && atoi(getenv("OJF_SUBCONV")) != 0;
-    if (split && v.branches.n_items && branch_kernel) {  // both 3x3 of all four branches: one launch (ojf_net_branch.h)
+    const float *bin[4] = {s.z2 ? sc.Q0 : sc.Z, sc.Q1, sc.Q2, sc.Q3};
+    if (s.branches == BRANCH_KERNEL) {  // both 3x3 of all four branches: one launch (ojf_net_branch.h)
+        // (measured equal to the two grouped launches, not faster - 82 against 79-80 us per frame, profiles/r04_pair_experiments.txt -
+        // so it is opt-in: OJF_BRANCH_KERNEL=1)
         if (launch_branches(v.branches, bin, sc.V, h, w, st)) return -2;
-    } else if (split && v.branches.n_sub && subconv) {  // LDS-staged sub-image blocks: one launch per 3x3 (ojf_net_branch.h)
+    } else if (s.branches == BRANCH_SUBCONV) {  // LDS-staged sub-image blocks: one launch per 3x3 (ojf_net_branch.h)
         float *u[4], *vv[4];
         const float *uc[4];
         for (int br = 0; br < 4; ++br) {
@@ -2773,12 +2938,12 @@ static int run_vortex(ojf_net *net, Vortex &v, const float *in, int in_g0, float
         for (int br = 0; br < 4; ++br) {
             fill_conv_args(ga[br], v.b3a[br], bin[br], 0, sc.U, br * c4, nullptr, OJF_ACT_RELU, net->cs, 1.0f, h, w);
             fill_conv_args(gb[br], v.b3b[br], sc.U, br * c4, sc.V, br * c4, nullptr, OJF_ACT_RELU, net->cs, 1.0f, h, w);
-            ga[br].in_split = ga[br].out_split = gb[br].in_split = split ? 1 : 0;
+            ga[br].in_split = ga[br].out_split = gb[br].in_split = s.split ? 1 : 0;
         }
-        if (chain_flow || net->npix < 32768) {  // (small frames: the stream hand-over costs more than it hides)
+        if (s.branches == BRANCH_GROUPED) {
             if (launch_conv_args(ga, 4, v.b3a[0].n_ot, st, net->arith)) return -2;
             if (launch_conv_args(gb, 4, v.b3b[0].n_ot, st, net->arith)) return -2;
-        } else {  // general flow: branch 0 needs no pooling, its 3x3 pair follows the global-average kernels on the side stream
+        } else {  // BRANCH_GROUPED_SIDE0
             OJF_HIP(hipStreamWaitEvent(sc.side, sc.ev_entry, 0));
             if (launch_conv_args(ga, 1, v.b3a[0].n_ot, sc.side, net->arith)) return -2;
             if (launch_conv_args(gb, 1, v.b3b[0].n_ot, sc.side, net->arith)) return -2;
@@ -2788,17 +2953,17 @@ static int run_vortex(ojf_net *net, Vortex &v, const float *in, int in_g0, float
     }
 
     // ---- tail: the four branch-exit 1x1, the final 1x1 over their concatenation (+ the global-average bias) ---------------
-    if (!chain_flow) {
+    if (!s.chain_flow) {
         OJF_HIP(hipEventRecord(sc.ev_join, sc.side));
         OJF_HIP(hipStreamWaitEvent(st, sc.ev_join, 0));  // bias of the final conv is ready
     }
-    if (!fused) {
-        if (ensure_planes(&sc.CAT, (size_t)net->npix, 4 * net->os)) return -2;
+    if (s.tail == TAIL_UNFUSED) {
         for (int br = 0; br < 4; ++br)
             if (launch_conv(v.b1[br], sc.V, br * c4, sc.CAT, br * o4, nullptr, OJF_ACT_RELU, net->os, 1.0f, h, w, st))
                 return -2;
         return launch_conv(v.fin, sc.CAT, 0, out, out_g0, v.bias_final, OJF_ACT_NONE, 0, 1.0f, h, w, st);
     }
+    // fused tail (the four branch-exit 1x1 and the final 1x1 in one launch), and what rides along with it
     TailArgs ta;
     for (int br = 0; br < 4; ++br) ta.v[br] = planes(sc.V) + (size_t)br * c4 * net->npix;
     ta.w = planes(v.tail_w); ta.b1 = v.tail_b1; ta.bias_final = v.bias_final; ta.rinv_final = v.tail_rinv;
@@ -2807,63 +2972,59 @@ static int run_vortex(ojf_net *net, Vortex &v, const float *in, int in_g0, float
     ta.chain_w = nullptr; ta.chain_b = nullptr; ta.out_rows = nullptr; ta.rows_stride = 0; ta.rows_n = 0; ta.scale = 1.0f;
     ta.entry_w = nullptr; ta.entry_b = nullptr; ta.entry_out = nullptr; ta.entry_og = 0; ta.entry_act_n = 0; ta.colsum = nullptr; ta.entry_split = 0;
     // MT = 1: two pixel tiles per wave (324 VGPRs, one wave per SIMD) measured slower (0.624 vs 0.609 ms net)
-    const dim3 grid(chain_blocks(net)), block(ojf::kChainThreads);
-    switch (tail) {
-    case TAIL_HEAD:
-        ta.chain_w = l.head->w; ta.chain_b = l.head->bias; ta.out_rows = l.head->out_rows;
-        ta.rows_stride = l.head->rows_stride; ta.rows_n = l.head->rows_n; ta.scale = l.head->scale;
-        if (net->chain_kind == 19 && h16) hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F16X3, 1, 2, 8, 19>), grid, block, 0, st, ta);
-        else if (net->chain_kind == 19) hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F32, 1, 2, 8, 19>), grid, block, 0, st, ta);
-        else if (h16) hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F16X3, 1, 2, 8, 20>), grid, block, 0, st, ta);
-        else hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F32, 1, 2, 8, 20>), grid, block, 0, st, ta);
-        mark_launch("vortex_tail_kernel (+ prediction head)", st);
-        if (l.head_done) *l.head_done = true;
+    Launch name = L_TAIL;
+    switch (s.tail) {
+    case TAIL_HEAD:  // last VortexPooling: the prediction head rides along
+        name = L_TAIL_HEAD;
+        ta.chain_w = head.w; ta.chain_b = head.bias; ta.out_rows = head.out_rows;
+        ta.rows_stride = head.rows_stride; ta.rows_n = head.rows_n; ta.scale = head.scale;
+        if (net->plan.chain_kind == 19) OJF_LAUNCH_BY_ARITH(vortex_tail_kernel, ta, 1, 2, 8, 19);
+        else OJF_LAUNCH_BY_ARITH(vortex_tail_kernel, ta, 1, 2, 8, 20);
         break;
     case TAIL_HALF_ENTRY:
-        // two-head net: this head's HALF of the next VortexPooling's entry GEMM rides along (partial sums: no bias, no activation,
-        // plain planes); `out` is never written
-        ta.entry_w = planes(l.next->entry_wh[l.half]); ta.entry_b = l.next->entry_bh[l.half]; ta.entry_out = planes(sc.Z);
-        ta.entry_og = 4 * c4; ta.entry_act_n = 0; ta.colsum = l.next_colsum; ta.colsum_off = l.half * net->os;
+        name = L_TAIL_HALF_ENTRY;
+        // two-head net: this head's HALF of the last VortexPooling's entry GEMM rides along (partial sums: no bias, no activation,
+        // plain planes), the channel sums of its result go to colsum3 at channel half * os; `out` is never written
+        ta.entry_w = planes(next.entry_wh[s.half]); ta.entry_b = next.entry_bh[s.half]; ta.entry_out = planes(sc.Z);
+        ta.entry_og = 4 * c4; ta.entry_act_n = 0; ta.colsum = net->colsum3; ta.colsum_off = s.half * net->os;
         ta.entry_split = 0;
-        if (h16) hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F16X3, 1, 2, 8, kTailEntry>), grid, block, 0, st, ta);
-        else hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F32, 1, 2, 8, kTailEntry>), grid, block, 0, st, ta);
-        mark_launch("vortex_tail_kernel (+ half of the next entry GEMM)", st);
-        if (l.next_done) *l.next_done = true;
+        OJF_LAUNCH_BY_ARITH(vortex_tail_kernel, ta, 1, 2, 8, kTailEntry);
         break;
     case TAIL_ENTRY:
-        // this VortexPooling feeds the next one: its entry GEMM and column sums ride along, `out` is never written
-        ta.entry_w = planes(l.next->entry_w); ta.entry_b = l.next->entry_b; ta.entry_out = planes(sc.Z);
+        name = L_TAIL_ENTRY;
+        // this VortexPooling feeds the last one: its entry GEMM and column sums ride along, `out` is never written
+        ta.entry_w = planes(next.entry_w); ta.entry_b = next.entry_b; ta.entry_out = planes(sc.Z);
         ta.entry_og = 4 * c4; ta.entry_act_n = net->cs; ta.colsum = sc.colsum;
-        ta.entry_split = h16 ? c4 : 0;  // (the next VortexPooling runs the chain flow: same rule as its `split`)
-        if (h16) hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F16X3, 1, 2, 8, kTailEntry>), grid, block, 0, st, ta);
-        else hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F32, 1, 2, 8, kTailEntry>), grid, block, 0, st, ta);
-        mark_launch("vortex_tail_kernel (+ next entry GEMM)", st);
-        if (l.next_done) *l.next_done = true;
+        ta.entry_split = h16 ? c4 : 0;  // (the last VortexPooling runs the chain flow: same rule as its `split`)
+        OJF_LAUNCH_BY_ARITH(vortex_tail_kernel, ta, 1, 2, 8, kTailEntry);
         break;
-    case TAIL_ALONE:
-        if (h16) hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F16X3, 1, 2, 8>), grid, block, 0, st, ta);
-        else hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F32, 1, 2, 8>), grid, block, 0, st, ta);
-        mark_launch("vortex_tail_kernel", st);
+    default:  // TAIL_ALONE
+        OJF_LAUNCH_BY_ARITH(vortex_tail_kernel, ta, 1, 2, 8);
         break;
     }
+    mark_launch(name, st);
     return check_hip(hipGetLastError(), "vortex_tail_kernel launch");
 }
+#undef OJF_LAUNCH_BY_ARITH
 
 static int run_dense(ojf_net *net, int head, hipStream_t st)
 {
     const int c4 = net->cs / 4;
     float *T = net->sc[head].T;
-    if (net->chain_dense) return launch_chain(net->chains[head], net->X[head], net->h, net->w, st);  // one launch (ojf_net_chain.h)
-    if ((int)net->pairs[head].size() == net->gf) {  // one fused launch per Block (ojf_net_pair.h)
+    switch (net->plan.dense) {
+    case DENSE_CHAIN: return launch_chain(net->chains[head], net->X[head], net->h, net->w, st);  // one launch (ojf_net_chain.h)
+    case DENSE_PAIRS:  // one fused launch per Block (ojf_net_pair.h)
         for (int i = 0; i < net->gf; ++i)
             if (launch_pair(net->pairs[head][i], net->X[head], 0, net->X[head], (i + 1) * c4, net->h, net->w, st)) return -2;
         return 0;
-    }
-    for (int i = 0; i < net->gf; ++i) {
-        if (launch_conv(net->dense[head][2 * i], net->X[head], 0, T, 0, nullptr, OJF_ACT_LEAKY, net->cs, 1.0f,
-                        net->h, net->w, st)) return -2;
-        if (launch_conv(net->dense[head][2 * i + 1], T, 0, net->X[head], (i + 1) * c4, nullptr, OJF_ACT_LEAKY,
-                        net->cs, 1.0f, net->h, net->w, st)) return -2;
+    case DENSE_CONVS:
+        for (int i = 0; i < net->gf; ++i) {
+            if (launch_conv(net->dense[head][2 * i], net->X[head], 0, T, 0, nullptr, OJF_ACT_LEAKY, net->cs, 1.0f,
+                            net->h, net->w, st)) return -2;
+            if (launch_conv(net->dense[head][2 * i + 1], T, 0, net->X[head], (i + 1) * c4, nullptr, OJF_ACT_LEAKY,
+                            net->cs, 1.0f, net->h, net->w, st)) return -2;
+        }
+        return 0;
     }
     return 0;
 }
@@ -2925,9 +3086,9 @@ OJF_API int ojf_net_create(ojf_net **out, int version, int n_points, int growth,
     using namespace ojf;
     if (!out || !L) return fail("ojf_net_create: null pointer argument");
     *out = nullptr;
-    if (version != 2 && version != 3) return fail("ojf_net_create: version must be 2 or 3");
-    if (n_points < 1 || growth < 1 || h <= 0 || w <= 0) return fail("ojf_net_create: bad sizes");
-    const int sem = use_semantics ? 1 : 0;
+    NetShape shape;
+    if (const char *why = net_shape(shape, version, n_points, growth, use_semantics, h, w, g_default_arith)) return refuse("ojf_net_create", why);
+    const int sem = shape.sem;
     if (n_layers != layer_count(version, growth, sem)) return fail("ojf_net_create: wrong number of folded layers");
     for (int i = 0; i < n_layers; ++i)
         if (!L[i].weight_host || !L[i].bias_host || (L[i].ksize != 1 && L[i].ksize != 3) || L[i].dilation < 1)
@@ -2940,18 +3101,26 @@ OJF_API int ojf_net_create(ojf_net **out, int version, int n_points, int growth,
             if (!std::isfinite(L[i].bias_host[k])) return fail("ojf_net_create: non-finite bias");
     }
 
+    {   // the dilations of the VortexPoolings' 3x3 pairs: vortex k's 18 layers follow its head's 2*growth dense layers
+        const int base[3] = {2 * growth, 2 * (2 * growth + 18) - 18, shape.heads * (2 * growth + 18)};
+        for (int k = 0; k < 3; ++k) {
+            if (k == 1 && shape.heads == 1) continue;
+            for (int br = 0; br < 4; ++br)
+                if (L[base[k] + 2 + 4 * br].dilation != L[base[k] + 3 + 4 * br].dilation) shape.same_dil[k] = false;
+        }
+    }
+    ForwardPlan plan;
+    if (const char *why = plan_forward(shape, &plan)) return refuse("ojf_net_create", why);
+
     ojf_net *net = new ojf_net();
+    net->shape = shape; net->plan = plan;
     net->version = version; net->P = n_points; net->gf = growth; net->sem = sem;
-    net->arith = g_default_arith;
-    net->c = 2 * n_points + 1 + (version == 2 ? sem : 0);
-    net->cs = round_up(net->c, 4);
-    net->heads = (version == 3 && sem) ? 2 : 1;
-    net->h = h; net->w = w; net->npix = h * w;
-    net->pool_in = net->c * (growth + 1);
-    net->os = round_up(net->pool_in, 4);
+    net->arith = shape.arith;
+    net->c = shape.c; net->cs = shape.cs; net->heads = shape.heads;
+    net->h = h; net->w = w; net->npix = shape.npix;
+    net->pool_in = shape.pool_in; net->os = shape.os;
     net->scale = output_scale;
     const int c = net->c, cs = net->cs, gf = growth, os = net->os;
-    if (net->heads * os > 256 || (gf + 1) * cs > 256) { delete net; return fail("ojf_net_create: topology too wide"); }
     net->macs_per_pixel = 0;
     for (int i = 0; i < n_layers; ++i) net->macs_per_pixel += (int64_t)L[i].c_in * L[i].c_out * L[i].ksize * L[i].ksize;
 
@@ -2970,7 +3139,7 @@ OJF_API int ojf_net_create(ojf_net **out, int version, int n_points, int growth,
             if (finish(ba, pa, net->arith) || finish(bb, pb, net->arith)) return -2;
             net->dense[head].push_back(pa);
             net->dense[head].push_back(pb);
-            if (net->arith == OJF_ARITH_F16X3 && cs <= 24) {
+            if (pair_form(shape)) {
                 PackedPair pp;
                 if (finish_pair(ba, bb, pp, pair_cfg_for(net->h, net->w))) return -2;
                 net->pairs[head].push_back(pp);
@@ -2978,27 +3147,26 @@ OJF_API int ojf_net_create(ojf_net **out, int version, int n_points, int growth,
                 bbs.push_back(bb);
             }
         }
-        if ((int)bas.size() == gf && cs == 4 * kChainNG && gf <= kChainMaxLayers && finish_chain(bas, bbs, net->chains[head])) return -2;
+        if (chain_form(shape) && finish_chain(bas, bbs, net->chains[head])) return -2;
         return 0;
     };
     const std::vector<int> dense_map = slot_map(net->pool_in, c, cs);
     const std::vector<int> flat_map = slot_map(net->pool_in, net->pool_in, os);
     if (version == 3) {
         rc = build_dense(0);
-        if (!rc) { rc = build_vortex(net, net->vortex[0], L + li, net->pool_in, dense_map, (gf + 1) * cs); li += 18; }
+        if (!rc) { rc = build_vortex(net, 0, L + li, net->pool_in, dense_map); li += 18; }
         if (!rc && sem) {
             rc = build_dense(1);
-            if (!rc) { rc = build_vortex(net, net->vortex[1], L + li, net->pool_in, dense_map, (gf + 1) * cs); li += 18; }
+            if (!rc) { rc = build_vortex(net, 1, L + li, net->pool_in, dense_map); li += 18; }
         }
         if (!rc) {
-            rc = build_vortex(net, net->vortex[2], L + li, net->heads * net->pool_in,
-                              slot_map(net->heads * net->pool_in, net->pool_in, os), net->heads * os);
+            rc = build_vortex(net, 2, L + li, net->heads * net->pool_in, slot_map(net->heads * net->pool_in, net->pool_in, os));
             li += 18;
         }
     } else {
         rc = build_dense(0);
-        if (!rc) { rc = build_vortex(net, net->vortex[0], L + li, net->pool_in, dense_map, (gf + 1) * cs); li += 18; }
-        if (!rc) { rc = build_vortex(net, net->vortex[2], L + li, net->pool_in, flat_map, os); li += 18; }
+        if (!rc) { rc = build_vortex(net, 0, L + li, net->pool_in, dense_map); li += 18; }
+        if (!rc) { rc = build_vortex(net, 2, L + li, net->pool_in, flat_map); li += 18; }
     }
     if (!rc) {
         int prev_phys = os;
@@ -3014,7 +3182,7 @@ OJF_API int ojf_net_create(ojf_net **out, int version, int n_points, int growth,
             prev_phys = round_up(l.c_out, 4);
         }
     }
-    if (!rc && n_points == 9 && growth == 5 && (c == 19 || c == 20)) {
+    if (!rc && plan.chain_kind) {
         // fused prediction head: repack the 11 pointwise layers as chain_layer fragments
         const int first = n_layers - (2 * (gf - 1) + 3);
         std::vector<float> cw, cb;
@@ -3029,7 +3197,6 @@ OJF_API int ojf_net_create(ojf_net **out, int version, int n_points, int growth,
             prev_phys = out_phys;
         }
         if (upload(cw, &net->chain_w) || upload(cb, &net->chain_b)) rc = -2;
-        else net->chain_kind = c;
     }
     if (!rc) {  // the gave convs act on a 1x1 map: not a per-pixel cost
         int idx = 0;
@@ -3038,25 +3205,6 @@ OJF_API int ojf_net_create(ojf_net **out, int version, int n_points, int growth,
         skip_dense(); sub_gave();
         if (version == 3 && sem) { skip_dense(); sub_gave(); }
         sub_gave();
-    }
-    if (!rc) {
-        // One dense_chain_kernel launch per head instead of gf dense_pair_kernel launches: the dense-growth buffers then hold
-        // split planes, which only the chain-flow entry kernel reads (OJF_NO_DENSE_CHAIN=1 / the general flow: pair kernels)
-        static const bool no_chain = getenv("OJF_NO_DENSE_CHAIN") != nullptr;
-        bool ok = net->arith == OJF_ARITH_F16X3 && !no_chain;
-        {
-            //  frames the chain kernel is not the right tool for fall back to one dense_pair_kernel launch per Block:
-            //  * more tiles than the flag array holds (frames beyond ~2.6 Mpixel used to fail in ojf_net_forward);
-            //  * w % 8 != 0: a 128-byte line of a plane is 8 pixels, so a line then straddles two image rows - pixels of tiles
-            //    whose flags a reader never checked - and only the slot of the Block just finished is read with sc1 loads: an
-            //    early reader could pull a not-yet-written pixel of an OLDER slot into its XCD's L2 and a later item read it stale.
-            const int big = ((w + 19) / 20) * ((h + 15) / 16);
-            const int tiles = big >= 200 ? big : ((w + 11) / 12) * ((h + 7) / 8);
-            if (tiles > kChainSyncInts - kChainFlags0 || (w % 8) != 0) ok = false;
-        }
-        for (int hd = 0; hd < net->heads && ok; ++hd)
-            ok = net->chains[hd].layers == gf && net->vortex[hd].entry_w && net->vortex[hd].tail_w;
-        net->chain_dense = ok;
     }
     const size_t np = (size_t)net->npix;
     if (!rc) rc = alloc_planes(&net->X[0], np, (gf + 1) * cs);
@@ -3072,6 +3220,8 @@ OJF_API int ojf_net_create(ojf_net **out, int version, int n_points, int growth,
         if (!rc) rc = alloc_planes(&sc.U, np, 4 * cs);
         if (!rc) rc = alloc_planes(&sc.V, np, 4 * cs);
         if (!rc) rc = alloc_planes(&sc.partial, kSumBlocks, 256);
+        for (int i = 0; i < plan.n_steps && !rc; ++i)  // fall-back buffer of the unfused tail
+            if (plan.step[i].set == hd && plan.step[i].tail == TAIL_UNFUSED && !sc.CAT) rc = alloc_planes(&sc.CAT, np, 4 * os);
         if (!rc) rc = check_hip(hipMalloc(reinterpret_cast<void **>(&sc.colsum), sizeof(ColSums)), "hipMalloc");
         if (!rc) rc = check_hip(hipMemset(sc.colsum, 0, sizeof(ColSums)), "hipMemset");
         if (!rc && hd == 0 && net->heads == 2) {
@@ -3092,6 +3242,8 @@ OJF_API int ojf_net_create(ojf_net **out, int version, int n_points, int growth,
     }
     if (!rc) rc = alloc_planes(&net->YY, np, net->heads * os);
     if (!rc) rc = alloc_planes(&net->Y3, np, os);
+    if (!rc && plan.head_layers) rc = alloc_planes(&net->PA, np, os);
+    if (!rc && plan.head_layers) rc = alloc_planes(&net->PB, np, os);
     if (!rc) rc = check_hip(hipStreamCreateWithFlags(&net->cap, hipStreamNonBlocking), "hipStreamCreate");
     {
         const char *g = getenv("OJF_NET_GRAPH");  // opt-in: see the note at ojf_net::cap
@@ -3113,7 +3265,7 @@ int net_input_slot(::ojf_net *net, NetInputSlot *slot)
     if (!net || !slot || net->sem || net->heads != 1) return 1;
     slot->x0 = net->X[0]; slot->cs4 = net->cs / 4; slot->P = net->P; slot->h = net->h; slot->w = net->w;
     slot->ovf = net->arith == OJF_ARITH_F16X3 ? overflow_flag() : nullptr;
-    slot->split = net->chain_dense ? 1 : 0;
+    slot->split = net->plan.dense == DENSE_CHAIN ? 1 : 0;
     return 0;
 }
 }  // namespace ojf
@@ -3137,7 +3289,7 @@ OJF_API int ojf_net_prepare_input(ojf_net *net, const float *values, const float
     a.n_classes = n_classes;
     a.v2_sem = (net->version == 2 && net->sem) ? 1 : 0;
     a.ovf = net->arith == OJF_ARITH_F16X3 ? overflow_flag() : nullptr;
-    a.split = net->chain_dense ? 1 : 0;
+    a.split = net->plan.dense == DENSE_CHAIN ? 1 : 0;
     hipLaunchKernelGGL(prepare_input_kernel, dim3((a.npix + 255) / 256), dim3(256), 0, as_stream(stream), a);
     return check_hip(hipGetLastError(), "prepare_input_kernel launch");
 }
@@ -3234,7 +3386,8 @@ static void pair_head_stream(ojf_net *net, hipStream_t st)
     if (net->sc[0].side) pair_stream(net->sc[0].side, &st, 1, alone, cycles);
 }
 
-// every launch of one forward pass, in order, on `st` (+ the side stream, forked and joined with events)
+// every launch of one forward pass, in the plan's order, on `st` (+ the second head's stream and the side streams, forked and
+// joined with events).  Per call: the stream, est / est_stride, and whether the second head's stream is distinct from `st`.
 static int forward_launches(ojf_net *net, float *est, int est_stride, hipStream_t st)
 {
     const int o4 = net->os / 4;
@@ -3244,61 +3397,28 @@ static int forward_launches(ojf_net *net, float *est, int est_stride, hipStream_
     ca.out_rows = est; ca.in_g0 = 0; ca.c4_in = o4; ca.npix = net->npix;
     ca.rows_stride = est_stride; ca.rows_n = net->P; ca.scale = net->scale;
     ca.ovf = net->arith == OJF_ARITH_F16X3 ? overflow_flag() : nullptr;
-    bool head_done = false;  // set when the last VortexPooling's tail kernel ran the head as well
-    VortexLinks last;        // links of the last VortexPooling: the head rides along where the tail can carry it
-    last.head = net->chain_kind ? &ca : nullptr;
-    last.head_done = &head_done;
-    if (net->version == 3) {
-        const bool two = net->heads == 2;
-        if (two) pair_head_stream(net, st);
-        hipStream_t s1 = two ? net->head1 : st;
-        if (two && s1 != st) {  // the semantic head runs beside the geometric one
-            OJF_HIP(hipEventRecord(net->ev_head_fork, st));
-            OJF_HIP(hipStreamWaitEvent(s1, net->ev_head_fork, 0));
-        }
-        // two heads: each head's tail runs ITS half of vortex3's entry GEMM (the concatenation YY is then never written)
-        const bool halves = two && net->vortex[2].entry_wh[0] && net->vortex[2].entry_wh[1] && net->sc[0].Q0 && net->colsum3;
-        bool done1 = false;
-        if (two) {
-            if (run_dense(net, 1, s1)) return -2;
-            VortexLinks l1;
-            l1.in_split = net->chain_dense;
-            if (halves) { l1.next = &net->vortex[2]; l1.next_done = &done1; l1.half = 1; l1.next_colsum = net->colsum3; }
-            if (run_vortex(net, net->vortex[1], net->X[1], 0, net->YY, o4, s1, net->sc[1], l1)) return -2;
-        }
-        if (run_dense(net, 0, st)) return -2;
-        bool entry_done = false;  // single head: vortex0's tail runs vortex3's entry GEMM (its own output is never written)
-        VortexLinks l0;
-        l0.in_split = net->chain_dense;
-        if (halves) { l0.next = &net->vortex[2]; l0.half = 0; l0.next_colsum = net->colsum3; }
-        else if (!two) l0.next = &net->vortex[2];
-        l0.next_done = &entry_done;
-        if (run_vortex(net, net->vortex[0], net->X[0], 0, net->YY, 0, st, net->sc[0], l0)) return -2;
-        if (two && s1 != st) {
+    const ForwardPlan &plan = net->plan;
+    const bool two = plan.n_steps == 3;
+    if (two) pair_head_stream(net, st);
+    hipStream_t s1 = two ? net->head1 : st;
+    if (two && s1 != st) {  // the semantic head runs beside the geometric one
+        OJF_HIP(hipEventRecord(net->ev_head_fork, st));
+        OJF_HIP(hipStreamWaitEvent(s1, net->ev_head_fork, 0));
+    }
+    for (int i = 0; i < plan.n_steps; ++i) {
+        const VortexStep &s = plan.step[i];
+        hipStream_t ss = s.vortex == 1 ? s1 : st;
+        if (s.vortex < 2) {  // a head: its dense Blocks first
+            if (run_dense(net, s.vortex, ss)) return -2;
+        } else if (two && s1 != st) {  // the last VortexPooling reads both heads' results
             OJF_HIP(hipEventRecord(net->ev_head_join, s1));
             OJF_HIP(hipStreamWaitEvent(st, net->ev_head_join, 0));
         }
-        if (halves && entry_done != done1) return fail("ojf_net_forward: internal error (one head ran its half of the entry GEMM, the other did not)");
-        last.entry_done = entry_done;
-        last.z2 = (halves && entry_done) ? net->sc[1].Z : nullptr;
-        if (run_vortex(net, net->vortex[2], net->YY, 0, net->Y3, 0, st, net->sc[0], last)) return -2;
-    } else {
-        if (run_dense(net, 0, st)) return -2;
-        bool entry_done = false;
-        VortexLinks l0;
-        l0.in_split = net->chain_dense;
-        l0.next = &net->vortex[2];
-        l0.next_done = &entry_done;
-        if (run_vortex(net, net->vortex[0], net->X[0], 0, net->YY, 0, st, net->sc[0], l0)) return -2;
-        last.entry_done = entry_done;
-        if (run_vortex(net, net->vortex[2], net->YY, 0, net->Y3, 0, st, net->sc[0], last)) return -2;
+        if (run_vortex(net, s, ss, ca)) return -2;
     }
-    if (head_done) return 0;
-    // (a net with a chain-form head - chain_kind - has fused tails, and the last one ran the head: ojf_net_create)
-    if (net->chain_kind) return fail("ojf_net_forward: internal error (the last tail did not run the prediction head)");
+    if (!plan.head_layers) return 0;
     const float *pin = net->Y3;
     const int np = (int)net->pred.size();
-    if (ensure_planes(&net->PA, (size_t)net->npix, net->os) || ensure_planes(&net->PB, (size_t)net->npix, net->os)) return -2;
     float *pp[2] = {net->PA, net->PB};
     for (int i = 0; i < np; ++i) {
         const PackedConv &pc = net->pred[i];
@@ -3331,11 +3451,7 @@ static void capture_graph(ojf_net *net, float *est, int est_stride)
     drop_graph(net);
     net->g_est = est;
     net->g_stride = est_stride;
-    // no allocation may happen while capturing: have the fall-back paths' buffers in place
-    if (ensure_planes(&net->sc[0].CAT, (size_t)net->npix, 4 * net->os) ||
-        (net->heads == 2 && ensure_planes(&net->sc[1].CAT, (size_t)net->npix, 4 * net->os)) ||
-        ensure_planes(&net->PA, (size_t)net->npix, net->os) ||
-        ensure_planes(&net->PB, (size_t)net->npix, net->os)) { net->use_graph = false; return; }
+    // (no allocation happens while capturing: every buffer of the plan exists since ojf_net_create)
     if (hipStreamBeginCapture(net->cap, hipStreamCaptureModeThreadLocal) != hipSuccess) { net->use_graph = false; return; }
     const int rc = forward_launches(net, est, est_stride, net->cap);
     hipGraph_t g = nullptr;
@@ -3423,6 +3539,30 @@ OJF_API int ojf_net_profile(ojf_net *net, float *est, int est_stride, ojf_stream
     g_marks.clear();
     (void)hipEventDestroy(e0);
     return rc ? rc : n;
+}
+
+OJF_API int ojf_net_plan(int version, int n_points, int growth, int use_semantics, int h, int w, int arithmetic, char *names,
+                         int names_cap)
+{
+    using namespace ojf;
+    if (!names || names_cap < 1) return refuse("ojf_net_plan", "bad argument");
+    if (arithmetic != OJF_ARITH_F32 && arithmetic != OJF_ARITH_F16X3) return refuse("ojf_net_plan", "unknown arithmetic (OJF_ARITH_F32 or OJF_ARITH_F16X3)");
+    NetShape shape;
+    ForwardPlan plan;
+    if (const char *why = net_shape(shape, version, n_points, growth, use_semantics, h, w, arithmetic)) return refuse("ojf_net_plan", why);
+    if (const char *why = plan_forward(shape, &plan)) return refuse("ojf_net_plan", why);
+    const std::vector<Launch> launches = plan_launches(shape, plan);
+    size_t used = 0;
+    names[0] = 0;
+    for (Launch l : launches) {
+        const size_t len = strlen(kLaunchNames[l]);
+        if (used + len + 2 > (size_t)names_cap) return refuse("ojf_net_plan", "names buffer too small");
+        memcpy(names + used, kLaunchNames[l], len);
+        names[used + len] = '\n';
+        used += len + 1;
+        names[used] = 0;
+    }
+    return (int)launches.size();
 }
 
 OJF_API int ojf_net_set_arithmetic(int arithmetic)

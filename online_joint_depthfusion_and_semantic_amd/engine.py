@@ -103,6 +103,17 @@ class FusionNetEngine:
             _lib.check(n, 'ojf_net_profile')
         return list(zip(names.value.decode().split('\n')[:n], [float(us[i]) for i in range(n)]))
 
+    @staticmethod
+    def plan(version, n_points, growth, use_semantics, h, w, arithmetic='f16x3'):
+        """Kernel names of the forward pass planned for a net of this shape, in host enqueue order (ojf_net_plan: no device needed;
+        version 2 | 3, growth = growth_factor - 1).  What profile() reports for such a net with the reference's dilations."""
+        lib = _lib.load()
+        names = ctypes.create_string_buffer(8192)
+        n = lib.ojf_net_plan(version, n_points, growth, int(bool(use_semantics)), h, w, _lib.ARITHMETIC[arithmetic], names, 8192)
+        if n < 0:
+            _lib.check(n, 'ojf_net_plan')
+        return names.value.decode().split('\n')[:n]
+
     def check(self):
         """Synchronise the stream and raise OjfError if the split-fp16 range guard fired (include/ojf.h)."""
         _lib.check(self.lib.ojf_net_check(_lib.stream_ptr(self.device)), 'ojf_net_check')

@@ -8,6 +8,7 @@ import torch.nn.functional as F
 
 from online_joint_depthfusion_and_semantic_amd import _lib, model
 from online_joint_depthfusion_and_semantic_amd.engine import FusionNetEngine, conv2d_rows
+import net_plan_cases
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -165,10 +166,12 @@ def test_f16x3_range_guard(cuda):
 
 
 @pytest.mark.parametrize('arith', ['f16x3', 'f32'])
-@pytest.mark.parametrize('version,sem,n_points,growth', [('v3', False, 5, 4), ('v3', True, 3, 3), ('v2', True, 7, 5)])
+@pytest.mark.parametrize('version,sem,n_points,growth', [('v3', False, 5, 4), ('v3', True, 3, 3), ('v2', True, 7, 5), ('v3', False, 8, 7)])
 def test_fusion_net_other_topologies(cuda, arith, version, sem, n_points, growth):
     """Channel counts other than 19/20 x 6 take the generic paths (stand-alone closing 1x1 convolutions and final
-    conv instead of the fused tail, layer-by-layer prediction head): same tolerance."""
+    conv instead of the fused tail, layer-by-layer prediction head): same tolerance.  `growth` is the model's growth_factor
+    (= the C ABI's growth + 1); 8 points x growth_factor 7 is 7 x 20 = 140 dense channels: the stand-alone 16-tile entry kernel,
+    fused tails (the first one carries the next entry GEMM), no chain-form head."""
     h, w = 40, 56
     cfg = NS(n_points=n_points, growth_factor=growth, use_semantics=sem, output_scale=1.0, resx=w, resy=h)
     torch.manual_seed(11)
@@ -416,3 +419,57 @@ def test_branch_kernel_against_the_grouped_launches(cuda, tmp_path, h, w, sem, s
     print('%s=1 vs grouped launches %dx%d sem=%s: max difference %.2e' % (switch, w, h, sem, err))
     assert err > 0.0, switch + '=1 did not change the path'
     assert err <= 2e-6, err
+
+
+def _profile_and_plan(cuda, version, sem, n_points, growth, h, w, arith):
+    """-> (launch names of a profiled forward, ojf_net_launch_count after a plain forward, the planned names) of a random net"""
+    cfg = NS(n_points=n_points, growth_factor=growth + 1, use_semantics=bool(sem), output_scale=1.0, resx=w, resy=h)
+    torch.manual_seed(5)
+    net = getattr(model, 'FusionNet_v%d' % version)(cfg).eval()
+    eng = FusionNetEngine(net, h, w, cuda, arithmetic=arith)
+    g = torch.Generator().manual_seed(3)
+    fv = ((torch.rand(h * w, n_points, generator=g) - 0.5) * 0.2).to(cuda)
+    fw = torch.rand(h * w, n_points, generator=g).to(cuda)
+    ids = torch.randint(0, 30, (h, w), generator=g, dtype=torch.uint8).to(cuda)
+    eng.prepare_input(fv, fw, torch.rand(h, w, generator=g).to(cuda), ids if sem else None, 30)
+    est = torch.empty((h * w, n_points), device=cuda)
+    eng.forward(est)
+    launches = eng.launches
+    names = [name for name, _ in eng.profile(est)]
+    eng.check()
+    eng.close()
+    return names, launches, FusionNetEngine.plan(version, n_points, growth, sem, h, w, arith)
+
+
+@pytest.mark.parametrize('case', list(net_plan_cases.PLANS), ids=lambda c: 'v%d-sem%d-%dx%d-%dx%d-%s' % c)
+def test_forward_runs_its_plan(cuda, monkeypatch, case):
+    """What a forward pass launches (ojf_net_profile: names in host enqueue order; ojf_net_launch_count after a plain forward) is
+    what ojf_net_plan says for the net's shape, for every row of the case table (tests/net_plan_cases.py)."""
+    for name in net_plan_cases.SWITCH_PLANS:
+        monkeypatch.delenv(name, raising=False)
+    names, launches, plan = _profile_and_plan(cuda, *case)
+    assert names == plan
+    assert launches == len(plan)
+
+
+_PLAN_AB_SCRIPT = """
+import sys
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + '/tests')
+import torch
+import test_net_gpu
+names, launches, plan = test_net_gpu._profile_and_plan(torch.device('cuda:0'), 3, 0, 9, 5, 24, 32, 'f16x3')
+assert names == plan and launches == len(plan), (names, launches, plan)
+print('\\n'.join(names))
+"""
+
+
+@pytest.mark.parametrize('switch', list(net_plan_cases.SWITCH_PLANS))
+def test_forward_runs_its_plan_under_a_switch(cuda, switch):
+    """The same with one of the test-only switches set (read once per process: a child process)."""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in net_plan_cases.SWITCH_PLANS}
+    env[switch] = '1'
+    out = subprocess.run([sys.executable, '-c', _PLAN_AB_SCRIPT, root], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert out.stdout.split('\n')[:-1] == net_plan_cases.SWITCH_PLANS[switch]
