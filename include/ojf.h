@@ -616,6 +616,37 @@ int ojf_fuse_projective(uint16_t *tsdf_dev, uint16_t *weights_dev, uint8_t *ids_
                         const uint8_t *labels_dev /* u8[n,h,w] or NULL */, const float *label_scores_dev /* or NULL */,
                         int h, int w, float trunc, float max_weight, float near, int carve, ojf_stream_t stream);
 
+/* ---- COLOR (a colour volume beside the fused geometry; no counterpart in the reference) ------------------------------
+ * The colour volume color_dev is fp16 [X,Y,Z,4], voxel-major, 8 B per voxel (c0, c1, c2, W): the running mean of the three
+ *   image channels on the image's 0..255 scale, in the image's channel order, and the colour weight W (0: no colour yet);
+ *   all zeros at reset.
+ * ojf_fuse_color: fuses n colour views (1 <= n <= OJF_COLOR_MAX_VIEWS, one h x w for all) into color_dev in place.  Every
+ *   voxel centre is projected into each view in turn exactly as ojf_fuse_projective does (same constants, nearest pixel,
+ *   depth_dev / mask_dev tests, near); a voxel with -band <= d - zc <= band takes c_k = (W*c_k + image[pixel][k]) / (W + 1),
+ *   W = min(W + 1, max_weight), rounded to fp16 after every view.  image_dev u8[n,h,w,4] (4-byte aligned; the 4th byte is
+ *   ignored).  band > 0, 1 <= max_weight <= 2048, near >= 0, pinhole K.  The TSDF / weight volumes are not read.  One
+ *   owner lane per voxel: no atomics, no workspace, the same bits on every run, and n views in one call give the bits of
+ *   n calls of one view.  A pointer off the 16-byte grid is served by element-wise accesses.  One kernel, never waits.
+ * ojf_color_sample: rgba_dev u8[n][4] = the colour at points_dev f32[n][3] given in voxel index coordinates (voxel
+ *   (i,j,k) sits at (i,j,k)): the trilinear mean over the corners that lie inside the grid and have W > 0, renormalised
+ *   by their weights, rounded to u8, alpha 255; (0,0,0,0) where no corner counts or a coordinate is non-finite, < -1 or
+ *   > its axis' size.  1 <= n < 2^31.
+ * ojf_color_render: rgba_dev u8[n,h,w,4] = the colour at the point of depth depth_dev f32[n,h,w] on each pixel's ray;
+ *   n, Kinv_host, E_host, h, w as for ojf_render, whose depth image then reproduces its hit points.  A depth that is not
+ *   finite and > 0 writes 0.  Both read-outs use one lane per output and write every output once.
+ * Bad arguments are refused before any HIP call.  The exact fp32 operation order is in csrc/ojf_color.hip. */
+#define OJF_COLOR_MAX_VIEWS 32
+int ojf_fuse_color(uint16_t *color_dev /* fp16 [X,Y,Z,4] */, int X, int Y, int Z, const double *origin_host,
+                   double resolution, int n, const double *K_host /* f64[n][9] */, const double *E_host /* f64[n][12] */,
+                   const float *depth_dev /* f32[n,h,w] */, const uint8_t *mask_dev /* u8[n,h,w] or NULL */,
+                   const uint8_t *image_dev /* u8[n,h,w,4] */, int h, int w, float band, float max_weight, float near,
+                   ojf_stream_t stream);
+int ojf_color_sample(const uint16_t *color_dev, int X, int Y, int Z, const float *points_dev /* f32[n][3] */, size_t n,
+                     uint8_t *rgba_dev /* u8[n][4] */, ojf_stream_t stream);
+int ojf_color_render(const uint16_t *color_dev, int X, int Y, int Z, const double *origin_host, double resolution, int n,
+                     const float *Kinv_host, const float *E_host, const float *depth_dev, int h, int w,
+                     uint8_t *rgba_dev /* u8[n,h,w,4] */, ojf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

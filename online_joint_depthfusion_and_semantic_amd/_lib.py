@@ -47,6 +47,7 @@ TRACK_MAX_LEVELS = 4  # include/ojf.h OJF_TRACK_MAX_LEVELS
 TRACK_MAX_ITERATIONS = 128  # include/ojf.h OJF_TRACK_MAX_ITERATIONS
 TRACK_TERMS = 29  # include/ojf.h OJF_TRACK_TERMS
 PROJECTIVE_MAX_VIEWS = 32  # include/ojf.h OJF_PROJECTIVE_MAX_VIEWS
+COLOR_MAX_VIEWS = 32  # include/ojf.h OJF_COLOR_MAX_VIEWS
 
 
 class ExtractJob(ctypes.Structure):
@@ -164,6 +165,11 @@ SIGNATURES = {
     # tsdf, weights, ids, scores, X, Y, Z, origin, resolution, n, K, E, depth, mask, labels, label scores, h, w, trunc,
     # max_weight, near, carve, stream
     'ojf_fuse_projective': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _i, _vp]),
+    # colour volume, X, Y, Z, origin, resolution, n, K, E, depth, mask, image, h, w, band, max_weight, near, stream
+    'ojf_fuse_color': (_i, [_vp, _i, _i, _i, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _vp]),
+    'ojf_color_sample': (_i, [_vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    # colour volume, X, Y, Z, origin, resolution, n, Kinv, E, depth, h, w, rgba, stream
+    'ojf_color_render': (_i, [_vp, _i, _i, _i, _vp, _d, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
 }
 
 _LIB = None

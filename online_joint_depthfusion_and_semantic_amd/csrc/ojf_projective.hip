@@ -37,32 +37,24 @@
 // one call give the bits of n calls of one view.  No atomics, no LDS, no workspace: every run repeats its bits.
 // The last group of a volume whose size is no multiple of 8, and every group of a volume whose pointers are not aligned
 // for the wide accesses, go element by element.
-#include "ojf_common.h"
-
-#include <math.h>
-#include <cmath>
+// The host constants and steps 1-3 are in ojf_projview.h, shared with the colour sweep (ojf_color.hip).
+#include "ojf_projview.h"
 
 namespace ojf {
 
 constexpr int kProjGroup = 8;
 constexpr int kProjBlock = 256;
 
-struct ProjView {  // 16 floats, by value in the kernel arguments
-    float A[9];    // A[3a+m]
-    float b[3];
-    float fx, fy, cx, cy;
-};
-
 struct ProjArgs {
     uint16_t *tsdf, *wgt;
     uint8_t *ids;      // NULL: geometry only
     uint16_t *scores;
-    const float *depth;
-    const uint8_t *mask, *labels;
+    ProjImages im;
+    const uint8_t *labels;
     const float *lscores;
     uint32_t total, groups;
-    int Y, Z, h, w, n, carve, vec;
-    float trunc, max_weight, near, cmax, rmax;
+    int Y, Z, n, carve, vec;
+    float trunc, max_weight;
 };
 
 struct ProjLaunch {
@@ -70,13 +62,7 @@ struct ProjLaunch {
     ProjView v[OJF_PROJECTIVE_MAX_VIEWS];
 };
 
-// element e of 16-bit (8-bit) values packed into 32-bit registers; e is a constant after unrolling
-__device__ __forceinline__ uint32_t get16(const uint32_t *q, int e) { return (q[e >> 1] >> ((e & 1) * 16)) & 0xffffu; }
-__device__ __forceinline__ void set16(uint32_t *q, int e, uint32_t v)
-{
-    const int sh = (e & 1) * 16;
-    q[e >> 1] = (q[e >> 1] & ~(0xffffu << sh)) | (v << sh);
-}
+// element e of 8-bit values packed into 32-bit registers (16-bit: ojf_projview.h); e is a constant after unrolling
 __device__ __forceinline__ uint32_t get8(const uint32_t *q, int e) { return (q[e >> 2] >> ((e & 3) * 8)) & 0xffu; }
 __device__ __forceinline__ void set8(uint32_t *q, int e, uint32_t v)
 {
@@ -117,21 +103,8 @@ __global__ __launch_bounds__(kProjBlock) void projective_kernel(ProjLaunch L)
     const bool vec = P.vec && cnt == kProjGroup;
     const bool sem = P.ids != nullptr;
 
-    // voxel indices of the group's elements (a group may run over the end of a z row)
     float xs[kProjGroup], ys[kProjGroup], zs[kProjGroup];
-    {
-        uint32_t k = first % (uint32_t)P.Z;
-        const uint32_t row = first / (uint32_t)P.Z;
-        uint32_t j = row % (uint32_t)P.Y, i = row / (uint32_t)P.Y;
-#pragma unroll
-        for (int e = 0; e < kProjGroup; ++e) {
-            xs[e] = (float)i; ys[e] = (float)j; zs[e] = (float)k;
-            if (++k == (uint32_t)P.Z) {
-                k = 0;
-                if (++j == (uint32_t)P.Y) { j = 0; ++i; }
-            }
-        }
-    }
+    voxel_indices<kProjGroup>(first, P.Y, P.Z, xs, ys, zs);
 
     uint32_t tq[4] = {0, 0, 0, 0}, wq[4] = {0, 0, 0, 0}, sq[4] = {0, 0, 0, 0}, iq[2] = {0, 0};
     bool loaded = false, sloaded = false, sdirty = false;
@@ -146,20 +119,9 @@ __global__ __launch_bounds__(kProjBlock) void projective_kernel(ProjLaunch L)
             o[e] = 0.0f;
             pix[e] = 0;
             if (e >= cnt) continue;
-            const float x = xs[e], y = ys[e], z = zs[e];
-            const float zc = ((V.A[6] * x + V.A[7] * y) + V.A[8] * z) + V.b[2];
-            if (!(zc > P.near)) continue;
-            const float p0 = ((V.A[0] * x + V.A[1] * y) + V.A[2] * z) + V.b[0];
-            const float p1 = ((V.A[3] * x + V.A[4] * y) + V.A[5] * z) + V.b[1];
-            const float u = V.fx * (p0 / zc) + V.cx;
-            const float q = V.fy * (p1 / zc) + V.cy;
-            const float c = floorf(u + 0.5f), r = floorf(q + 0.5f);
-            if (!(c >= 0.0f && c <= P.cmax && r >= 0.0f && r <= P.rmax)) continue;
-            const uint32_t px = ((uint32_t)v * (uint32_t)P.h + (uint32_t)(int)r) * (uint32_t)P.w + (uint32_t)(int)c;
-            const float d = P.depth[px];
-            if (!(fabsf(d) < INFINITY && d > 0.0f)) continue;
-            if (P.mask && P.mask[px] == 0) continue;
-            const float s = d - zc;
+            uint32_t px;
+            float s;
+            if (!project_depth(V, P.im, v, xs[e], ys[e], zs[e], px, s)) continue;
             if (s < -P.trunc) continue;
             const bool in_band = s <= P.trunc;
             if (!in_band && !P.carve) continue;
@@ -225,13 +187,6 @@ __global__ __launch_bounds__(kProjBlock) void projective_kernel(ProjLaunch L)
     }
 }
 
-static bool all_finite(const double *p, int n)
-{
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(p[i])) return false;
-    return true;
-}
-
 }  // namespace ojf
 
 OJF_API int ojf_fuse_projective(uint16_t *tsdf, uint16_t *wgt, uint8_t *ids, uint16_t *scores, int X, int Y, int Z,
@@ -244,45 +199,22 @@ OJF_API int ojf_fuse_projective(uint16_t *tsdf, uint16_t *wgt, uint8_t *ids, uin
     if ((ids != nullptr) != (scores != nullptr) || (ids != nullptr) != (labels != nullptr))
         return fail("ojf_fuse_projective: ids_dev, scores_dev and labels_dev are all given or all null");
     if (lscores && !labels) return fail("ojf_fuse_projective: label_scores_dev needs labels_dev (null otherwise)");
-    if (n < 1 || n > OJF_PROJECTIVE_MAX_VIEWS) return fail("ojf_fuse_projective: n must be 1..OJF_PROJECTIVE_MAX_VIEWS views");
-    if (X <= 0 || Y <= 0 || Z <= 0) return fail("ojf_fuse_projective: non-positive volume size");
-    if ((int64_t)X * Y * Z > 0x7fffffffLL) return fail("ojf_fuse_projective: volume too large");
-    if (h <= 0 || w <= 0) return fail("ojf_fuse_projective: non-positive image size");
-    if ((int64_t)n * h * w > 0x7fffffffLL || h > (1 << 24) || w > (1 << 24)) return fail("ojf_fuse_projective: images too large");
     if (!(trunc > 0.0f) || !std::isfinite(trunc)) return fail("ojf_fuse_projective: trunc must be > 0 and finite");
-    if (!(max_weight >= 1.0f && max_weight <= 2048.0f)) return fail("ojf_fuse_projective: max_weight must be in 1..2048");
-    if (!(near >= 0.0f) || !std::isfinite(near)) return fail("ojf_fuse_projective: near must be >= 0 and finite");
     if (carve != 0 && carve != 1) return fail("ojf_fuse_projective: carve must be 0 or 1");
-    if (!all_finite(origin, 3) || !std::isfinite(res) || !all_finite(K, 9 * n) || !all_finite(E, 12 * n))
-        return fail("ojf_fuse_projective: non-finite K, E, origin or resolution");
-    if (!(res > 0.0)) return fail("ojf_fuse_projective: resolution must be > 0");
-    for (int v = 0; v < n; ++v) {
-        const double *Kv = K + 9 * v;
-        if (Kv[1] != 0.0 || Kv[3] != 0.0 || Kv[6] != 0.0 || Kv[7] != 0.0 || Kv[8] != 1.0)
-            return fail("ojf_fuse_projective: K must be a pinhole matrix [fx 0 cx; 0 fy cy; 0 0 1]");
-    }
+    if (int rc = check_projective_views("ojf_fuse_projective", X, Y, Z, origin, res, n, OJF_PROJECTIVE_MAX_VIEWS, K, E, h, w, max_weight, near))
+        return rc;
     ProjLaunch L;
     ProjArgs &A = L.a;
     A.tsdf = tsdf; A.wgt = wgt; A.ids = ids; A.scores = scores;
-    A.depth = depth; A.mask = mask; A.labels = labels; A.lscores = lscores;
+    A.im.depth = depth; A.im.mask = mask; A.labels = labels; A.lscores = lscores;
     A.total = (uint32_t)((int64_t)X * Y * Z);
     A.groups = (A.total + kProjGroup - 1) / kProjGroup;
-    A.Y = Y; A.Z = Z; A.h = h; A.w = w; A.n = n; A.carve = carve;
+    A.Y = Y; A.Z = Z; A.im.h = h; A.im.w = w; A.n = n; A.carve = carve;
     // the wide accesses need 16-byte aligned fp16 volumes and an 8-byte aligned id volume; anything else goes element by element
     A.vec = (((uintptr_t)tsdf | (uintptr_t)wgt | (uintptr_t)scores) & 15) == 0 && ((uintptr_t)ids & 7) == 0;
-    A.trunc = trunc; A.max_weight = max_weight; A.near = near;
-    A.cmax = (float)(w - 1); A.rmax = (float)(h - 1);
-    for (int v = 0; v < n; ++v) {
-        const double *Kv = K + 9 * v, *Ev = E + 12 * v;
-        ProjView &V = L.v[v];
-        double gm[3];
-        for (int m = 0; m < 3; ++m) gm[m] = (origin[m] + 0.5 * res) - Ev[4 * m + 3];
-        for (int a = 0; a < 3; ++a) {
-            for (int m = 0; m < 3; ++m) V.A[3 * a + m] = (float)(Ev[4 * m + a] * res);
-            V.b[a] = (float)((Ev[a] * gm[0] + Ev[4 + a] * gm[1]) + Ev[8 + a] * gm[2]);
-        }
-        V.fx = (float)Kv[0]; V.fy = (float)Kv[4]; V.cx = (float)Kv[2]; V.cy = (float)Kv[5];
-    }
+    A.trunc = trunc; A.max_weight = max_weight; A.im.near = near;
+    A.im.cmax = (float)(w - 1); A.im.rmax = (float)(h - 1);
+    for (int v = 0; v < n; ++v) make_proj_view(K + 9 * v, E + 12 * v, origin, res, L.v[v]);
     const uint32_t blocks = (A.groups + kProjBlock - 1) / kProjBlock;
     hipLaunchKernelGGL(projective_kernel, dim3(blocks), dim3(kProjBlock), 0, as_stream(stream), L);
     OJF_HIP(hipGetLastError());

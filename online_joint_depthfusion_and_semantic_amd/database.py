@@ -59,6 +59,7 @@ class Database(torch.utils.data.Dataset):
         self.origin, self.resolution = {}, {}
         self.scenes_gt, self.scenes_est, self.fusion_weights = {}, {}, {}
         self.ids_gt, self.ids_est, self.scores = {}, {}, {}
+        self.colors = {}  # scene -> fp16 [X,Y,Z,4] colour volume (color.py), only for scenes integrate_color was called on
         self.tracked_poses = {}  # frame_id -> f64 [4,4] camera-to-world: frames fused with a tracked pose (drivers.test_fusion)
 
         for s in dataset.scenes:
@@ -96,6 +97,8 @@ class Database(torch.utils.data.Dataset):
                 sample['ids_gt'] = self.ids_gt[item].volume
         else:
             sample.update(histograms=None, ids_est=None, ids_gt=None, scores=None)
+        if self.colors.get(item) is not None:
+            sample['colors'] = self.colors[item]
         return sample
 
     def __len__(self):
@@ -112,6 +115,8 @@ class Database(torch.utils.data.Dataset):
         for s in scenes:
             self.scenes_est[s].volume = self._dev(self.scenes_est[s].volume)
             self.fusion_weights[s] = self._dev(self.fusion_weights[s])
+            if self.colors.get(s) is not None:
+                self.colors[s] = self._dev(self.colors[s])
             if gt:
                 o = self.origin[s]
                 self.origin[s] = o.double().cpu() if torch.is_tensor(o) else torch.from_numpy(np.asarray(o, np.float64))
@@ -130,6 +135,8 @@ class Database(torch.utils.data.Dataset):
             self.scenes_est[s].volume = host(self.scenes_est[s].volume)
             self.scenes_gt[s].volume = host(self.scenes_gt[s].volume)
             self.fusion_weights[s] = host(self.fusion_weights[s])
+            if self.colors.get(s) is not None:
+                self.colors[s] = host(self.colors[s])
             if self.semantics:
                 self.ids_est[s].volume = host(self.ids_est[s].volume)
                 self.scores[s].volume = host(self.scores[s].volume)
@@ -141,6 +148,11 @@ class Database(torch.utils.data.Dataset):
         being re-allocated on the host and uploaded."""
         for s in ([scene_id] if scene_id else self.scenes):
             self.state[s] = False
+            c = self.colors.get(s)
+            if _is_dev(c):
+                ops.volume_fill(c, 0.0)
+            elif c is not None:
+                self.colors[s] = np.zeros(c.shape, dtype=np.float16)  # (a host volume; goes up with the rest below)
             if _is_dev(self.scenes_est[s].volume):
                 ops.volume_fill(self.scenes_est[s].volume, self.initial_value)
                 ops.volume_fill(self.fusion_weights[s], 0.0)
@@ -161,6 +173,7 @@ class Database(torch.utils.data.Dataset):
         self.scenes_est[scene_id] = None
         self.scenes_gt[scene_id] = None
         self.fusion_weights[scene_id] = None
+        self.colors.pop(scene_id, None)
         if self.semantics:
             self.ids_est[scene_id] = None
             self.scores[scene_id] = None
@@ -248,26 +261,51 @@ class Database(torch.utils.data.Dataset):
             vol = torch.from_numpy(np.ascontiguousarray(vol))
         return vol.to(device='cuda', dtype=dtype).contiguous()
 
-    def get_mesh(self, scene_id, semantics=False, palette=None):
+    def _color_volume(self, scene_id, who):
+        if self.colors.get(scene_id) is None:
+            raise ValueError('Database.{}: scene {!r} has no colour volume (integrate_color)'.format(who, scene_id))
+        return self._device_volume(self.colors[scene_id], torch.float16)
+
+    def _vertex_colors(self, scene_id, vertices, who):
+        """u8 [V,4] colours (alpha 255 where coloured) of mesh-frame vertices: a vertex at v sits at voxel index v / resolution."""
+        from . import color
+        if len(vertices) == 0:
+            return np.zeros((0, 4), dtype=np.uint8)
+        g = np.asarray(vertices, dtype=np.float32) / np.float32(self.resolution[scene_id])  # (one fp32 division per coordinate)
+        return color.sample_color(self._color_volume(scene_id, who), g).cpu().numpy()
+
+    def get_mesh(self, scene_id, semantics=False, palette=None, color=False):
         """database.py:118-139: (vertices, faces, normals, rgb) of the zero level set of the estimated volume in
         the reference's mesh frame (voxel index * voxel size, no origin).  Marching tetrahedra instead of skimage's
-        marching cubes: same surface, different triangulation (mesh.py)."""
+        marching cubes: same surface, different triangulation (mesh.py).  color=True: rgb is what the scene's colour
+        volume holds at the vertices (color.sample_color), in [0,1] and the images' channel order, 0 where nothing is
+        coloured."""
         from . import mesh
         ids = self._device_volume(self.ids_est[scene_id].volume, torch.uint8) if semantics else None
         m = mesh.extract_mesh(self._device_volume(self.scenes_est[scene_id].volume, torch.float16), ids=ids,
                               resolution=float(self.resolution[scene_id]), palette=palette)
+        if color:
+            return m['vertices'], m['faces'], m['normals'], self._vertex_colors(scene_id, m['vertices'], 'get_mesh')[:, :3] / 255.0
         return m['vertices'], m['faces'], m['normals'], m['rgb']
 
-    def render(self, scene_id, intrinsics, extrinsics, shape, semantics=False, normals=True):
+    def render(self, scene_id, intrinsics, extrinsics, shape, semantics=False, normals=True, color=False):
         """Ray-cast the estimated volume of a scene at one or more camera poses (render.py): {'depth', 'normals',
         'labels'} device tensors of [n,h,w](,3), 0 where a ray hits nothing.  Unobserved voxels (fusion weight 0) are
-        transparent; semantics=True labels every hit with ids_est.  Works on resident and on host (to_numpy) state."""
+        transparent; semantics=True labels every hit with ids_est; color=True adds 'color', u8 [n,h,w,4]: the scene's
+        colour volume at the hit points (color.render_color; alpha 255 where coloured).  Works on resident and on host
+        (to_numpy) state."""
         from . import render
         tsdf = self._device_volume(self.scenes_est[scene_id].volume, torch.float16)
         w = self._device_volume(self.fusion_weights[scene_id], torch.float16)
         ids = self._device_volume(self.ids_est[scene_id].volume, torch.uint8) if semantics else None
-        return render.render_views(tsdf, w, ids, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]),
-                                   intrinsics=intrinsics, extrinsics=extrinsics, shape=shape, normals=normals)
+        cvol = self._color_volume(scene_id, 'render') if color else None
+        out = render.render_views(tsdf, w, ids, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]),
+                                  intrinsics=intrinsics, extrinsics=extrinsics, shape=shape, normals=normals)
+        if color:
+            from . import color as color_
+            out['color'] = color_.render_color(cvol, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]),
+                                               intrinsics=intrinsics, extrinsics=extrinsics, depth=out['depth'])
+        return out
 
     def track(self, scene_id, depth, intrinsics, extrinsics, reference_extrinsics=None, **kw):
         """Camera pose of a depth frame against the estimated volume of a scene (tracking.py, frame-to-model ICP):
@@ -302,6 +340,25 @@ class Database(torch.utils.data.Dataset):
                                    labels=dev(labels) if sem else None, label_scores=dev(label_scores) if sem else None, **kw)
         self.state[scene_id] = True
 
+    def integrate_color(self, scene_id, image, depth, intrinsics, extrinsics, mask=None, **kw):
+        """Fuse the colour images of one or more frames into the scene's colour volume (color.py; allocated, zeroed, on first
+        use): image u8 [n,]h,w,3|4 or float [n,]3,h,w on the 0..255 scale (the batch dict's), depth / mask / poses of the
+        same frames as for ``integrate_depth``; ``kw`` goes to ``color.integrate_color`` (band - default: the initial value -,
+        max_weight, near).  Geometry and labels are not touched."""
+        from . import color
+        tsdf = self.scenes_est[scene_id].volume
+        if not _is_dev(tsdf) or not (self.colors.get(scene_id) is None or _is_dev(self.colors[scene_id])):
+            raise ValueError('Database.integrate_color: the volumes of {!r} are not resident on the device (to_torch())'.format(scene_id))
+        kw.setdefault('band', self.initial_value)
+        fresh = self.colors.get(scene_id) is None
+        vol = color.new_volume(tsdf.shape, tsdf.device) if fresh else self.colors[scene_id]
+
+        def dev(x):
+            return None if x is None else torch.as_tensor(x).to(tsdf.device)
+        color.integrate_color(vol, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]), image=dev(image),
+                              depth=dev(depth), intrinsics=intrinsics, extrinsics=extrinsics, mask=dev(mask), **kw)
+        self.colors[scene_id] = vol  # (a refused call leaves a scene without a colour volume without one)
+
     def save_to_workspace(self, workspace, mode, save_mode='ply'):
         """database.py:141-177: every scene that holds integrated frames goes to the workspace's output directory as
         ``<scene>.tsdf_<mode>.hf5`` / ``.weights_<mode>.hf5`` / ``.semantic_<mode>.hf5`` ('tsdf'), ``<scene>_<mode>.ply``
@@ -323,7 +380,8 @@ class Database(torch.utils.data.Dataset):
 
     def save(self, path, save_mode='ply', scene_id=None, palette=None):
         """database.py:172-261: 'tsdf' (volumes), 'ply' (mesh), 'test' (volumes + mesh + label-coloured mesh whose
-        alpha channel carries the label id)."""
+        alpha channel carries the label id).  A scene with a colour volume also gets ``<scene>_color.ply`` (the mesh with
+        its sampled vertex colours, alpha 255 where coloured) beside every mesh and ``<scene>.color.hf5`` beside the volumes."""
         if scene_id is None:
             raise NotImplementedError
         if save_mode not in ('tsdf', 'ply', 'test'):
@@ -340,6 +398,9 @@ class Database(torch.utils.data.Dataset):
                 table = np.array(mesh.default_palette() if palette is None else palette, dtype=np.uint8)
                 rgba = np.concatenate([table[m['labels']], m['labels'][:, None]], axis=1)
                 mesh.save_ply(os.path.join(path, base + '_semantic.ply'), m['vertices'], m['faces'], m['normals'], rgba)
+            if self.colors.get(scene_id) is not None:
+                mesh.save_ply(os.path.join(path, base + '_color.ply'), m['vertices'], m['faces'], m['normals'],
+                              self._vertex_colors(scene_id, m['vertices'], 'save'))
             if save_mode == 'ply':
                 return
 
@@ -349,6 +410,8 @@ class Database(torch.utils.data.Dataset):
                   'weights': ('weights', host(self.fusion_weights[scene_id]))}
         if self.semantics:
             arrays['semantics'] = ('semantics', host(self.ids_est[scene_id].volume))
+        if self.colors.get(scene_id) is not None:
+            arrays['color'] = ('color', host(self.colors[scene_id]))
         from .datasets import save_volume_hdf
         for name, (key, arr) in arrays.items():  # same file / dataset names as database.py:184-201 (npz without h5py)
             save_volume_hdf(os.path.join(path, '{}.{}.hf5'.format(base, name)), key, arr)

@@ -322,6 +322,7 @@ class Pipeline(torch.nn.Module):
         recover = self._guard_policy() == 'f32'
         for b, sem in zip(batches, sems):
             self._fuse_guarded(b, database, sem, fp, recover)
+            self._fuse_colors([b], database)
 
     def _fuse_guarded(self, batch, database, sem=None, fingerprint=None, recover=False):
         """One frame step of fuse_sequence / fuse_many's sequential paths under FUSION_MODEL.guard_policy (what ``fuse`` does
@@ -624,7 +625,29 @@ class Pipeline(torch.nn.Module):
             return self._fuse_classical([batch], [None], database)
         # (a frame the forward call's poll refuses was raised BEFORE its net / integrate were enqueued: it is not among the
         # skipped ones, it follows them - _fuse_guarded)
-        return self._fuse_guarded(batch, database, recover=self._guard_policy() == 'f32')
+        self._fuse_guarded(batch, database, recover=self._guard_policy() == 'f32')
+        self._fuse_colors([batch], database)
+
+    # ---- FUSION_MODEL.fuse_color: the frames' colour images into the scenes' colour volumes (color.py) -----------------------
+    def _color_options(self):
+        """None (FUSION_MODEL.fuse_color off, the default) or the keywords of Database.integrate_color: color_band (default
+        DATA.init_value)."""
+        fm = self.config.FUSION_MODEL
+        if not fm.get('fuse_color', False):
+            return None
+        return dict(band=fm.get('color_band', None) or self.config.DATA.init_value)
+
+    def _fuse_colors(self, batches, database):
+        """The learned modes' colour step: ``batch['image']`` of every frame, in order, into its scene's colour volume with the
+        depth frame, mask and pose its frame step used, on the current stream.  Called once per frame the caller has fused
+        (a frame the range guard made the pipeline fuse again is not coloured again).  Geometry and labels are not touched."""
+        kw = self._color_options()
+        if kw is None:
+            return
+        for b in batches:
+            frame, mask = self._frames(b, filtered=False)
+            database.integrate_color(b['frame_id'][0].split('/')[0], b['image'].to(self.device), frame.unsqueeze(0),
+                                     b['intrinsics'][0], b['extrinsics'][0], mask=mask.unsqueeze(0), **kw)
 
     def _fuse_frame(self, batch, database, slot=0, semantics=None, fingerprint=None):
         """One frame step on the current stream with the device state of ``slot``; ``semantics`` = (sem_ids, scores) computed
@@ -674,13 +697,15 @@ class Pipeline(torch.nn.Module):
         ``_fuse_frame`` takes, runs of consecutive frames of one scene and one image shape as ONE kernel call of up to
         ``_lib.PROJECTIVE_MAX_VIEWS`` views (the same bits as a call per frame), and the same side effects on ``database``.
         ``sems[i]``: the frame's (sem_ids, scores) from a batched 2-D pass, or None.  FUSION_MODEL keys: truncation
-        (default DATA.init_value), max_weight (128), carve (False)."""
+        (default DATA.init_value), max_weight (128), carve (False); with fuse_color, the images of a run go into the scene's
+        colour volume as one call as well."""
         from . import projective
         fm = self.config.FUSION_MODEL
         kw = dict(truncation=fm.get('truncation', None) or self.config.DATA.init_value,
                   max_weight=fm.get('max_weight', 128.0), carve=bool(fm.get('carve', False)))
         self._refuse_tripped_guard('Pipeline.fuse')  # (the labels of a 2-D pass that tripped the guard must not reach a volume)
         sem = bool(self.config.DATA.semantics)
+        color_kw = self._color_options()
         run, run_key = [], None
 
         def flush():
@@ -696,6 +721,10 @@ class Pipeline(torch.nn.Module):
                 labels=torch.stack([r[4] for r in run]) if sem else None,
                 label_scores=torch.stack([r[5] for r in run]) if sem else None, **kw)
             self._commit_frame(database, scene_id, volume)
+            if color_kw is not None:
+                database.integrate_color(scene_id, torch.cat([r[6] for r in run]), torch.stack([r[0] for r in run]),
+                                         torch.stack([r[2] for r in run]), torch.stack([r[3] for r in run]),
+                                         mask=torch.stack([r[1] for r in run]), **color_kw)
             del run[:]
 
         for b, s in zip(batches, sems):
@@ -706,7 +735,8 @@ class Pipeline(torch.nn.Module):
                 flush()
                 run_key = key
             E = torch.as_tensor(b['extrinsics'][0]).detach().cpu().to(torch.float64)
-            run.append((frame, mask, torch.as_tensor(b['intrinsics'][0]).detach().cpu().to(torch.float64), E[:3], sem_ids, scores))
+            run.append((frame, mask, torch.as_tensor(b['intrinsics'][0]).detach().cpu().to(torch.float64), E[:3], sem_ids, scores,
+                        b['image'].to(self.device) if color_kw is not None else None))
             self._frames_fused += 1
         flush()
 
@@ -720,7 +750,13 @@ class Pipeline(torch.nn.Module):
         latency-bound chains of 600-block kernels, and several of them fill the chip better (the two heads of a semantic net
         already run this way).  With ``semantic_strategy: predict`` the 2-D network of the S frames runs first, on the current
         stream (one engine).  The reference has no counterpart: its drivers fuse one frame at a time
-        (test_fusion.py:68-80)."""
+        (test_fusion.py:68-80).  With FUSION_MODEL.fuse_color the frames' colour calls follow on the current stream, after the
+        join."""
+        self._fuse_many_frames(batches, database, device)
+        if not self._classical:  # (the classical frame steps bring their colour calls along)
+            self._fuse_colors(batches, database)
+
+    def _fuse_many_frames(self, batches, database, device):
         self.device = torch.device(device)
         ids = [b['frame_id'][0].split('/')[0] for b in batches]
         if len(set(ids)) != len(ids):
@@ -736,7 +772,7 @@ class Pipeline(torch.nn.Module):
             return
         if len(batches) > _lib.MAX_SCENES:  # (the launches take up to MAX_SCENES scenes: larger calls go in groups)
             for i in range(0, len(batches), _lib.MAX_SCENES):
-                self.fuse_many(batches[i:i + _lib.MAX_SCENES], database, device)
+                self._fuse_many_frames(batches[i:i + _lib.MAX_SCENES], database, device)
             return
         main = torch.cuda.current_stream(self.device)
         sems = self._frame_semantics_many(batches)  # (None, None) without semantics; predict: ONE batched pass, this stream
