@@ -463,7 +463,9 @@ int ojf_integrate_many(int n, const ojf_integrate_job *jobs, int n_points, int n
  * ojf_seg_maxpool: nn.MaxPool2d(3, 2, 1) of the ResNet stem (modules/adapnet.py:101, torchvision layout).
  * ojf_seg_mean: mean over the pixels per channel (eASPP branch 5 :204-208, Decoder._skip :292-296) -> out[c].
  * ojf_seg_broadcast: out[p][c] = vec[c] (* mul[p][c]): the bilinear upsampling of a 1x1 map / the gated skip.
- * ojf_seg_softmax_max: pipeline.py:57,183 softmax over the classes then max: scores f32[npix], ids u8[npix].
+ * ojf_seg_softmax_max: pipeline.py:57,183 softmax over the classes then max: scores f32[npix], ids u8[npix]; the id is the
+ *   first maximum.  A row that holds a NaN or a +Inf, or only -Inf, is all-NaN after the reference's softmax, whose max is
+ *   then its first element: score NaN, id 0 (not the index of the NaN / +Inf).
  * ojf_seg_pool_fc: the squeeze chains of eASPP branch 5 (adapnet.py:204-210) and Decoder._skip (:292-296) as two launches
  *   for n (1..8) members: out_m[p][c] = act(bias[c] + sum_k W[c][k] * mean_p' in_m[p'][k]) (* mul_m[p][c]) for every pixel p
  *   of the OUTPUT map - global average (two fixed-order stages), a 1x1 convolution on the 1x1 map in fp32 (W_dev [c_out][c_in],
@@ -486,7 +488,10 @@ int ojf_seg_softmax_max(const float *logits_dev, int stride, int n_classes, int 
 
 /* ---- VOLUME HELPERS (Database) -------------------------------------------------------------
  * ojf_volume_fill_*: Database.reset (modules/database.py:351-370).
- * ojf_volume_filter: Database.filter (:108-112): where weights < value: tsdf = init_value, weights = 0.
+ * ojf_volume_filter: Database.filter (:108-112): where weights < value: tsdf = init_value, weights = 0.  The reference
+ *   compares its fp16 weights with a Python float, which numpy and torch do in fp16: the test is weights < float16(value).
+ *   The call rounds ``threshold`` to fp16 (nearest even) once on the host, so float16(0.1) = 0.0999755859375 is kept by
+ *   threshold 0.1 on the device exactly as on the host.
  * ojf_volume_evaluate: utils/metrics.py:111-127 evaluation() on device: with mask = weights > 0 and
  *   est/gt clipped to +-0.04, sums_dev f64[8] receives {n_mask, sum_sq_err, sum_abs_err,
  *   n_intersection(est<0 & gt<0), n_union(est<0 | gt<0), n_sign_equal, 0, 0}.

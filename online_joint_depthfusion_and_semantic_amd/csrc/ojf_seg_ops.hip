@@ -103,6 +103,8 @@ __global__ __launch_bounds__(256) void seg_broadcast_kernel(const float *vec, co
 }
 
 // torch.softmax(logits, dim=1).max(dim=1): score = exp(l_max - l_max) / sum_j exp(l_j - l_max), id = first arg max.
+// A row that holds a NaN or a +Inf (inf - inf), or nothing but -Inf, is all-NaN after torch.softmax, and torch.max of an
+// all-NaN row is (NaN, 0) - its first element: such a row yields score NaN and id 0, wherever its NaN / +Inf sits.
 // VEC: rows are 16-byte aligned - a lane fetches its pixel's classes as float4 (the scalar form issued C 4-byte loads per
 // lane, each spread over 64 cache lines: 20 us for a 320x240 frame with 30 classes; same operations in the same order).
 template <bool VEC>
@@ -125,22 +127,23 @@ __global__ __launch_bounds__(256) void seg_softmax_max_kernel(const float *logit
     auto at = [&](int c) { if constexpr (VEC) return v[c]; else return l[c]; };
     float m = at(0);
     int am = 0;
-    bool nan = m != m;
+    bool bad = m != m;  // the softmax of this row is all-NaN
     if constexpr (VEC) {
 #pragma unroll
         for (int c = 1; c < kMaxVec; ++c)
             if (c < C) {
                 const float x = v[c];
-                if (x != x && !nan) { nan = true; am = c; }  // torch.max returns the first NaN
-                if (!nan && x > m) { m = x; am = c; }
+                bad |= x != x;
+                if (x > m) { m = x; am = c; }
             }
     } else {
         for (int c = 1; c < C; ++c) {
             const float x = l[c];
-            if (x != x && !nan) { nan = true; am = c; }
-            if (!nan && x > m) { m = x; am = c; }
+            bad |= x != x;
+            if (x > m) { m = x; am = c; }
         }
     }
+    bad |= m == INFINITY || m == -INFINITY;  // a +Inf among the logits / only -Inf: l - m is inf - inf
     float s = 0.0f;
     if constexpr (VEC) {
 #pragma unroll
@@ -149,8 +152,8 @@ __global__ __launch_bounds__(256) void seg_softmax_max_kernel(const float *logit
     } else {
         for (int c = 0; c < C; ++c) s += expf(l[c] - m);
     }
-    scores[p] = nan ? __builtin_nanf("") : 1.0f / s;
-    ids[p] = (uint8_t)am;
+    scores[p] = bad ? __builtin_nanf("") : 1.0f / s;
+    ids[p] = bad ? (uint8_t)0 : (uint8_t)am;
 }
 
 // ---- squeeze chains: global average -> 1x1 convolution on the 1x1 map -> broadcast (x gate) ------------------------------

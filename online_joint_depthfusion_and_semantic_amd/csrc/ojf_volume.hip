@@ -31,7 +31,8 @@ __global__ __launch_bounds__(256) void fill_u16_kernel(uint16_t *v, size_t n, ui
 __global__ __launch_bounds__(256) void filter_kernel(uint16_t *tsdf, uint16_t *wgt, size_t n, float thr,
                                                       uint16_t init_bits)
 {
-    // Database.filter: volume[weights < value] = init ; weights[weights < value] = 0
+    // Database.filter: volume[weights < value] = init ; weights[weights < value] = 0.  The reference compares its fp16
+    // weights with float16(value): thr arrives rounded to fp16, and two fp16 values compare exactly in fp32.
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t step = (size_t)gridDim.x * blockDim.x;
     for (size_t i = tid; i < n; i += step) {
@@ -228,8 +229,9 @@ OJF_API int ojf_volume_filter(uint16_t *tsdf, uint16_t *wgt, size_t n, float thr
     const _Float16 hv = (_Float16)init_value;
     uint16_t bits;
     __builtin_memcpy(&bits, &hv, 2);
+    const float thr16 = (float)(_Float16)threshold;  // (numpy and torch compare an fp16 array with float16(value))
     hipLaunchKernelGGL(filter_kernel, dim3(stream_grid(n)), dim3(256), 0, as_stream(stream), tsdf, wgt, n,
-                       threshold, bits);
+                       thr16, bits);
     return check_hip(hipGetLastError(), "ojf_volume_filter launch");
 }
 

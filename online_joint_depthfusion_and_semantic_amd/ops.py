@@ -283,10 +283,13 @@ def volume_fill(vol, value):
 
 
 def volume_filter(tsdf, weights, threshold, init_value):
+    """Database.filter: where weights < float16(threshold) (the reference's fp16 comparison, include/ojf.h)."""
     _lib.require_gpu()
     lib = _lib.load()
+    with np.errstate(over='ignore'):
+        thr = float(np.float16(threshold))  # straight from the double: through the ABI's float it could round twice
     rc = lib.ojf_volume_filter(_lib.ptr(_vol16(tsdf)), _lib.ptr(_vol16(weights)), tsdf.numel(),
-                               float(threshold), float(init_value), _lib.stream_ptr(tsdf.device))
+                               thr, float(init_value), _lib.stream_ptr(tsdf.device))
     _lib.check(rc, 'ojf_volume_filter')
 
 
