@@ -107,6 +107,65 @@ def run_extract_integrate(h, w, grid, frames, keep_arrays):
     return out
 
 
+def save_npz_lzma(path, arrays):
+    """np.savez_compressed with LZMA members (numpy.load reads them like deflated ones): the box fixture's four volumes
+    per frame are five times the cube fixture's, and with deflate the file would outgrow it."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, 'w', compression=zipfile.ZIP_LZMA) as z:
+        for k, v in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+            z.writestr(k + '.npy', buf.getvalue())
+
+
+def run_extract_integrate_box(h=13, w=15, frames=(0, 3)):
+    """run_extract_integrate on the non-cubic boxes of tests/box_cases.py (shape, origin and resolution from BOXES):
+    the reference's Extractor + Integrator with state carried over ``frames`` of each box, every array kept under
+    '<box>_f<frame>_<key>'."""
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    from box_cases import BOXES, box
+    cfg = ref_config(h, w, True, False)
+    ex, ig = Extractor(cfg), Integrator(cfg)
+    st = SyntheticStream(h, w, 64, 20)
+    out = {}
+    for name in sorted(BOXES):
+        org, res, shape = box(name)
+        tsdf = torch.full(shape, 0.1, dtype=torch.float16)
+        wgt = torch.zeros(shape, dtype=torch.float16)
+        ids = torch.zeros(shape, dtype=torch.uint8)
+        sc = torch.zeros(shape, dtype=torch.float16)
+        origin = torch.from_numpy(org)
+        for k, i in enumerate(frames):
+            b = st.batch(i)
+            depth = b['tof_depth']
+            if k == 1:  # zero-depth pixels that are NOT masked out by noise alone
+                depth[0, ::5, ::3] = 0.0
+                b['mask'] = (depth > 0.05) & (depth < 5.0)
+            values = ex.forward(depth, b['extrinsics'], b['intrinsics'], tsdf, wgt, origin, res)
+            rng = np.random.default_rng([7, i])
+            est = torch.from_numpy(rng.uniform(-0.15, 0.15, (1, h * w, 9)).astype(np.float32))
+            fd = torch.where(b['mask'], depth, torch.zeros_like(depth)).view(1, h * w, 1)
+            valid = (fd != 0.).nonzero()[:, 1]
+            rep = lambda t: t.view(1, h * w, 1).unsqueeze(-2).repeat(1, 1, 9, 1)[:, valid, :7]
+            updates = dict(values=torch.clamp(est[:, valid, :7], -0.1, 0.1), indices=values['indices'][:, valid, :7],
+                           weights=values['weights'][:, valid, :7], semantics=rep(b['semantic_gt']),
+                           scores=rep(b['semantic_scores']))
+            tsdf, wgt, ids, sc = ig.forward(updates, tsdf, wgt, sc, ids)
+            idx = values['indices'][0].numpy()
+            assert np.abs(idx).max() < 2 ** 15
+            rec = dict(depth=depth[0].numpy(), mask=b['mask'][0].numpy(), extrinsics=b['extrinsics'][0].numpy(),
+                       intrinsics=b['intrinsics'][0].numpy(), est=est[0].numpy(), sem_ids=b['semantic_gt'][0].numpy(),
+                       sem_scores=b['semantic_scores'][0].numpy(),
+                       fusion_values=values['fusion_values'][0].numpy(), fusion_weights=values['fusion_weights'][0].numpy(),
+                       indices=idx.astype(np.int16), weights=values['weights'][0].numpy(),
+                       points=values['points'][0].numpy(), pcl=values['pcl'][0].numpy(),
+                       tsdf=tsdf.numpy().copy(), wgt=wgt.numpy().copy(), ids=ids.numpy().copy(), scores=sc.numpy().copy())
+            for key, v in rec.items():
+                out['%s_f%d_%s' % (name, i, key)] = v
+    return out
+
+
 class DuckDatabase:
     """The five dict attributes + __getitem__ the reference Pipeline touches."""
 
@@ -440,6 +499,9 @@ def full_size():
 def main():
     if '--probe-matmul' in sys.argv:
         print(probe_matmul())
+        return
+    if '--box' in sys.argv:  # only the non-cubic-box fixture of the extract / integrate path
+        save_npz_lzma(os.path.join(HERE, 'extract_integrate_box_13x15.npz'), run_extract_integrate_box())
         return
     if '--full-size' in sys.argv:  # only the 320x240 -> 256^3 pipeline fixtures
         full_size()

@@ -34,10 +34,12 @@ def f16_ulp_distance(a, b):
 
 
 def fresh_volumes(grid, semantics=True, init=0.1):
-    vols = dict(tsdf=np.full((grid,) * 3, init, np.float16), wgt=np.zeros((grid,) * 3, np.float16))
+    """``grid``: the edge of a cube, or an (X, Y, Z) shape."""
+    shape = (grid,) * 3 if isinstance(grid, (int, np.integer)) else tuple(int(n) for n in grid)
+    vols = dict(tsdf=np.full(shape, init, np.float16), wgt=np.zeros(shape, np.float16))
     if semantics:
-        vols['ids'] = np.zeros((grid,) * 3, np.uint8)
-        vols['scores'] = np.zeros((grid,) * 3, np.float16)
+        vols['ids'] = np.zeros(shape, np.uint8)
+        vols['scores'] = np.zeros(shape, np.float16)
     return vols
 
 

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle
-from helpers import n_mismatch, golden, net_from_golden, oracle_net_est, oracle_fuse, fresh_volumes, make_stream
+from helpers import NS, n_mismatch, golden, net_from_golden, oracle_net_est, oracle_fuse, fresh_volumes, make_stream
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -17,11 +17,15 @@ def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
-def _replay(h, w, grid, frames, get):
-    """Replays the generator's stream through the oracle; ``get(i, key)`` returns golden inputs."""
+def _replay(h, w, grid, frames, get, origin=None, resolution=None):
+    """Replays the generator's stream through the oracle; ``get(i, key)`` returns golden inputs.  ``grid``: the edge of
+    the stream's cube, or an (X, Y, Z) shape together with its origin and resolution; ``frames``: a count or the ids."""
     vols = fresh_volumes(grid, True)
-    st = make_stream(h, w, grid)
-    for i in range(frames):
+    if origin is None:
+        st = make_stream(h, w, grid)
+    else:
+        st = NS(origin=np.asarray(origin, np.float64), resolution=resolution)
+    for i in (range(frames) if isinstance(frames, int) else frames):
         depth, mask = get(i, 'depth'), get(i, 'mask')
         Ki, E = oracle.camera_arrays(get(i, 'intrinsics'), get(i, 'extrinsics'))
         ex = oracle.extract(depth, Ki, E, st.origin, st.resolution, vols['tsdf'], vols['wgt'], debug=True)
@@ -40,6 +44,27 @@ def test_oracle_matches_reference_arrays_tiny():
         assert n_mismatch(ex['indices'], g['f%d_indices' % i].astype(np.int64)) == 0, i
         for key in ('tsdf', 'wgt', 'ids', 'scores'):
             assert n_mismatch(vols[key], g['f%d_%s' % (i, key)]) == 0, (key, i)
+
+
+@pytest.mark.parametrize('name', ['room', 'slab'])
+def test_oracle_matches_reference_arrays_on_a_box(name):
+    """The reference's Extractor + Integrator on the non-cubic boxes of box_cases.py (extents and origin components all
+    different; 13x15 frames 0 and 3, state carried): every stored array bit for bit, as on the cube."""
+    from box_cases import BOXES, box
+    g = golden('extract_integrate_box_13x15.npz')
+    origin, res, shape = box(name)
+    assert len(set(shape)) == 3 and len(set(BOXES[name]['origin'])) == 3
+    seen = 0
+    for i, ex, vols in _replay(13, 15, shape, (0, 3), lambda i, k: g['%s_f%d_%s' % (name, i, k)], origin, res):
+        for key in ('fusion_values', 'fusion_weights', 'weights', 'points', 'pcl'):
+            assert n_mismatch(ex[key], g['%s_f%d_%s' % (name, i, key)]) == 0, (key, i)
+        assert g['%s_f%d_indices' % (name, i)].dtype == np.int16
+        assert n_mismatch(ex['indices'], g['%s_f%d_indices' % (name, i)].astype(np.int64)) == 0, i
+        for key in ('tsdf', 'wgt', 'ids', 'scores'):
+            assert vols[key].shape == shape
+            assert n_mismatch(vols[key], g['%s_f%d_%s' % (name, i, key)]) == 0, (key, i)
+        seen += 1
+    assert seen == 2 and int((vols['wgt'] > 0).sum()) >= 1000
 
 
 @pytest.mark.parametrize('name,h,w,grid,frames', [('A_120x160_g64', 120, 160, 64, 3), ('B_240x320_g256', 240, 320, 256, 2)])

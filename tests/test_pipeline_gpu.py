@@ -156,6 +156,88 @@ def test_stream_config_A_against_oracle(cuda, sem):
     assert torch.all(db.scenes_est[s].volume == torch.tensor(0.1, dtype=torch.float16))
 
 
+@pytest.mark.parametrize('sem', [False, True])
+def test_stream_on_a_box_against_oracle(cuda, sem):
+    """test_stream_config_A_against_oracle on a NON-CUBIC volume whose origin components all differ (box_cases.py ``room``,
+    66 x 62 x 37, 45x52 frames 0, 3, 7, 12): Database takes the shape from the dataset's grid, Pipeline.fuse, evaluate, the
+    F-score, filter, reset and render run on it.  The bars are the cube test's."""
+    import copy
+    from box_cases import BOXES, BoxStream
+    from online_joint_depthfusion_and_semantic_amd.render import render_views
+    h, w = 45, 52
+    cfg = default_config(h, w, semantics=sem, use_semantics=sem, integrate_mode='fast')
+    cfg.SETTINGS.device = str(cuda)
+    st = BoxStream('room', h, w)
+    db = Database(st, database_config(cfg))
+    s = st.scene
+    assert tuple(db.scenes_est[s].volume.shape) == st.shape == tuple(db.scenes_gt[s].volume.shape)
+    assert np.array_equal(np.asarray(db.origin[s]), st.origin) and db.resolution[s] == st.resolution
+    pipe = Pipeline(cfg)
+    torch.manual_seed(5)
+    for m in pipe._fusion_network.modules():
+        if isinstance(m, torch.nn.Conv2d):
+            torch.nn.init.xavier_normal_(m.weight)
+        if isinstance(m, torch.nn.BatchNorm2d):
+            m.running_mean.normal_(0, 0.1)
+            m.running_var.uniform_(0.5, 1.5)
+    pipe = pipe.to(cuda).eval()
+    cpu_net = copy.deepcopy(pipe._fusion_network).cpu().eval()
+    vols = fresh_volumes(st.shape, True)
+    with torch.no_grad():
+        for i in BOXES['room']['frames']:
+            pipe.fuse(_batch(st, i, cuda), db, cuda)
+            oracle_fuse(st, i, vols, cpu_net, sem)
+    got_t, got_w = db.scenes_est[s].volume.cpu().numpy(), db.fusion_weights[s].cpu().numpy()
+    wd = f16_ulp_distance(got_w, vols['wgt'])
+    assert wd.max() <= 1
+    nan = np.isnan(got_t) | np.isnan(vols['tsdf'])
+    assert (np.isnan(got_t) == np.isnan(vols['tsdf'])).all()
+    td = np.where(nan, 0, np.abs(got_t.astype(np.float32) - vols['tsdf'].astype(np.float32)))
+    touched = vols['wgt'] > 0
+    print('box stream sem=%s: %d touched, %d weight ulps, TSDF p99 %.2e max %.2e' % (
+        sem, int(touched.sum()), int((wd > 0).sum()), float(np.percentile(td[touched], 99)), float(td.max())))
+    assert touched.sum() > 20000
+    assert np.percentile(td[touched], 99) <= 6.2e-5 and td.max() <= 2 * TSDF_ABS_TOL, float(td.max())
+    if sem:
+        assert n_mismatch(db.ids_est[s].volume.cpu().numpy(), vols['ids']) == 0
+        assert n_mismatch(db.scores[s].volume.cpu().numpy(), vols['scores']) == 0
+    gt = db.scenes_gt[s].volume.cpu().numpy()
+    have = db.evaluate(mode='val')
+    same = metrics.evaluation(got_t, gt, got_w > 0)
+    for k in same:
+        assert abs(same[k] - have[k]) <= 1e-6 * max(1.0, abs(same[k])), (k, same[k], have[k])
+    want = metrics.evaluation(vols['tsdf'], gt, vols['wgt'] > 0)
+    for k in want:
+        assert abs(want[k] - have[k]) <= 1e-3 * max(1.0, abs(want[k])), (k, want[k], have[k])
+    f_have = metrics.reconstruction_f_score(got_t, gt, got_w, st.origin, st.resolution)
+    f_want = metrics.reconstruction_f_score(vols['tsdf'], gt, vols['wgt'], st.origin, st.resolution)
+    assert abs(f_have['fscore'] - f_want['fscore']) <= 1e-3 and f_want['fscore'] > 0.05, (f_have, f_want)
+    f_dev = metrics.reconstruction_f_score(db.scenes_est[s].volume, db.scenes_gt[s].volume, db.fusion_weights[s],
+                                           st.origin, st.resolution)  # volumes on the device -> ojf_points_within
+    assert f_dev == f_have, (f_dev, f_have)
+    # Database.render == render_views on the same volumes, from a fused pose
+    f = st.batch(3)
+    direct = render_views(db.scenes_est[s].volume, db.fusion_weights[s], db.ids_est[s].volume if sem else None,
+                          origin=db.origin[s], resolution=db.resolution[s], intrinsics=f['intrinsics'],
+                          extrinsics=f['extrinsics'], shape=(h, w))
+    shown = db.render(s, f['intrinsics'], f['extrinsics'], (h, w), semantics=sem)
+    for k in ('depth', 'normals') + (('labels',) if sem else ()):
+        assert torch.equal(shown[k].view(torch.uint8), direct[k].view(torch.uint8)), k
+    assert float((direct['depth'] > 0).float().mean()) > 0.3
+    # filter (outlier removal) on device == numpy semantics
+    db.filter(value=2.0)
+    low = vols['wgt'] < np.float16(2.0)
+    vols['tsdf'][low] = np.float16(0.1)
+    vols['wgt'][low] = 0
+    assert 0 < low.sum() < low.size and (vols['wgt'] > 0).any()
+    assert f16_ulp_distance(db.fusion_weights[s].cpu().numpy(), vols['wgt']).max() <= 1
+    assert (db.scenes_est[s].volume.cpu().numpy()[low] == np.float16(0.1)).all()
+    db.reset(s)
+    assert float(db.fusion_weights[s].float().abs().sum()) == 0 and db.state[s] is False
+    assert torch.all(db.scenes_est[s].volume == torch.tensor(0.1, dtype=torch.float16))
+    assert tuple(db.scenes_est[s].volume.shape) == st.shape
+
+
 def test_fuse_with_predicted_semantics(cuda):
     """semantic_strategy 'predict': AdapNet++ (torch ops on the GPU) -> softmax -> (score, id) per pixel
     (pipeline.py:42-60,181-185) feeding the HIP semantic volume update."""
