@@ -652,6 +652,39 @@ int ojf_color_render(const uint16_t *color_dev, int X, int Y, int Z, const doubl
                      const float *Kinv_host, const float *E_host, const float *depth_dev, int h, int w,
                      uint8_t *rgba_dev /* u8[n,h,w,4] */, ojf_stream_t stream);
 
+/* ---- RASTER (depth, face, label and colour images of a triangle mesh; the reference renders with OpenGL) --------------
+ * ojf_rasterize: n views (1 <= n <= OJF_RASTER_MAX_VIEWS, one h x w for all) of the mesh vertices_dev f32[nv][3] (world
+ *   frame) / faces_dev i32[nf][3].  K_host f64[n][9] pinhole intrinsics, E_host f64[n][12] camera-to-world, as for
+ *   ojf_fuse_projective; pixel (r, c) has its centre at integer coordinates.  Homogeneous two-sided rasterisation (no
+ *   culling, no near-plane clipping: triangles that cross the camera plane come out right): a pixel's ray (rx, ry, 1) hits
+ *   a triangle with camera points a, b, c when the edge values e_i = n_i . ray (n0 = b x c, n1 = c x a, n2 = a x b) are all
+ *   >= 0 or all <= 0, S = e0 + e1 + e2 != 0 and z = det / S (det = a . n0) is finite and > near.  The pixel keeps the minimum
+ *   of (bits(z) << 32) | face index: the nearest hit, ties to the lower face index.  depth_dev f32[n,h,w]: camera z-depth,
+ *   0 where nothing is hit; face_dev i32[n,h,w]: the face, -1 where nothing is hit.  A face with an index outside [0, nv)
+ *   or a non-finite vertex is skipped.  Edge values of a shared edge negate bit for bit: no holes along shared edges.
+ *   keys_dev: u64[n,h,w] workspace (8-byte aligned; its content on return is unspecified).  near >= 0.  Enqueues a fill,
+ *   one kernel over (view, triangle) that resolves visibility with a 64-bit atomic minimum - order-independent, the same
+ *   bits on every run, and n views in one call give the bits of n calls of one view -, one that spreads the triangles
+ *   with large pixel boxes over many waves (their list is kept in depth_dev / face_dev until these are written) and one
+ *   that writes the images.
+ * ojf_rasterize_attributes: per pixel of face_dev (as ojf_rasterize wrote it, same mesh and views):  labels_dev u8[n,h,w]
+ *   = face_labels_dev u8[nf] of the pixel's face, 0 where nothing is hit (both set or both NULL);  rgba_dev u8[n,h,w,4] =
+ *   the barycentric mean (lambda_i = e_i / S) of vertex_rgba_dev u8[nv][4] over the face's vertices, bytes 0..2 rounded to
+ *   u8, alpha 255, all four bytes 0 where nothing is hit (both set or both NULL; 4-byte aligned).  At least one of the two
+ *   outputs.  A face_dev entry outside [0, nf) counts as "nothing is hit".  One kernel.
+ * Bad arguments (sizes, n*h*w or 3*nf >= 2^31, a non-pinhole K, non-finite K / E / near, near < 0, null required pointers)
+ *   are refused before any HIP call; neither call ever waits.  The exact fp32 operation order is in csrc/ojf_raster.hip. */
+#define OJF_RASTER_MAX_VIEWS 32
+int ojf_rasterize(const float *vertices_dev /* f32[nv][3] */, int nv, const int *faces_dev /* i32[nf][3] */, int nf, int n,
+                  const double *K_host /* f64[n][9] */, const double *E_host /* f64[n][12] */, int h, int w, float near,
+                  uint64_t *keys_dev /* u64[n,h,w] workspace */, float *depth_dev /* f32[n,h,w] */,
+                  int *face_dev /* i32[n,h,w] */, ojf_stream_t stream);
+int ojf_rasterize_attributes(const float *vertices_dev, int nv, const int *faces_dev, int nf, int n, const double *K_host,
+                             const double *E_host, int h, int w, const int *face_dev /* i32[n,h,w] */,
+                             const uint8_t *face_labels_dev /* u8[nf] or NULL */,
+                             const uint8_t *vertex_rgba_dev /* u8[nv][4] or NULL */, uint8_t *labels_dev /* u8[n,h,w] or NULL */,
+                             uint8_t *rgba_dev /* u8[n,h,w,4] or NULL */, ojf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

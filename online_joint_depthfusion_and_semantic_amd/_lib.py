@@ -48,6 +48,7 @@ TRACK_MAX_ITERATIONS = 128  # include/ojf.h OJF_TRACK_MAX_ITERATIONS
 TRACK_TERMS = 29  # include/ojf.h OJF_TRACK_TERMS
 PROJECTIVE_MAX_VIEWS = 32  # include/ojf.h OJF_PROJECTIVE_MAX_VIEWS
 COLOR_MAX_VIEWS = 32  # include/ojf.h OJF_COLOR_MAX_VIEWS
+RASTER_MAX_VIEWS = 32  # include/ojf.h OJF_RASTER_MAX_VIEWS
 
 
 class ExtractJob(ctypes.Structure):
@@ -170,6 +171,10 @@ SIGNATURES = {
     'ojf_color_sample': (_i, [_vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     # colour volume, X, Y, Z, origin, resolution, n, Kinv, E, depth, h, w, rgba, stream
     'ojf_color_render': (_i, [_vp, _i, _i, _i, _vp, _d, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    # vertices, nv, faces, nf, n, K, E, h, w, near, keys, depth, face, stream
+    'ojf_rasterize': (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    # vertices, nv, faces, nf, n, K, E, h, w, face, face labels, vertex rgba, labels, rgba, stream
+    'ojf_rasterize_attributes': (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _LIB = None

@@ -190,9 +190,10 @@ def reconstruction_f_score(est, gt, weights, origin, resolution, tau=None):
     return f_score(surface_points(est, mask, origin, resolution), surface_points(gt, mask, origin, resolution), tau)
 
 
-def save_ply(filename, vertices, faces, normals=None, rgba=None):
+def save_ply(filename, vertices, faces, normals=None, rgba=None, face_labels=None):
     """Binary little-endian PLY with the element/property names trimesh writes (x y z [nx ny nz] [red green blue
-    alpha]; face vertex_indices), so files load wherever the reference's do."""
+    alpha]; face vertex_indices), so files load wherever the reference's do.  face_labels (u8 [F]): one more face
+    property, ``uchar label``, so that a labelled mesh (rasterize.py) fits in one file."""
     vertices = np.asarray(vertices, dtype='<f4')
     faces = np.asarray(faces, dtype='<i4')
     fields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')]
@@ -208,14 +209,18 @@ def save_ply(filename, vertices, faces, normals=None, rgba=None):
     if rgba is not None:
         c = np.asarray(rgba, dtype=np.uint8)
         vrec['red'], vrec['green'], vrec['blue'], vrec['alpha'] = c[:, 0], c[:, 1], c[:, 2], c[:, 3]
-    frec = np.zeros(faces.shape[0], dtype=[('n', 'u1'), ('v', '<i4', (3,))])
+    frec = np.zeros(faces.shape[0], dtype=[('n', 'u1'), ('v', '<i4', (3,))] + ([] if face_labels is None else [('label', 'u1')]))
     frec['n'] = 3
     frec['v'] = faces
+    if face_labels is not None:
+        frec['label'] = np.asarray(face_labels, dtype=np.uint8).reshape(faces.shape[0])
     names = {'<f4': 'float', 'u1': 'uchar'}
     header = ['ply', 'format binary_little_endian 1.0', 'comment ojf_mesh (marching tetrahedra)',
               'element vertex {}'.format(vertices.shape[0])]
     header += ['property {} {}'.format(names[t], n) for n, t in fields]
-    header += ['element face {}'.format(faces.shape[0]), 'property list uchar int vertex_indices', 'end_header']
+    header += ['element face {}'.format(faces.shape[0]), 'property list uchar int vertex_indices']
+    header += ['property uchar label'] if face_labels is not None else []
+    header += ['end_header']
     with open(filename, 'wb') as f:
         f.write(('\n'.join(header) + '\n').encode('ascii'))
         f.write(vrec.tobytes())
@@ -223,10 +228,11 @@ def save_ply(filename, vertices, faces, normals=None, rgba=None):
 
 
 def load_ply(filename):
-    """Reader for the files save_ply writes (tests and downstream tools); returns dict(vertices, faces, normals, rgba)."""
+    """Reader for the files save_ply writes (tests and downstream tools); returns dict(vertices, faces, normals, rgba),
+    and ``face_labels`` (u8 [F]) for a file that carries the per-face ``label`` property."""
     with open(filename, 'rb') as f:
         assert f.readline().strip() == b'ply'
-        fields, n_vert, n_face, element = [], 0, 0, None
+        fields, n_vert, n_face, element, labelled = [], 0, 0, None, False
         while True:
             line = f.readline().decode('ascii').split()
             if line[0] == 'end_header':
@@ -239,12 +245,17 @@ def load_ply(filename):
                     n_face = int(line[2])
             elif line[0] == 'property' and element == 'vertex':
                 fields.append((line[2], {'float': '<f4', 'uchar': 'u1'}[line[1]]))
+            elif line[:3] == ['property', 'uchar', 'label'] and element == 'face':
+                labelled = True
         vrec = np.frombuffer(f.read(np.dtype(fields).itemsize * n_vert), dtype=fields)
-        frec = np.frombuffer(f.read(13 * n_face), dtype=[('n', 'u1'), ('v', '<i4', (3,))])
+        ftype = np.dtype([('n', 'u1'), ('v', '<i4', (3,))] + ([('label', 'u1')] if labelled else []))
+        frec = np.frombuffer(f.read(ftype.itemsize * n_face), dtype=ftype)
     out = {'vertices': np.stack([vrec['x'], vrec['y'], vrec['z']], axis=1), 'faces': frec['v'].copy(), 'normals': None,
            'rgba': None}
     if 'nx' in vrec.dtype.names:
         out['normals'] = np.stack([vrec['nx'], vrec['ny'], vrec['nz']], axis=1)
     if 'alpha' in vrec.dtype.names:
         out['rgba'] = np.stack([vrec['red'], vrec['green'], vrec['blue'], vrec['alpha']], axis=1)
+    if labelled:
+        out['face_labels'] = frec['label'].copy()
     return out
