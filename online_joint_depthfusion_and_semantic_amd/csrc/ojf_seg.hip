@@ -10,11 +10,11 @@
 // ojf_net.hip: x*w = wl*xh + wh*xl + wh*xh, fp32 accumulate, rows equilibrated by a power of two).  A lane's
 // accumulator holds 4 consecutive output channels of one pixel: one 16-byte NHWC store.
 //
-// Three shapes of the same loop (ojf_segconv_forward picks by the size of the layer):
+// Two shapes of the same loop (ojf_segconv_forward picks by the size of the layer; layers that tile both ways take
+// segconv_gemm_kernel further down):
 //   * many independent waves: a wave owns 64 output channels x 32 pixels, 4 waves per block over (channels x pixels);
 //   * few pixels (15x20 .. 60x80 maps): the 4 waves of a block share one (channels, pixels) pair and split K four
-//     ways (LDS reduction in fixed order); 16 / 32 / 64 channels per block so that at least ~150 blocks exist;
-//   * many pixels (>= 256 blocks of 64 channels x 128 pixels): segconv_wide_kernel, weights through LDS (LDS-DMA).
+//     ways (LDS reduction in fixed order); 16 / 32 / 64 channels per block so that at least ~150 blocks exist.
 // Operands come straight from global memory through L1 (buffer loads; out-of-image taps are out-of-range offsets that
 // return zeros), three K blocks in flight per wave in a branch-free loop.  Channel slices of a wider tensor
 // (concatenations) are addressed by pointer + row stride.  Transposed convolutions: see ojf_segdeconv_create.
@@ -199,11 +199,13 @@ __device__ __forceinline__ void seg_epilogue_px(const SegArgs &a, const f32x4 (&
         const f32x4 rv = rvs[m], bv = bvs[m];
         // transposed convolution: GEMM row c = (phase, channel); phase (ay, ax) of input pixel (y, x) is output pixel
         // (y*up + ay, x*up + ax).  up_cp is a multiple of 4, so a lane's four rows share the phase.
-        int co = c, n_co = a.c_out, ay = 0, ax = 0;
+        // n_st: channels of the output row this launch may write (pad_to >= c_out; a transposed convolution owns its up_c real
+        // channels only - pad_to counts GEMM rows there, and the padded rows of a phase belong to whoever follows in the row)
+        int co = c, n_co = a.c_out, n_st = a.pad_to, ay = 0, ax = 0;
         if (a.up > 1) {
             const int phase = c / a.up_cp;
             co = c - phase * a.up_cp;
-            n_co = a.up_c;
+            n_co = n_st = a.up_c;
             ay = phase / a.up;
             ax = phase - ay * a.up;
             if (co >= n_co) continue;
@@ -270,12 +272,12 @@ __device__ __forceinline__ void seg_epilogue_px(const SegArgs &a, const f32x4 (&
                 row = (size_t)b * a.Ho * a.Wo * a.up * a.up + ((size_t)oy * a.up + ay) * ((size_t)a.Wo * a.up) + (size_t)ox * a.up + ax;
             }
             float *o = a.out + row * a.out_stride + co;
-            if ((full || co + 3 < a.pad_to) && (a.vec_store & 1)) {
+            if (co + 3 < n_st && (a.vec_store & 1)) {
                 *reinterpret_cast<f32x4 *>(o) = v;
             } else {
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
-                    if (co + i < n_co || co + i < a.pad_to) o[i] = v[i];
+                    if (co + i < n_st) o[i] = v[i];
             }
         }
     }
@@ -415,117 +417,6 @@ __global__ __launch_bounds__(KS > 4 ? 64 * KS : 256) void segconv_kernel(const S
     }
 
     seg_epilogue<MW, NW, DROP>(a, acc, ct0, pt0, n_pix, col, kg, rvs, bvs);
-}
-
-// Many-pixel layers (decoder 3x3 stacks, layer1): the four waves of a block work on the SAME 64 output channels and
-// 32 pixels each, and the weight fragments of a K block reach them through LDS (LDS-DMA, 8 KB per K block, three
-// stages): one global fetch per block instead of one per wave.  With per-wave fetches these layers were bound by
-// L1 (12 KB per wave per K block against 24 MFMAs); B operands stay per-wave buffer loads.
-template <int NW>
-__global__ __launch_bounds__(256) void segconv_wide_kernel(const SegGroupArgs grp)
-{
-    int bx, by, bz;
-    if (!seg_block(grp, bx, by, bz)) return;  // block-uniform
-    const SegArgs &a = grp.a[bz];
-    constexpr int MW = 4, D = 3;  // D = stages of the weight ring / K blocks of pixel operands in flight per wave (6 and 8 measured no faster)
-    __shared__ f32x4 wtile[D][MW * 2 * 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int ct0 = by * MW;
-    const int pt0 = (bx * 4 + wave) * NW;
-    const int n_pix = a.B * a.Ho * a.Wo;
-    const int col = lane & 15, kg = lane >> 4;
-    const int n_kb = a.n_kb;
-
-    int iy0[NW], ix0[NW], img0[NW];
-    bool live[NW];
-#pragma unroll
-    for (int n = 0; n < NW; ++n) {
-        const int p = (pt0 + n) * 16 + col;
-        live[n] = p < n_pix;
-        const int b = p / (a.Ho * a.Wo), q = p - b * (a.Ho * a.Wo);  // image, pixel inside it
-        const int oy = q / a.Wo, ox = q - oy * a.Wo;
-        iy0[n] = oy * a.stride - a.pad;
-        ix0[n] = ox * a.stride - a.pad;
-        img0[n] = b * a.H * a.W;
-    }
-    int tap = kg / a.c8, cg = kg - tap * a.c8;
-    int ty = tap / a.ksize, tx = tap - ty * a.ksize;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.in), 0, a.in_bytes, 0x00020000);
-
-    f32x4 rvs[MW], bvs[MW];
-    seg_vectors<MW>(a, ct0, kg, rvs, bvs);
-    f32x4 acc[MW][NW];
-#pragma unroll
-    for (int m = 0; m < MW; ++m)
-#pragma unroll
-        for (int n = 0; n < NW; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // wave w moves chunks w and w + 4 of the 8 one-KB chunks (channel tile m, half h) of a K block
-    auto stream_weights = [&](int kb, int stage) {
-        const int kbc = kb < n_kb ? kb : n_kb - 1;  // past the end: refetch the last block (multiplied by zeros)
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int c = wave + 4 * r, m = c >> 1, h = c & 1;
-            const f32x4 *src = a.wp + ((size_t)(ct0 + m) * n_kb + kbc) * 128 + h * 64 + lane;
-            __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)src,
-                                             (void __attribute__((address_space(3))) *)(&wtile[stage][c * 64]), 16, 0, 0);
-        }
-    };
-    f32x4 xa[D][NW], xb[D][NW];
-    auto fetch_pixels = [&](int kb, f32x4 (&fa)[NW], f32x4 (&fb)[NW]) {
-        const int dy = ty * a.dil, dx = tx * a.dil;
-        const bool in_range = kb < n_kb;
-#pragma unroll
-        for (int n = 0; n < NW; ++n) {
-            const int iy = iy0[n] + dy, ix = ix0[n] + dx;
-            const bool ok = in_range && live[n] && ty < a.ksize && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-            const unsigned off = ok ? (unsigned)(((img0[n] + iy * a.W + ix) * a.in_stride + cg * 8) * 4) : 0xfffffff0u;
-            fa[n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
-            fb[n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? off + 16u : 0xfffffff0u, 0, 0));
-        }
-        cg += 4;
-        while (cg >= a.c8) {
-            cg -= a.c8;
-            if (++tx == a.ksize) {
-                tx = 0;
-                ++ty;
-            }
-        }
-    };
-    auto multiply = [&](int stage, const f32x4 (&fa)[NW], const f32x4 (&fb)[NW]) {
-        f16x8 xh[NW], xl[NW];
-#pragma unroll
-        for (int n = 0; n < NW; ++n) split8(fa[n], fb[n], xh[n], xl[n]);
-#pragma unroll
-        for (int m = 0; m < MW; ++m) {
-            const f32x4 wh = wtile[stage][(m * 2) * 64 + lane], wl = wtile[stage][(m * 2 + 1) * 64 + lane];
-#pragma unroll
-            for (int n = 0; n < NW; ++n) acc[m][n] = mfma3(wh, wl, xh[n], xl[n], acc[m][n]);
-        }
-    };
-
-    // every wave issues exactly 2 + 2*NW memory operations per K block, weights first: when the pixel operands of
-    // block kb have arrived, so have this wave's weight chunks of block kb (in-order return); the barrier then makes
-    // the other waves' chunks visible and guarantees that nobody still reads the stage refilled next
-    const int rounds = (n_kb + D - 1) / D;
-#pragma unroll
-    for (int s = 0; s < D - 1; ++s) {
-        stream_weights(s, s);
-        fetch_pixels(s, xa[s], xb[s]);
-    }
-    for (int r = 0; r < rounds; ++r) {
-#pragma unroll
-        for (int s = 0; s < D; ++s) {
-            const int kb = r * D + s;
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 2) * (2 + 2 * NW)) : "memory");  // all but the D - 2 newest K blocks' operations
-            __syncthreads();
-            stream_weights(kb + D - 1, (s + D - 1) % D);
-            fetch_pixels(kb + D - 1, xa[(s + D - 1) % D], xb[(s + D - 1) % D]);
-            multiply(s, xa[s], xb[s]);
-        }
-    }
-    if (pt0 * 16 >= n_pix) return;
-    seg_epilogue<MW, NW>(a, acc, ct0, pt0, n_pix, col, kg, rvs, bvs);
 }
 
 // GEMM-shaped form for layers with enough pixels to tile both ways (round 5: the frames of several scenes / a look-ahead
@@ -937,8 +828,6 @@ unsigned seg_map(SegMap &m, int X, int Y, int Z)
 
 // Thresholds of the form choice, shared by seg_launch and seg_launch_multi (each is the measured default of its round's A/B runs:
 // profiles/r05_seg_experiments.txt)
-constexpr int kWideMinKb = 6;         // the wide form's three-stage weight ring wants at least this many K blocks ...
-constexpr int kWideMinBlocks = 256;   // ... and 64 channels x 128 pixels must give this many blocks
 constexpr int kPlainMinWaves = 1024;  // waves of (64 channels, 2 pixel tiles) from which every wave owns its pair: >= 4 per CU hide the operand latency
 constexpr int kSplitKMinKb = 8;       // below this many K blocks the in-block K split is not worth its LDS reduction
 constexpr int kSplitKMinBlocks = 150; // split-K launches take as many channel tiles per block as leave this many blocks
@@ -948,6 +837,8 @@ constexpr int kPlainNw1Min = 50;      // one pixel tile per wave in the plain fo
 constexpr int kGemmMin = 256;         // 128 x 128 tile alone gives this many blocks
 constexpr int kGemm22Min = 128;       // ... or the 64 x 64 tile this many
 constexpr int kGemmMinKb = 4;
+constexpr int kMultiOwnMinKb = 6;        // seg_launch_multi: a member of at least this many K blocks ...
+constexpr int kMultiOwnMinBlocks = 256;  // ... whose group fills this many blocks of 64 channels x 128 pixels runs GEMM-shaped, in a launch of its group
 
 bool seg_trace_on()
 {
@@ -1053,9 +944,6 @@ int seg_launch(SegGroupArgs &g, int n, hipStream_t st)
         else if (mw == 2) hipLaunchKernelGGL((segconv_kernel<2, 1, 1, 4, 3, true>), dim3(seg_map(g.map, n_pt, a.n_ct / 2, n)), dim3(256), 0, st, g);
         else hipLaunchKernelGGL((segconv_kernel<4, 1, 1, 4, 3, true>), dim3(seg_map(g.map, n_pt, groups, n)), dim3(256), 0, st, g);
         variant = mw == 1 ? "<1,1,1,4> drop" : (mw == 2 ? "<2,1,1,4> drop" : "<4,1,1,4> drop");
-    } else if (a.n_kb >= kWideMinKb && (long)groups * ((n_pt + 7) / 8) * n >= kWideMinBlocks) {
-        variant = "wide<2>";
-        hipLaunchKernelGGL((segconv_wide_kernel<2>), dim3(seg_map(g.map, (n_pt + 7) / 8, groups, n)), dim3(256), 0, st, g);
     } else if (waves2 >= kPlainMinWaves || a.n_kb < kSplitKMinKb) {
         if (groups == 1) {
             variant = "<4,2,1,1>";
@@ -1122,7 +1010,8 @@ int seg_launch_multi(SegGroupArgs &g, int n, hipStream_t st)
         for (int j = 0; j < n; ++j) same += same_shape(i, j) ? 1 : 0;
         special = special || a.rng != nullptr || a.rng_bump != nullptr;
         const long waves2 = (long)groups * ((n_pt + 1) / 2) * same;
-        if (a.n_kb >= kWideMinKb && (long)groups * ((n_pt + 7) / 8) * same >= kWideMinBlocks) special = true;  // (a wide-kernel layer: with its own group)
+        // (a layer this large takes the GEMM-shaped form with its own group: seg_launch's b22 >= kGemm22Min follows from this)
+        if (a.n_kb >= kMultiOwnMinKb && (long)groups * ((n_pt + 7) / 8) * same >= kMultiOwnMinBlocks) special = true;
         if (waves2 >= kPlainMinWaves || a.n_kb < kSplitKMinKb) ++n_plain; else ++n_split;
         X1 = n_pt > X1 ? n_pt : X1;
         Y1 = a.n_ct > Y1 ? a.n_ct : Y1;

@@ -36,7 +36,7 @@ SHAPES = [
     (48, 4, 3, 1, 1, 1, 30, 40), (4, 48, 3, 1, 1, 1, 30, 40), (48, 24, 3, 1, 1, 1, 60, 80),         # SSMA skips
     (280, 256, 3, 1, 1, 1, 30, 40), (256, 256, 3, 1, 1, 1, 60, 80), (256, 30, 1, 1, 1, 0, 60, 80), (256, 24, 1, 1, 1, 0, 1, 1),
     (24, 40, 3, 1, 1, 1, 7, 5), (8, 8, 5, 3, 2, 4, 33, 17),  # odd geometry: ragged tiles, 5x5, stride 3
-    # >= 256 blocks of 64 channels x 128 pixels: the LDS-shared-weights kernel (640x480 frames)
+    # the many-pixel layers of 640x480 frames (and an odd 131x157 one): GEMM-shaped forms today (64 x 64 and 128 x 80 tiles)
     (256, 256, 3, 1, 1, 1, 120, 160), (64, 64, 3, 1, 1, 1, 240, 320), (64, 128, 3, 2, 1, 1, 240, 320), (40, 72, 3, 1, 2, 2, 131, 157),
     (256, 30, 1, 1, 1, 0, 240, 320),
 ]
@@ -173,7 +173,7 @@ def test_front_end_operators_match_torch(cuda):
     (256, 256, 3, 1, (1, 2), 60, 80, True),   # the GEMM-shaped form alone and as a pair
     (128, 32, 3, 1, (1, 2, 1, 2), 30, 40, True),    # both dilations of a multi-scale unit of both encoders
     (64, 64, 3, 1, (3, 6, 12, 3, 6, 12), 15, 20, True),  # the three cascades of two eASPPs (split-K kernel)
-    (1024, 256, 1, 1, (1, 1), 15, 20, True), (64, 64, 3, 1, (1, 1), 240, 320, True)])  # ... and the LDS-shared-weights kernel
+    (1024, 256, 1, 1, (1, 1), 15, 20, True), (64, 64, 3, 1, (1, 1), 240, 320, True)])  # ... and a 240x320 map (GEMM-shaped both ways)
 def test_grouped_launch_gives_the_bits_of_single_launches(cin, cout, k, stride, dils, h, w, same_form):
     """ojf_segconv_forward_group (blockIdx.z = member) against one ojf_segconv_forward per member: same kernels, same
     arithmetic, same order - identical bits, with residuals and ReLU, on members of different dilation.  Where the block
@@ -282,36 +282,50 @@ def test_batched_front_end_operators():
     assert (sc.view(B, -1) - ws.reshape(B, -1)).abs().max().item() <= 1e-6 and torch.equal(ids.view(B, -1).long(), wi.reshape(B, -1))
 
 
+# segconv.multi cases of test_heterogeneous_multi_launch_equals_separate_calls: the inputs (channels, h, w) by name, and per case
+# the members (c_in, c_out, k, stride, input, activation, gated).  test_segconv_forms_gpu.py proves from the launch trace that the
+# first four are ONE launch each and that the last falls back to separate launches.
+HETERO_INPUTS = {'x15': (1024, 15, 20), 'x30': (512, 30, 40), 'x60': (48, 60, 80), 'x30b': (48, 30, 40), 'x15b': (512, 15, 20),
+                 'y15': (16, 15, 20), 'y30': (4, 30, 40), 'y60': (4, 60, 80)}
+HETERO_CASES = [
+    # layer4 unit 0: shortcut 1024 -> 2048, first 1x1 1024 -> 512 (both in-block split-K), two encoders
+    [(1024, 2048, 1, 1, 'x15', None, False), (1024, 2048, 1, 1, 'x15', None, False), (1024, 512, 1, 1, 'x15', 'relu', False), (1024, 512, 1, 1, 'x15', 'relu', False)],
+    # layer3 unit 0 with the skip projection: stride-2 shortcut, 1x1, 512 -> 24
+    [(512, 1024, 1, 2, 'x30', None, False), (512, 256, 1, 1, 'x30', 'relu', False), (512, 24, 1, 1, 'x30', None, False)],
+    # SSMA squeeze on three map sizes, then a plain-form trio (tiny K) with a gate
+    [(48, 4, 3, 1, 'x60', 'relu', False), (48, 4, 3, 1, 'x30b', 'relu', False), (512, 16, 3, 1, 'x15b', 'relu', False)],
+    [(16, 512, 3, 1, 'y15', 'sigmoid', True), (4, 48, 3, 1, 'y30', 'sigmoid', False)],
+    # a mix of forms (split-K + plain): falls back to separate launches, same results
+    [(512, 256, 3, 1, 'x15b', 'relu', False), (4, 48, 3, 1, 'y60', None, False)],
+]
+
+
+def heterogeneous_cases():
+    """HETERO_CASES as lists of (nn.Conv2d, NHWC input, keyword arguments) on the device."""
+    g = torch.Generator().manual_seed(123)
+    inputs = {k: to_nhwc(torch.randn((1,) + shape, generator=g).cuda()) for k, shape in HETERO_INPUTS.items()}
+    cases = []
+    for members in HETERO_CASES:
+        calls = []
+        for cin, cout, k, s, key, act, gated in members:
+            m = nn.Conv2d(cin, cout, k, stride=s, padding=k // 2, bias=True).cuda()
+            with torch.no_grad():
+                m.weight.copy_(torch.randn(m.weight.shape, generator=g) / np.sqrt(cin * k * k))
+            kw = {'act': act} if act else {}
+            if gated:
+                h, w = HETERO_INPUTS[key][1:]
+                kw['mul'] = to_nhwc(torch.rand((1, cout, (h - 1) // s + 1, (w - 1) // s + 1), generator=g).cuda())
+            calls.append((m, inputs[key], kw))
+        cases.append(calls)
+    return cases
+
+
 def test_heterogeneous_multi_launch_equals_separate_calls():
     """segconv.multi: independent convolutions of DIFFERENT shapes (a unit's shortcut next to its first 1x1 and the encoder's
     skip projection; the three SSMA blocks on three map sizes) in one launch where their kernel forms allow it - every member
     equals its own single call up to the K-block order of another form (3e-6 of the layer's scale)."""
     from online_joint_depthfusion_and_semantic_amd.segconv import SegConv, multi
-    g = torch.Generator().manual_seed(123)
-
-    def conv(cin, cout, k, s=1, d=1):
-        m = nn.Conv2d(cin, cout, k, stride=s, dilation=d, padding=d * (k // 2), bias=True).cuda()
-        with torch.no_grad():
-            m.weight.copy_(torch.randn(m.weight.shape, generator=g) / np.sqrt(cin * k * k))
-        return m
-    x15 = to_nhwc((torch.randn((1, 1024, 15, 20), generator=g)).cuda())
-    x30 = to_nhwc((torch.randn((1, 512, 30, 40), generator=g)).cuda())
-    x60 = to_nhwc((torch.randn((1, 48, 60, 80), generator=g)).cuda())
-    x30b = to_nhwc((torch.randn((1, 48, 30, 40), generator=g)).cuda())
-    x15b = to_nhwc((torch.randn((1, 512, 15, 20), generator=g)).cuda())
-    gate = to_nhwc(torch.rand((1, 512, 15, 20), generator=g).cuda())
-    cases = [
-        # layer4 unit 0: shortcut 1024 -> 2048, first 1x1 1024 -> 512 (both in-block split-K), two encoders
-        [(conv(1024, 2048, 1), x15, {}), (conv(1024, 2048, 1), x15, {}), (conv(1024, 512, 1), x15, {'act': 'relu'}), (conv(1024, 512, 1), x15, {'act': 'relu'})],
-        # layer3 unit 0 with the skip projection: stride-2 shortcut, 1x1, 512 -> 24
-        [(conv(512, 1024, 1, s=2), x30, {}), (conv(512, 256, 1), x30, {'act': 'relu'}), (conv(512, 24, 1), x30, {})],
-        # SSMA squeeze on three map sizes, then a plain-form trio (tiny K) with a gate
-        [(conv(48, 4, 3), x60, {'act': 'relu'}), (conv(48, 4, 3), x30b, {'act': 'relu'}), (conv(512, 16, 3), x15b, {'act': 'relu'})],
-        [(conv(16, 512, 3), to_nhwc(torch.randn((1, 16, 15, 20), generator=g).cuda()), {'act': 'sigmoid', 'mul': gate}),
-         (conv(4, 48, 3), to_nhwc(torch.randn((1, 4, 30, 40), generator=g).cuda()), {'act': 'sigmoid'})],
-        # a mix of forms (split-K + plain): falls back to separate launches, same results
-        [(conv(512, 256, 3), x15b, {'act': 'relu'}), (conv(4, 48, 3), to_nhwc(torch.randn((1, 4, 60, 80), generator=g).cuda()), {})],
-    ]
+    cases = heterogeneous_cases()
     for calls in cases:
         ops = [(SegConv(m), x, kw) for m, x, kw in calls]
         got = multi(ops)
@@ -323,4 +337,4 @@ def test_heterogeneous_multi_launch_equals_separate_calls():
                 wide = y.as_strided((1, (op.c_out + 7) // 8 * 8, y.shape[2], y.shape[3]), y.stride())
                 assert float(wide[:, op.c_out:].abs().max()) == 0.0
     from online_joint_depthfusion_and_semantic_amd import _lib
-    assert _lib.load().ojf_net_check(_lib.stream_ptr(x15.device)) == 0
+    assert _lib.load().ojf_net_check(_lib.stream_ptr(cases[0][0][1].device)) == 0
