@@ -1668,6 +1668,15 @@ static inline void mark_launch(Launch what, hipStream_t st)
     g_marks.push_back(LaunchMark{kLaunchNames[what], st, e});
 }
 
+// OJF_NET_TRACE=1 (read once per process, like OJF_SEG_TRACE): one stderr line per launch, "ojf_net <launch name> | <field> <value> ...",
+// with the numbers the launch site decided: how it cuts the frame into pixel blocks, bands and tiles.  tests/net_edge_cases.py restates
+// those decisions and tests/test_net_edges_gpu.py compares the two.  Unset, nothing changes: the lines are the only effect.
+static bool net_trace_on()
+{
+    static const bool on = getenv("OJF_NET_TRACE") ? atoi(getenv("OJF_NET_TRACE")) != 0 : false;
+    return on;
+}
+
 // Fork / join events between streams of the same device: no timing and no system-scope fence - nothing here is read by
 // the host or another device through these events.
 static unsigned event_flags() { return hipEventDisableTiming | hipEventDisableSystemFence; }
@@ -1899,6 +1908,9 @@ static int launch_pair_t(PairArgs &a, hipStream_t st)
     }
     a.tiles_x = (a.w + TW - 1) / TW;
     const int tiles = a.tiles_x * ((a.h + TH - 1) / TH);
+    if (net_trace_on())
+        fprintf(stderr, "ojf_net %s | tw %d th %d tiles_x %d tiles %d grid_x %d banded %d\n", kLaunchNames[L_DENSE_PAIR], TW, TH, a.tiles_x, tiles,
+                tiles, (tiles & 7) == 0 ? 1 : 0);
     hipLaunchKernelGGL((dense_pair_kernel<TW, TH>), dim3(tiles), dim3(G::THREADS), G::LDS_BYTES, st, a);
     mark_launch(L_DENSE_PAIR, st);
     return check_hip(hipGetLastError(), "dense_pair_kernel launch");
@@ -2032,6 +2044,9 @@ static int launch_chain_t(ChainDenseArgs &a, hipStream_t st)
     if (tiles > kChainSyncInts - kChainFlags0) return fail("dense chain: too many tiles for the flag array");
     // one block per CU (160 KB of LDS); the blocks draw (Block, tile) items until none is left
     const int grid = cus > 0 && cus < tiles ? cus : tiles;
+    if (net_trace_on())
+        fprintf(stderr, "ojf_net %s | tw %d th %d tiles_x %d tiles_y %d tiles %d grid_x %d\n", kLaunchNames[L_DENSE_CHAIN], TW, TH, a.tiles_x,
+                a.tiles_y, tiles, grid);
     hipLaunchKernelGGL((dense_chain_kernel<TW, TH, WAVES>), dim3(grid), dim3(G::THREADS), G::LDS_BYTES, st, a);
     mark_launch(L_DENSE_CHAIN, st);
     return check_hip(hipGetLastError(), "dense_chain_kernel launch");
@@ -2295,6 +2310,14 @@ static int launch_conv_args(const ConvArgs *args, int n, int nt, hipStream_t st,
     for (int i = 0; i < n && lean; ++i) lean = conv_lean_ok(args[i]);
     int n_ins = 0, n_outs = 0;
     for (int i = 0; i < n; ++i) { n_ins += args[i].in_split ? 1 : 0; n_outs += args[i].out_split ? 1 : 0; }
+    if (net_trace_on()) {
+        char perm[128];
+        int at = 0;
+        for (int i = 0; i < n; ++i)
+            at += snprintf(perm + at, sizeof(perm) - (size_t)at, "%s%d:%d:%d", i ? "," : "", grp.g[i].row_perm, grp.g[i].perm_q, grp.g[i].perm_rem);
+        fprintf(stderr, "ojf_net %s | n %d mt %d nt %d grid_x %u nblocks %d grid16_x %u band %d lean %d perm %s\n", kLaunchNames[conv_launch(arith, n)],
+                n, mt, nt, grid.x, grp.nblocks, grid16.x, grp.band, lean ? 1 : 0, perm);
+    }
     if ((n_ins || n_outs) && (arith != OJF_ARITH_F16X3 || (n_ins && (n_ins != n || mt != 2 || nt != 2))))
         return fail("conv: split planes are a format of the split-fp16 grouped 3x3 launches only");
 #define OJF_LAUNCH16(MT_, NT_)                                                                                      \
@@ -2869,17 +2892,20 @@ static int run_vortex(ojf_net *net, const VortexStep &s, hipStream_t st, const C
     float *out = last ? net->Y3 : net->YY;
     const int in_g0 = 0, out_g0 = last ? 0 : s.vortex * o4;
     const dim3 grid(chain_blocks(net)), block(ojf::kChainThreads);
+    const int banded = (grid.x & 7) == 0 ? 1 : 0;  // (banded_block_x; for the trace only)
 
     // ---- entry: the four branch-entry 1x1 as one GEMM into sc.Z, the global-average branch's column sums ----------------
     if (s.entry == ENTRY_GENERIC) {
         // global-average branch -> bias of the final conv, on the side stream (fork here, join before the tail)
         OJF_HIP(hipEventRecord(sc.ev_fork, st));
         OJF_HIP(hipStreamWaitEvent(sc.side, sc.ev_fork, 0));
-        hipLaunchKernelGGL(colsum_kernel, dim3(kSumBlocks, v.c_in_phys / 4), dim3(256), 0, sc.side, planes(in), in_g0,
-                           net->npix, sc.partial);
+        const dim3 sgrid(kSumBlocks, v.c_in_phys / 4), ggrid(1);
+        hipLaunchKernelGGL(colsum_kernel, sgrid, dim3(256), 0, sc.side, planes(in), in_g0, net->npix, sc.partial);
+        if (net_trace_on()) fprintf(stderr, "ojf_net %s | grid_x %u grid_y %u\n", kLaunchNames[L_COLSUM], sgrid.x, sgrid.y);
         mark_launch(L_COLSUM, sc.side);
         OJF_HIP(hipGetLastError());
-        hipLaunchKernelGGL(gave_bias_kernel, dim3(1), dim3(256), 0, sc.side, gave_args(net, v, sc.partial, kSumBlocks, 256));
+        hipLaunchKernelGGL(gave_bias_kernel, ggrid, dim3(256), 0, sc.side, gave_args(net, v, sc.partial, kSumBlocks, 256));
+        if (net_trace_on()) fprintf(stderr, "ojf_net %s | grid_x %u grid_y %u\n", kLaunchNames[L_GAVE_BIAS], ggrid.x, ggrid.y);
         mark_launch(L_GAVE_BIAS, sc.side);
         OJF_HIP(hipGetLastError());
         // branch entries: one GEMM, branch 0 gets bias + ReLU in the epilogue
@@ -2897,6 +2923,8 @@ static int run_vortex(ojf_net *net, const VortexStep &s, hipStream_t st, const C
         // rounding of the channel sums: not kept, profiles/r06_fusion_net_experiments.txt)
         if (s.entry_ntin == 16) OJF_LAUNCH_BY_ARITH(entry1x1_kernel, ea, 1, 16, 5);
         else OJF_LAUNCH_BY_ARITH(entry1x1_kernel, ea, 1, 8, 5);
+        if (net_trace_on())
+            fprintf(stderr, "ojf_net %s | ntin %d blocks %u banded %d\n", kLaunchNames[L_ENTRY1X1], s.entry_ntin, grid.x, banded);
         mark_launch(L_ENTRY1X1, st);
         OJF_HIP(hipGetLastError());
     }
@@ -2914,7 +2942,9 @@ static int run_vortex(ojf_net *net, const VortexStep &s, hipStream_t st, const C
         pa.split_out = s.split ? 1 : 0;
         if (s.z2) { pa.z2 = planes(net->sc[1].Z); pa.q0 = planes(sc.Q0); pa.bias0 = v.bias0; }
         // grid.x: the tiles (+ the global-average block of the chain flow) rounded up to a multiple of 8 (XCD bands)
-        hipLaunchKernelGGL(pool_pyramid_kernel, dim3(round_up(pa.tiles + (s.chain_flow ? 1 : 0), 8), (s.z2 ? 4 : 3) * c4), dim3(256), 0, st, pa);
+        const dim3 pgrid(round_up(pa.tiles + (s.chain_flow ? 1 : 0), 8), (s.z2 ? 4 : 3) * c4);
+        hipLaunchKernelGGL(pool_pyramid_kernel, pgrid, dim3(256), 0, st, pa);
+        if (net_trace_on()) fprintf(stderr, "ojf_net %s | tiles %d grid_x %u grid_y %u\n", kLaunchNames[L_POOL_PYRAMID], pa.tiles, pgrid.x, pgrid.y);
         mark_launch(L_POOL_PYRAMID, st);
         OJF_HIP(hipGetLastError());
     }
@@ -3002,6 +3032,7 @@ static int run_vortex(ojf_net *net, const VortexStep &s, hipStream_t st, const C
         OJF_LAUNCH_BY_ARITH(vortex_tail_kernel, ta, 1, 2, 8);
         break;
     }
+    if (net_trace_on()) fprintf(stderr, "ojf_net %s | blocks %u banded %d\n", kLaunchNames[name], grid.x, banded);
     mark_launch(name, st);
     return check_hip(hipGetLastError(), "vortex_tail_kernel launch");
 }

@@ -19,8 +19,8 @@ class NS:
         self.__dict__.update(k)
 
 
-def seeded_net(version, sem, h, w, seed=0):
-    cfg = NS(n_points=9, growth_factor=6, use_semantics=sem, output_scale=1.0, resx=w, resy=h)
+def seeded_net(version, sem, h, w, seed=0, n_points=9, growth_factor=6):
+    cfg = NS(n_points=n_points, growth_factor=growth_factor, use_semantics=sem, output_scale=1.0, resx=w, resy=h)
     torch.manual_seed(seed)
     net = getattr(model, 'FusionNet_' + version)(cfg)
     for m in net.modules():  # train_fusion.py:29-31 xavier init; randomised BN statistics
@@ -67,10 +67,10 @@ def test_conv2d_layer(cuda, arith, cin, cout, k, dil, act, h, w):
     assert err <= TOL
 
 
-def _inputs(h, w, seed=1):
+def _inputs(h, w, seed=1, n_points=9):
     g = torch.Generator().manual_seed(seed)
-    return dict(tsdf_values=(torch.rand(1, 9, h, w, generator=g) - 0.5) * 0.2,
-                tsdf_weights=torch.rand(1, 9, h, w, generator=g) * 4,
+    return dict(tsdf_values=(torch.rand(1, n_points, h, w, generator=g) - 0.5) * 0.2,
+                tsdf_weights=torch.rand(1, n_points, h, w, generator=g) * 4,
                 tsdf_frame=torch.rand(1, 1, h, w, generator=g) * 4,
                 sem_ids=torch.randint(0, 30, (h, w), generator=g, dtype=torch.uint8))
 
@@ -99,7 +99,12 @@ def test_fusion_net_forward(cuda, arith, version, sem, h, w):
         assert err <= TOL, (version, sem, h, w, err)
         if stride > 9:
             assert torch.all(got[:, 9:] == 5.0)
-    assert eng.macs_per_pixel == (326876 if not sem else (508820 if version == 'v3' else None)) or version == 'v2'
+    # the exact count of all four nets: c_in * c_out * k^2 over the folded layers, without the global-average 1x1 of every
+    # VortexPooling - it acts on a 1x1 map, not per pixel (326876 / 508820 for v3 without / with semantics)
+    macs = sum(wt.shape[1] * wt.shape[0] * k * k for wt, _, k, _ in model.fold_layers(net))
+    macs -= sum(m.gave_pool[1].in_channels * m.gave_pool[1].out_channels for m in net.modules() if isinstance(m, model.VortexPooling))
+    assert eng.macs_per_pixel == macs
+    assert version != 'v3' or macs == (508820 if sem else 326876)
     eng.close()
 
 
@@ -173,24 +178,9 @@ def test_fusion_net_other_topologies(cuda, arith, version, sem, n_points, growth
     (= the C ABI's growth + 1); 8 points x growth_factor 7 is 7 x 20 = 140 dense channels: the stand-alone 16-tile entry kernel,
     fused tails (the first one carries the next entry GEMM), no chain-form head."""
     h, w = 40, 56
-    cfg = NS(n_points=n_points, growth_factor=growth, use_semantics=sem, output_scale=1.0, resx=w, resy=h)
-    torch.manual_seed(11)
-    net = getattr(model, 'FusionNet_' + version)(cfg)
-    for m in net.modules():
-        if isinstance(m, torch.nn.Conv2d):
-            torch.nn.init.xavier_normal_(m.weight)
-            m.bias.data.normal_(0, 0.05)
-        if isinstance(m, torch.nn.BatchNorm2d):
-            m.running_mean.normal_(0, 0.1)
-            m.running_var.uniform_(0.5, 1.5)
-            m.weight.data.uniform_(0.5, 1.5)
-            m.bias.data.normal_(0, 0.1)
-    net = net.eval()
-    g = torch.Generator().manual_seed(2)
-    x = dict(tsdf_values=(torch.rand(1, n_points, h, w, generator=g) - 0.5) * 0.2,
-             tsdf_weights=torch.rand(1, n_points, h, w, generator=g) * 4,
-             tsdf_frame=torch.rand(1, 1, h, w, generator=g) * 4)
-    sem_ids = torch.randint(0, 30, (h, w), generator=g, dtype=torch.uint8)
+    net = seeded_net(version, sem, h, w, seed=11, n_points=n_points, growth_factor=growth)
+    x = _inputs(h, w, seed=2, n_points=n_points)
+    sem_ids = x.pop('sem_ids')
     x['semantic_frame'] = ((1 + sem_ids.float()) / 30).view(1, 1, h, w)
     with torch.no_grad():
         ref = net(x)[0].permute(1, 2, 0).reshape(h * w, n_points)
