@@ -115,17 +115,21 @@ def _net(version, sem, h, w, seed=3, n_points=9):
     return net
 
 
-def _whole_net_gradient_case(cuda, version, sem, training, path, h, w, noise_factor=2.0):
+def _whole_net_inputs(h, w, seed=11):
+    g = torch.Generator().manual_seed(seed)
+    x = dict(tsdf_values=(torch.rand(1, 9, h, w, generator=g) - 0.5) * 0.2, tsdf_weights=torch.rand(1, 9, h, w, generator=g) * 4,
+             tsdf_frame=torch.rand(1, 1, h, w, generator=g) * 4, semantic_frame=torch.randint(1, 31, (1, 1, h, w), generator=g).float() / 30)
+    return x, (torch.rand(1, 9, h, w, generator=g) - 0.5) * 0.2
+
+
+def _whole_net_gradient_case(cuda, version, sem, training, path, h, w, noise_factor=2.0, input_seed=11):
     graph = path == 'graph'
     net = _net(version, sem, h, w)
     ref, ref32 = copy.deepcopy(net).double(), copy.deepcopy(net)
     net = net.to(cuda)
     for m in (net, ref, ref32):
         m.train(training)
-    g = torch.Generator().manual_seed(11)
-    x = dict(tsdf_values=(torch.rand(1, 9, h, w, generator=g) - 0.5) * 0.2, tsdf_weights=torch.rand(1, 9, h, w, generator=g) * 4,
-             tsdf_frame=torch.rand(1, 1, h, w, generator=g) * 4, semantic_frame=torch.randint(1, 31, (1, 1, h, w), generator=g).float() / 30)
-    target = (torch.rand(1, 9, h, w, generator=g) - 0.5) * 0.2
+    x, target = _whole_net_inputs(h, w, input_seed)
 
     def loss(e, t):
         return (e - t).abs().mean() + 10 * ((e - t) ** 2).mean()
@@ -401,9 +405,11 @@ def _second_pass_case(cuda, version, sem, training, h, w):
 @pytest.mark.parametrize('training', [False, True])
 @pytest.mark.parametrize('version,sem', [('v3', True), ('v2', False)])
 def test_executor_backward_data_in_split_fp16_from_the_second_pass(cuda, version, sem, training):
-    """The executor's first backward pass runs backward-data and the weight gradients on fp32-input MFMAs and measures the
-    magnitude of every dy tensor; from the second pass on dy is stored with a power-of-two factor and both run in the
-    split-fp16 arithmetic (ojf_trainer_backward: conv_f16x3_kernel on the transposed weights, train_wgrad_mfma_kernel<true>).
+    """dy is stored with a power-of-two factor derived in the same pass (BnActArgs::bnd), so with arithmetic 'f16x3' EVERY backward pass,
+    the first included, runs backward-data and the weight gradients in the split-fp16 arithmetic (ojf_trainer_backward: conv_f16x3_kernel
+    on the transposed weights, train_wgrad_mfma_kernel<true>); until the factor moved into the pass, the first pass ran on fp32-input
+    MFMAs, which is what this test was written against.  It now pins that the passes repeat each other (the comparison of the two
+    arithmetics is test_backward_arithmetic_f32_keeps_the_backward_convolutions_on_fp32_mfma and tests/test_train_edges_gpu.py).
     Same frame, same weights (eval() mode, or train() mode without dropout: batch statistics do not depend on the running
     buffers): passes 2 and 3 must reproduce pass 1's gradients to fp32-class accuracy - per tensor within 2e-5 of max(its
     scale, 1e-3 of the largest gradient) in eval() mode; 2e-4 in train() mode, where the batch-statistics chain amplifies any
