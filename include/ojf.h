@@ -517,7 +517,8 @@ int ojf_volume_confusion(const uint8_t *ids_est_dev, const uint8_t *ids_gt_dev, 
  *   Marching tetrahedra on the 6-tetrahedra split of every cell (watertight, no ambiguous cases) - same surface up
  *   to the triangulation, NOT the same triangle list as skimage's Lewiner tables.  Cells with a NaN corner or
  *   (weights_dev != NULL) an unobserved corner are skipped.
- *   workspace_dev: ojf_mesh_workspace_bytes(X,Y,Z) bytes of device memory (per-block counts / offsets).
+ *   workspace_dev: ojf_mesh_workspace_bytes(X,Y,Z) bytes of device memory (per-block counts / offsets).  After the
+ *   call it holds, as u32 per block of 64 x 4 cells, the offset of the block's first triangle in the list.
  *   Call once with capacity = 0 (vertices may be NULL) to get *count_dev = number of triangles, then again with
  *   buffers of capacity triangles: vertices_dev f32[capacity][3][3] = origin + voxel_index * resolution (origin 0
  *   gives the reference's mesh frame); labels_dev u8[capacity][3] (or NULL) = ids_dev at the voxel nearest to each

@@ -143,6 +143,44 @@ def surface_points(tsdf, mask, origin, resolution):
     return torch.cat(pts, dim=0) if pts else torch.zeros((0, 3), dtype=torch.float64, device=tsdf.device)
 
 
+MAX_BINS = 1 << 24  # 64 MB of int32 offsets
+
+
+def bin_grid(lo, span, tau):
+    """Cell size and bin counts of the grid ``points_within`` sorts a point set into (host arithmetic only).
+
+    lo, span: the three minima and extents (max - min) of the set, finite; tau >= 0.  Returns (cell, G) with
+    cell >= tau, cell > 0, G[a] = floor(span[a] / cell) + 1 (the bin of the largest coordinate, plus one),
+    G[a] == 1 on every axis whose extent is below the cell size, and G[0] * G[1] * G[2] <= MAX_BINS exactly.  The
+    bins only select candidates; the hits are defined by the f64 distance test, so the cell size never shows in them.
+    ``lo`` is taken for the interface's sake: the grid does not depend on where the set lies."""
+    import math
+    tau = float(tau)
+    extent = [max(float(v), 0.0) for v in span]
+    if not (tau >= 0.0) or not all(math.isfinite(v) for v in extent) or not all(math.isfinite(float(v)) for v in lo):
+        raise ValueError('bin_grid: need tau >= 0 and a finite point set')
+    cell = max(tau, 1e-30)
+    # coarsen when tau is tiny against the extent.  Only the axes that are at least one cell long count: a flat or
+    # degenerate axis has one bin whatever the cell, so the cap is shared among the others.  Logarithms, because the
+    # product of three extents (or of three extent / cell ratios) can leave the f64 range.
+    for _ in range(4):
+        active = [v for v in extent if v >= cell]
+        if not active:
+            break
+        need = math.exp((sum(math.log(v) for v in active) - math.log(MAX_BINS)) / len(active))
+        if not need > cell:
+            break
+        cell = need
+    # now span / cell <= ~2^24 on every axis: the counts are small integers.  The +1 per axis can still carry the
+    # product past the cap; grow the cell until it does not (at least 1/64 per step, so a handful of steps).
+    while True:
+        G = [int(math.floor(v / cell)) + 1 for v in extent]
+        n_bins = G[0] * G[1] * G[2]
+        if n_bins <= MAX_BINS:
+            return cell, G
+        cell *= max((n_bins / MAX_BINS) ** (1.0 / sum(1 for g in G if g > 1)), 1.0 + 1.0 / 64)
+
+
 def points_within(query, points, tau):
     """Number of rows of ``query`` [N,3] with a row of ``points`` [M,3] within ``tau`` (cuda tensors, evaluated in
     f64 by ojf_points_within exactly like ``cKDTree(points).query(query)[0] <= tau``).  Returns (count, hit u8[N])."""
@@ -153,14 +191,13 @@ def points_within(query, points, tau):
     hit = torch.zeros(q.shape[0], dtype=torch.uint8, device=q.device)
     if q.shape[0] == 0 or p.shape[0] == 0:
         return 0, hit
-    cell = max(float(tau), 1e-30)
     lo = p.min(dim=0).values
     span = p.max(dim=0).values - lo
-    # coarsen the bins when tau is tiny against the extent: at most ~2^24 cells (64 MB of offsets)
-    extent = [max(float(v), 0.0) for v in span.tolist()]
-    cell = max(cell, (max(extent[0], cell) * max(extent[1], cell) * max(extent[2], cell) / float(1 << 24)) ** (1.0 / 3.0))
-    c = torch.floor((p - lo) / cell).to(torch.int64)
-    G = [int(v) + 1 for v in c.max(dim=0).values.tolist()]
+    cell, G = bin_grid(lo.tolist(), span.tolist(), tau)  # at most MAX_BINS cells, one bin on a flat axis
+    # divide by a device tensor: a Python scalar would be multiplied in as its reciprocal, which rounds differently from
+    # the division bin_grid and the kernel make and can put the largest coordinate into bin G instead of G - 1
+    c = torch.floor((p - lo) / torch.tensor(cell, dtype=torch.float64, device=p.device)).to(torch.int64)
+    assert all(top < g for top, g in zip(c.max(dim=0).values.tolist(), G)), 'points_within: a point fell outside the bin grid'
     key = (c[:, 0] * G[1] + c[:, 1]) * G[2] + c[:, 2]
     key, order = torch.sort(key)
     p = p[order].contiguous()

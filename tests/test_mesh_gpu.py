@@ -13,73 +13,10 @@ import numpy as np
 import pytest
 import torch
 
+import mesh_ref
+from mesh_ref import np_triangle_count, np_cell_valid, np_vertex_set  # the numpy statements live beside the reference
+
 pytestmark = pytest.mark.gpu
-
-KUHN_DIRS = [(1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1)]
-CORNER = np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0], [0, 0, 1], [1, 0, 1], [1, 1, 1], [0, 1, 1]])
-TETS = [(0, 5, 1, 6), (0, 1, 2, 6), (0, 2, 3, 6), (0, 3, 7, 6), (0, 7, 4, 6), (0, 4, 5, 6)]
-
-
-def np_triangle_count(vol, iso, valid):
-    """Triangles marching tetrahedra emit: per tetrahedron 1 (one corner apart) or 2 (two against two)."""
-    X, Y, Z = vol.shape
-    inside = vol < iso
-    corner = [inside[c[0]:X - 1 + c[0], c[1]:Y - 1 + c[1], c[2]:Z - 1 + c[2]].astype(np.int64) for c in CORNER]
-    total = 0
-    for t in TETS:
-        k = sum(corner[c] for c in t)
-        total += int(((((k == 1) | (k == 3)) * 1 + (k == 2) * 2) * valid).sum())
-    return total
-
-
-def np_cell_valid(vol, weights):
-    X, Y, Z = vol.shape
-    ok = ~np.isnan(vol)
-    if weights is not None:
-        ok &= weights > 0
-    valid = np.ones((X - 1, Y - 1, Z - 1), dtype=bool)
-    for c in CORNER:
-        valid &= ok[c[0]:X - 1 + c[0], c[1]:Y - 1 + c[1], c[2]:Z - 1 + c[2]]
-    return valid
-
-
-def np_vertex_set(vol, iso, valid, origin, res):
-    """Unique surface vertices: crossings on every Kuhn edge that belongs to at least one valid cell."""
-    X, Y, Z = vol.shape
-    vol = vol.astype(np.float32)
-    iso = np.float32(iso)
-    out = []
-    pad = np.zeros((X + 1, Y + 1, Z + 1), dtype=bool)  # pad[i+1,j+1,k+1] = valid[i,j,k]
-    pad[1:X, 1:Y, 1:Z] = valid
-    for d in KUHN_DIRS:
-        d = np.array(d)
-        n = np.array([X, Y, Z]) - d
-        a = vol[:n[0], :n[1], :n[2]]
-        b = vol[d[0]:, d[1]:, d[2]:]
-        cross = (a < iso) != (b < iso)
-        # cells sharing the edge p..p+d: lower corners p - e with e in {0,1} on the axes where d is 0
-        used = np.zeros(cross.shape, dtype=bool)
-        free = [ax for ax in range(3) if d[ax] == 0]
-        for m in range(1 << len(free)):
-            e = np.zeros(3, dtype=int)
-            for q, ax in enumerate(free):
-                e[ax] = (m >> q) & 1
-            sl = tuple(slice(1 - e[ax], 1 - e[ax] + n[ax]) for ax in range(3))
-            used |= pad[sl]
-        with np.errstate(invalid='ignore'):
-            cross &= used
-        idx = np.argwhere(cross)
-        if idx.shape[0] == 0:
-            continue
-        va, vb = a[cross], b[cross]
-        pa, pb = idx.astype(np.float32), (idx + d).astype(np.float32)
-        swap = va > vb
-        p0, p1 = np.where(swap[:, None], pb, pa), np.where(swap[:, None], pa, pb)
-        v0, v1 = np.where(swap, vb, va), np.where(swap, va, vb)
-        t = ((iso - v0) / (v1 - v0)).astype(np.float32)
-        p = (p0 + (t[:, None] * (p1 - p0)).astype(np.float32)).astype(np.float32)
-        out.append((np.asarray(origin, dtype=np.float64)[None] + p.astype(np.float64) * float(res)).astype(np.float32))
-    return np.unique(np.concatenate(out, axis=0), axis=0) if out else np.zeros((0, 3), np.float32)
 
 
 def sphere(n, r, centre=None, dtype=np.float16):
@@ -190,6 +127,9 @@ def test_labels_follow_nearest_voxel_rule():
     want = ids[idx[:, 0], idx[:, 1], idx[:, 2]]
     got = lab.cpu().numpy().reshape(-1)
     assert tie.mean() < 0.01 and np.array_equal(got[~tie], want[~tie])
+    # and exactly, ties included: the reference rounds the fp32 index coordinates themselves, before any division
+    ref = mesh_ref.triangles(vol, 0.0, None, ids, (0., 0., 0.), res)
+    assert np.array_equal(tri.cpu().numpy(), ref.tri) and np.array_equal(lab.cpu().numpy(), ref.labels)
     m = mesh.extract_mesh(dev(vol), ids=dev(ids), resolution=res)
     assert m['labels'].shape[0] == m['vertices'].shape[0] and m['rgb'].shape == (m['vertices'].shape[0], 3)
     assert m['rgb'].min() >= 0 and m['rgb'].max() <= 1
