@@ -466,6 +466,10 @@ int ojf_integrate_many(int n, const ojf_integrate_job *jobs, int n_points, int n
  * ojf_seg_softmax_max: pipeline.py:57,183 softmax over the classes then max: scores f32[npix], ids u8[npix]; the id is the
  *   first maximum.  A row that holds a NaN or a +Inf, or only -Inf, is all-NaN after the reference's softmax, whose max is
  *   then its first element: score NaN, id 0 (not the index of the NaN / +Inf).
+ * ojf_seg_softmax: the whole distribution of the same softmax, probs_dev f32[npix] rows of out_stride >= n_classes floats
+ *   (the floats behind the classes are not written): p_c = exp(l_c - l_max) / sum_j exp(l_j - l_max) with
+ *   ojf_seg_softmax_max's l_max, summation order and bad-row rule (such a row is NaN in every class).  The largest value of
+ *   a row has the bits of ojf_seg_softmax_max's score, and its first arg max is that call's id.
  * ojf_seg_pool_fc: the squeeze chains of eASPP branch 5 (adapnet.py:204-210) and Decoder._skip (:292-296) as two launches
  *   for n (1..8) members: out_m[p][c] = act(bias[c] + sum_k W[c][k] * mean_p' in_m[p'][k]) (* mul_m[p][c]) for every pixel p
  *   of the OUTPUT map - global average (two fixed-order stages), a 1x1 convolution on the 1x1 map in fp32 (W_dev [c_out][c_in],
@@ -485,6 +489,8 @@ int ojf_seg_pool_fc(int n, const float *const *ins_dev, int in_stride, int c_in,
                     float *const *outs_dev, int out_stride, int npix_out, float *partial_dev, ojf_stream_t stream);
 int ojf_seg_softmax_max(const float *logits_dev, int stride, int n_classes, int npix, float *scores_dev, uint8_t *ids_dev,
                         ojf_stream_t stream);
+int ojf_seg_softmax(const float *logits_dev, int stride, int n_classes, int npix, float *probs_dev, int out_stride,
+                    ojf_stream_t stream);
 
 /* ---- VOLUME HELPERS (Database) -------------------------------------------------------------
  * ojf_volume_fill_*: Database.reset (modules/database.py:351-370).
@@ -652,6 +658,37 @@ int ojf_color_sample(const uint16_t *color_dev, int X, int Y, int Z, const float
 int ojf_color_render(const uint16_t *color_dev, int X, int Y, int Z, const double *origin_host, double resolution, int n,
                      const float *Kinv_host, const float *E_host, const float *depth_dev, int h, int w,
                      uint8_t *rgba_dev /* u8[n,h,w,4] */, ojf_stream_t stream);
+
+/* ---- LABELS (a per-voxel class distribution and the labels decided from it; no counterpart in the reference) -----------
+ * The label volume probs_vol_dev is fp16 [X,Y,Z,S], voxel-major, 16-byte aligned, S = 8 * ceil((n_classes + 1) / 8) for
+ *   2 <= n_classes <= 256 (a record of S/8 16-byte chunks per voxel): channels 0..n_classes-1 hold the running mean P_k of
+ *   the class probabilities, channel n_classes the weight W (0: nothing fused); all zeros at reset.  The channels behind W
+ *   are padding that no call reads or writes.
+ * ojf_fuse_label_probs: fuses n views (1 <= n <= OJF_LABEL_MAX_VIEWS, one h x w for all) into probs_vol_dev in place.
+ *   Every voxel centre is projected into each view in turn exactly as ojf_fuse_projective does (same constants, nearest
+ *   pixel, depth_dev / mask_dev tests, near); a voxel with -band <= d - zc <= band takes, for every class k,
+ *   P_k = (W*P_k + p_k) / (W + 1), then W = min(W + 1, max_weight), all rounded to fp16 after every view.  The observation
+ *   p comes in exactly one of two forms (the other pointer NULL): probs_dev f32[n,h,w] rows of prob_stride >= n_classes
+ *   floats, p_k = the value if it lies in [0, 1], else 0 (a NaN counts as 0); or labels_dev u8[n,h,w], p_k = 1 for the
+ *   pixel's label and 0 for the others - a pixel whose label is >= n_classes leaves the voxel alone.  band > 0,
+ *   1 <= max_weight <= 2048, near >= 0, pinhole K.  The TSDF / weight volumes are not read.  One owner lane per voxel:
+ *   no atomics, no workspace, the same bits on every run, and n views in one call give the bits of n calls of one view.
+ *   One kernel, never waits.
+ * ojf_label_decide: for every voxel with W > 0, ids_dev u8[X,Y,Z] = the smallest k whose P_k is the largest of the record
+ *   and scores_dev fp16[X,Y,Z] = the bits of that P_k; a voxel whose W is 0, -0, negative or NaN keeps its id and score.
+ *   One kernel, never waits.
+ * Bad arguments (a volume off the 16-byte grid, n_classes outside 2..256, prob_stride < n_classes, both observation forms
+ *   or neither, and what ojf_fuse_projective refuses) are refused before any HIP call.  The exact fp32 operation order is
+ *   in csrc/ojf_labels.hip. */
+#define OJF_LABEL_MAX_VIEWS 32
+int ojf_fuse_label_probs(uint16_t *probs_vol_dev /* fp16 [X,Y,Z,S] */, int n_classes, int X, int Y, int Z,
+                         const double *origin_host, double resolution, int n, const double *K_host /* f64[n][9] */,
+                         const double *E_host /* f64[n][12] */, const float *depth_dev /* f32[n,h,w] */,
+                         const uint8_t *mask_dev /* u8[n,h,w] or NULL */, const float *probs_dev /* f32[n,h,w][prob_stride] or NULL */,
+                         int prob_stride, const uint8_t *labels_dev /* u8[n,h,w] or NULL */, int h, int w, float band,
+                         float max_weight, float near, ojf_stream_t stream);
+int ojf_label_decide(const uint16_t *probs_vol_dev, int n_classes, int X, int Y, int Z, uint8_t *ids_dev /* u8 [X,Y,Z] */,
+                     uint16_t *scores_dev /* fp16 [X,Y,Z] */, ojf_stream_t stream);
 
 /* ---- RASTER (depth, face, label and colour images of a triangle mesh; the reference renders with OpenGL) --------------
  * ojf_rasterize: n views (1 <= n <= OJF_RASTER_MAX_VIEWS, one h x w for all) of the mesh vertices_dev f32[nv][3] (world

@@ -49,6 +49,7 @@ TRACK_TERMS = 29  # include/ojf.h OJF_TRACK_TERMS
 PROJECTIVE_MAX_VIEWS = 32  # include/ojf.h OJF_PROJECTIVE_MAX_VIEWS
 COLOR_MAX_VIEWS = 32  # include/ojf.h OJF_COLOR_MAX_VIEWS
 RASTER_MAX_VIEWS = 32  # include/ojf.h OJF_RASTER_MAX_VIEWS
+LABEL_MAX_VIEWS = 32  # include/ojf.h OJF_LABEL_MAX_VIEWS
 
 
 class ExtractJob(ctypes.Structure):
@@ -149,6 +150,7 @@ SIGNATURES = {
     'ojf_seg_mean': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     'ojf_seg_broadcast': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     'ojf_seg_softmax_max': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    'ojf_seg_softmax': (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
     'ojf_seg_pool_fc': (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
     'ojf_segconv_set_dropout': (_i, [_vp, _vp, _c.c_uint, _i]),
     'ojf_points_within': (_i, [_vp, _sz, _vp, _vp, _vp, _d, _i, _i, _i, _d, _vp, _vp, _vp]),
@@ -171,6 +173,11 @@ SIGNATURES = {
     'ojf_color_sample': (_i, [_vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     # colour volume, X, Y, Z, origin, resolution, n, Kinv, E, depth, h, w, rgba, stream
     'ojf_color_render': (_i, [_vp, _i, _i, _i, _vp, _d, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    # label volume, n_classes, X, Y, Z, origin, resolution, n, K, E, depth, mask, probs, prob_stride, labels, h, w, band, max_weight,
+    # near, stream
+    'ojf_fuse_label_probs': (_i, [_vp, _i, _i, _i, _i, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _f, _f, _f, _vp]),
+    # label volume, n_classes, X, Y, Z, ids, scores, stream
+    'ojf_label_decide': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     # vertices, nv, faces, nf, n, K, E, h, w, near, keys, depth, face, stream
     'ojf_rasterize': (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
     # vertices, nv, faces, nf, n, K, E, h, w, face, face labels, vertex rgba, labels, rgba, stream

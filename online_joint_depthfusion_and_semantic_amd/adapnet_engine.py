@@ -330,6 +330,17 @@ class SegEngine:
         """Pipeline._segmentation(...).max(-1) (modules/pipeline.py:42-60,183): raw batch tensors in - ``image`` [1,3,H,W]
         as the dataset hands it over (divided by 255 here, pipeline.py:44), ``depth`` [1,H,W] / [1,1,H,W] replicated to three
         channels (:50) - per-pixel (scores f32 [H*W], ids u8 [H*W]) out.  Every step is a libojf launch."""
+        return segconv.softmax_max(self._predict_logits(image, depth))
+
+    def predict_probs(self, image, depth=None):
+        """The whole distribution behind ``predict``: f32 [H,W,stride] class probabilities (stride = the class count rounded up
+        to 4, zeros behind the classes) from the same forward pass; their maximum over the classes and its first index are
+        ``predict``'s scores and ids.  What ``label_probs.integrate_label_probs(probs=...)`` takes."""
+        H, W = image.shape[-2:]
+        probs = segconv.softmax(self._predict_logits(image, depth))
+        return probs.view(H, W, probs.shape[1])
+
+    def _predict_logits(self, image, depth):
         if self.fusion:
             first = segconv.pack_input(image.contiguous(), 255.0)
             # DATA.input == 'image': the reference feeds the image to both encoders (modules/pipeline.py:52-55)
@@ -339,4 +350,4 @@ class SegEngine:
             logits = self.forward(segconv.pack_input(depth.contiguous(), 1.0))
         else:
             logits = self.forward(segconv.pack_input(image.contiguous(), 255.0))
-        return segconv.softmax_max(logits)
+        return logits

@@ -48,7 +48,10 @@ def default_config(h=240, w=320, semantics=False, use_semantics=None, n_classes=
                          'growth_factor': 6, 'use_semantics': bool(use_semantics),
                          'arithmetic': 'f16x3',  # 'f16x3' | 'f32' (include/ojf.h OJF_ARITH_*)
                          # also fuse batch['image'] into a colour volume per scene (color.py), within color_band of the surface
-                         'fuse_color': False, 'color_band': init_value},
+                         'fuse_color': False, 'color_band': init_value,
+                         # also cast every fused frame's label image as a one-hot vote into a per-voxel class distribution per
+                         # scene (label_probs.py), within label_band of the surface; Database.decide_labels() turns it into labels
+                         'fuse_label_probs': False, 'label_band': init_value},
         'SEMANTIC_2D_MODEL': {'stage': 2, 'n_classes': n_classes},
         'TRAINING': {'optimization': {'accumulation_steps': 8, 'clipping': True}},
         'TESTING': {'outlier_filter_val': 2, 'track_invalid_poses': False},

@@ -6,6 +6,7 @@
 //   ojf_seg_mean         global average over the pixels (eASPP branch 5, Decoder._skip), fixed summation order
 //   ojf_seg_broadcast    a per-channel vector to every pixel (bilinear upsampling of a 1x1 map), optionally times a tensor
 //   ojf_seg_softmax_max  softmax over the classes + max: (score, id) per pixel
+//   ojf_seg_softmax      the same softmax, all classes written out
 // All are small HBM-streaming kernels: 16 bytes per lane where the row stride allows it.
 #include "ojf_common.h"
 
@@ -107,9 +108,12 @@ __global__ __launch_bounds__(256) void seg_broadcast_kernel(const float *vec, co
 // all-NaN row is (NaN, 0) - its first element: such a row yields score NaN and id 0, wherever its NaN / +Inf sits.
 // VEC: rows are 16-byte aligned - a lane fetches its pixel's classes as float4 (the scalar form issued C 4-byte loads per
 // lane, each spread over 64 cache lines: 20 us for a 320x240 frame with 30 classes; same operations in the same order).
-template <bool VEC>
+// FULL (ojf_seg_softmax): the whole distribution instead, probs[p][c] = exp(l_c - l_max) / sum_j exp(l_j - l_max) with the
+// same l_max, the same sum and the same bad-row rule (NaN to every class) - one text, so that the largest value of a row
+// has the bits of the score above (exp(0) / s = 1 / s) and sits first at the id above.
+template <bool VEC, bool FULL = false>
 __global__ __launch_bounds__(256) void seg_softmax_max_kernel(const float *logits, int stride, int C, int npix, float *scores,
-                                                               uint8_t *ids)
+                                                               uint8_t *ids, float *probs = nullptr, int out_stride = 0)
 {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= npix) return;
@@ -152,8 +156,19 @@ __global__ __launch_bounds__(256) void seg_softmax_max_kernel(const float *logit
     } else {
         for (int c = 0; c < C; ++c) s += expf(l[c] - m);
     }
-    scores[p] = bad ? __builtin_nanf("") : 1.0f / s;
-    ids[p] = bad ? (uint8_t)0 : (uint8_t)am;
+    if constexpr (FULL) {
+        float *o = probs + (size_t)p * out_stride;
+        if constexpr (VEC) {
+#pragma unroll
+            for (int c = 0; c < kMaxVec; ++c)
+                if (c < C) o[c] = bad ? __builtin_nanf("") : expf(v[c] - m) / s;
+        } else {
+            for (int c = 0; c < C; ++c) o[c] = bad ? __builtin_nanf("") : expf(l[c] - m) / s;
+        }
+    } else {
+        scores[p] = bad ? __builtin_nanf("") : 1.0f / s;
+        ids[p] = bad ? (uint8_t)0 : (uint8_t)am;
+    }
 }
 
 // ---- squeeze chains: global average -> 1x1 convolution on the 1x1 map -> broadcast (x gate) ------------------------------
@@ -323,6 +338,19 @@ OJF_API int ojf_seg_softmax_max(const float *logits, int stride, int n_classes, 
     if (vec) hipLaunchKernelGGL(seg_softmax_max_kernel<true>, dim3((npix + 255) / 256), dim3(256), 0, as_stream(stream), logits, stride, n_classes, npix, scores, ids);
     else hipLaunchKernelGGL(seg_softmax_max_kernel<false>, dim3((npix + 255) / 256), dim3(256), 0, as_stream(stream), logits, stride, n_classes, npix, scores, ids);
     return check_hip(hipGetLastError(), "seg_softmax_max_kernel launch");
+}
+
+OJF_API int ojf_seg_softmax(const float *logits, int stride, int n_classes, int npix, float *probs, int out_stride, ojf_stream_t stream)
+{
+    using namespace ojf;
+    if (!logits || !probs || n_classes < 1 || n_classes > 256 || npix < 1 || stride < n_classes || out_stride < n_classes)
+        return fail("ojf_seg_softmax: bad argument");
+    if (((uintptr_t)logits & 3) || ((uintptr_t)probs & 3)) return fail("ojf_seg_softmax: logits_dev and probs_dev must be 4-byte aligned");
+    // (the vector form of the loads, under ojf_seg_softmax_max's conditions; the stores are per class either way)
+    const bool vec = n_classes <= 64 && stride % 4 == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0 && stride >= (n_classes + 3) / 4 * 4;
+    if (vec) hipLaunchKernelGGL((seg_softmax_max_kernel<true, true>), dim3((npix + 255) / 256), dim3(256), 0, as_stream(stream), logits, stride, n_classes, npix, (float *)nullptr, (uint8_t *)nullptr, probs, out_stride);
+    else hipLaunchKernelGGL((seg_softmax_max_kernel<false, true>), dim3((npix + 255) / 256), dim3(256), 0, as_stream(stream), logits, stride, n_classes, npix, (float *)nullptr, (uint8_t *)nullptr, probs, out_stride);
+    return check_hip(hipGetLastError(), "seg_softmax_kernel launch");
 }
 
 OJF_API int ojf_seg_pool_fc(int n, const float *const *ins, int in_stride, int c_in, int npix_in, const float *const *weights,

@@ -60,6 +60,7 @@ class Database(torch.utils.data.Dataset):
         self.scenes_gt, self.scenes_est, self.fusion_weights = {}, {}, {}
         self.ids_gt, self.ids_est, self.scores = {}, {}, {}
         self.colors = {}  # scene -> fp16 [X,Y,Z,4] colour volume (color.py), only for scenes integrate_color was called on
+        self.label_probs = {}  # scene -> fp16 [X,Y,Z,S] class distribution (label_probs.py), only for scenes integrate_label_probs was called on
         self.tracked_poses = {}  # frame_id -> f64 [4,4] camera-to-world: frames fused with a tracked pose (drivers.test_fusion)
 
         for s in dataset.scenes:
@@ -99,6 +100,8 @@ class Database(torch.utils.data.Dataset):
             sample.update(histograms=None, ids_est=None, ids_gt=None, scores=None)
         if self.colors.get(item) is not None:
             sample['colors'] = self.colors[item]
+        if self.label_probs.get(item) is not None:
+            sample['label_probs'] = self.label_probs[item]
         return sample
 
     def __len__(self):
@@ -117,6 +120,8 @@ class Database(torch.utils.data.Dataset):
             self.fusion_weights[s] = self._dev(self.fusion_weights[s])
             if self.colors.get(s) is not None:
                 self.colors[s] = self._dev(self.colors[s])
+            if self.label_probs.get(s) is not None:
+                self.label_probs[s] = self._dev(self.label_probs[s])
             if gt:
                 o = self.origin[s]
                 self.origin[s] = o.double().cpu() if torch.is_tensor(o) else torch.from_numpy(np.asarray(o, np.float64))
@@ -137,6 +142,8 @@ class Database(torch.utils.data.Dataset):
             self.fusion_weights[s] = host(self.fusion_weights[s])
             if self.colors.get(s) is not None:
                 self.colors[s] = host(self.colors[s])
+            if self.label_probs.get(s) is not None:
+                self.label_probs[s] = host(self.label_probs[s])
             if self.semantics:
                 self.ids_est[s].volume = host(self.ids_est[s].volume)
                 self.scores[s].volume = host(self.scores[s].volume)
@@ -153,6 +160,11 @@ class Database(torch.utils.data.Dataset):
                 ops.volume_fill(c, 0.0)
             elif c is not None:
                 self.colors[s] = np.zeros(c.shape, dtype=np.float16)  # (a host volume; goes up with the rest below)
+            p = self.label_probs.get(s)
+            if _is_dev(p):
+                ops.volume_fill(p, 0.0)
+            elif p is not None:
+                self.label_probs[s] = np.zeros(p.shape, dtype=np.float16)
             if _is_dev(self.scenes_est[s].volume):
                 ops.volume_fill(self.scenes_est[s].volume, self.initial_value)
                 ops.volume_fill(self.fusion_weights[s], 0.0)
@@ -174,6 +186,7 @@ class Database(torch.utils.data.Dataset):
         self.scenes_gt[scene_id] = None
         self.fusion_weights[scene_id] = None
         self.colors.pop(scene_id, None)
+        self.label_probs.pop(scene_id, None)
         if self.semantics:
             self.ids_est[scene_id] = None
             self.scores[scene_id] = None
@@ -359,6 +372,44 @@ class Database(torch.utils.data.Dataset):
                               depth=dev(depth), intrinsics=intrinsics, extrinsics=extrinsics, mask=dev(mask), **kw)
         self.colors[scene_id] = vol  # (a refused call leaves a scene without a colour volume without one)
 
+    def integrate_label_probs(self, scene_id, depth, intrinsics, extrinsics, mask=None, probs=None, labels=None, **kw):
+        """Fuse the label observations of one or more frames into the scene's class-distribution volume (label_probs.py;
+        allocated, zeroed, on first use): exactly one of ``probs`` (float [n,]h,w,>=n_classes, a distribution per pixel -
+        ``SegEngine.predict_probs``) and ``labels`` (u8 [n,]h,w, a one-hot vote per pixel); depth / mask / poses of the same
+        frames as for ``integrate_depth``; ``kw`` goes to ``label_probs.integrate_label_probs`` (band - default: the initial
+        value -, max_weight, near).  Geometry, ids_est and scores are not touched: ``decide_labels`` writes the labels."""
+        from . import label_probs
+        if not self.semantics:
+            raise ValueError('Database.integrate_label_probs: the database has no semantics (n_classes)')
+        tsdf = self.scenes_est[scene_id].volume
+        if not _is_dev(tsdf) or not (self.label_probs.get(scene_id) is None or _is_dev(self.label_probs[scene_id])):
+            raise ValueError('Database.integrate_label_probs: the volumes of {!r} are not resident on the device (to_torch())'.format(scene_id))
+        kw.setdefault('band', self.initial_value)
+        fresh = self.label_probs.get(scene_id) is None
+        vol = label_probs.new_volume(tsdf.shape, self.n_classes, tsdf.device) if fresh else self.label_probs[scene_id]
+
+        def dev(x):
+            return None if x is None else torch.as_tensor(x).to(tsdf.device)
+        label_probs.integrate_label_probs(vol, self.n_classes, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]),
+                                          depth=dev(depth), intrinsics=intrinsics, extrinsics=extrinsics, mask=dev(mask),
+                                          probs=dev(probs), labels=dev(labels), **kw)
+        self.label_probs[scene_id] = vol  # (a refused call leaves a scene without a volume without one)
+
+    def decide_labels(self, scene_id=None):
+        """Write the decision of the class-distribution volumes - of one scene, or of every scene that has one - into ids_est /
+        scores (label_probs.decide_labels): a voxel with a vote takes the first class of its largest mean and that mean, the
+        others keep what they hold.  Everything that reads ids_est (evaluate_semantics, filter_semantics, render, get_mesh, save)
+        sees the decided labels from then on."""
+        from . import label_probs
+        for s in ([scene_id] if scene_id is not None else list(self.label_probs)):
+            vol = self.label_probs.get(s)
+            if vol is None:
+                raise ValueError('Database.decide_labels: scene {!r} has no class-distribution volume (integrate_label_probs)'.format(s))
+            ids, scores = self.ids_est[s].volume, self.scores[s].volume
+            if not (_is_dev(vol) and _is_dev(ids) and _is_dev(scores)):
+                raise ValueError('Database.decide_labels: the volumes of {!r} are not resident on the device (to_torch())'.format(s))
+            label_probs.decide_labels(vol, self.n_classes, ids, scores)
+
     def save_to_workspace(self, workspace, mode, save_mode='ply'):
         """database.py:141-177: every scene that holds integrated frames goes to the workspace's output directory as
         ``<scene>.tsdf_<mode>.hf5`` / ``.weights_<mode>.hf5`` / ``.semantic_<mode>.hf5`` ('tsdf'), ``<scene>_<mode>.ply``
@@ -381,7 +432,8 @@ class Database(torch.utils.data.Dataset):
     def save(self, path, save_mode='ply', scene_id=None, palette=None):
         """database.py:172-261: 'tsdf' (volumes), 'ply' (mesh), 'test' (volumes + mesh + label-coloured mesh whose
         alpha channel carries the label id).  A scene with a colour volume also gets ``<scene>_color.ply`` (the mesh with
-        its sampled vertex colours, alpha 255 where coloured) beside every mesh and ``<scene>.color.hf5`` beside the volumes."""
+        its sampled vertex colours, alpha 255 where coloured) beside every mesh and ``<scene>.color.hf5`` beside the volumes; a scene
+        with a class-distribution volume gets ``<scene>.label_probs.hf5`` there."""
         if scene_id is None:
             raise NotImplementedError
         if save_mode not in ('tsdf', 'ply', 'test'):
@@ -412,6 +464,8 @@ class Database(torch.utils.data.Dataset):
             arrays['semantics'] = ('semantics', host(self.ids_est[scene_id].volume))
         if self.colors.get(scene_id) is not None:
             arrays['color'] = ('color', host(self.colors[scene_id]))
+        if self.label_probs.get(scene_id) is not None:
+            arrays['label_probs'] = ('label_probs', host(self.label_probs[scene_id]))
         from .datasets import save_volume_hdf
         for name, (key, arr) in arrays.items():  # same file / dataset names as database.py:184-201 (npz without h5py)
             save_volume_hdf(os.path.join(path, '{}.{}.hf5'.format(base, name)), key, arr)

@@ -302,7 +302,9 @@ class Pipeline(torch.nn.Module):
         but the 2-D network does not depend on the volumes: with ``semantic_strategy: predict`` the labels of all the frames
         are predicted first, as ONE batched AdapNet++ pass (SegEngine.predict_many: 0.62 / 0.48 ms per frame at four / eight
         frames per pass against 1.20 ms one at a time).  Same volumes as the separate calls, with the batched
-        pass's rounding of the scores (include/ojf.h, ojf_segconv_forward_batch).  The reference predicts and fuses one frame
+        pass's rounding of the scores (include/ojf.h, ojf_segconv_forward_batch).  With FUSION_MODEL.fuse_label_probs every frame's
+        label image - the ids of that pass, or semantic_gt - also votes in its scene's class-distribution volume, right after its
+        frame step.  The reference predicts and fuses one frame
         at a time (test_fusion.py:68-80); a driver that reads a recorded stream can hand over chunks (drivers.test_fusion does).
 
         ``prefetch``: the chunk the NEXT call will bring (the same batch objects).  Its batched 2-D pass is enqueued on a
@@ -323,24 +325,25 @@ class Pipeline(torch.nn.Module):
         for b, sem in zip(batches, sems):
             self._fuse_guarded(b, database, sem, fp, recover)
             self._fuse_colors([b], database)
+            self._fuse_labels([b], [sem[0]], database)
 
     def _fuse_guarded(self, batch, database, sem=None, fingerprint=None, recover=False):
         """One frame step of fuse_sequence / fuse_many's sequential paths under FUSION_MODEL.guard_policy (what ``fuse`` does
         for its one frame): with 'f32' a fired range guard switches the arithmetic, fuses the skipped frames again and goes
         on with this one; the frame joins the ring of remembered batches.  ``sem`` (the frame's labels from a batched 2-D
         pass) does not depend on the fusion net's arithmetic and is used either way; the re-fused frames predict theirs
-        again, one frame at a time."""
+        again, one frame at a time.  Returns the frame's label image (``_fuse_frame``)."""
         if not recover:
             return self._fuse_frame(batch, database, 0, sem, fingerprint)
         try:
-            self._fuse_frame(batch, database, 0, sem, fingerprint)
+            sem_ids = self._fuse_frame(batch, database, 0, sem, fingerprint)
         except _lib.OjfError as err:
             if 'fp16 range' not in str(err):
                 raise
             self._guard_recover(err)
-            self._fuse_frame(batch, database, 0, sem)  # (fp32 engine: a new fingerprint)
-            return
+            return self._fuse_frame(batch, database, 0, sem)  # (fp32 engine: a new fingerprint)
         self._guard_remember(batch, database)
+        return sem_ids
 
     def _batched_2d_pass_applies(self, batches):
         cfg = self.config
@@ -625,8 +628,9 @@ class Pipeline(torch.nn.Module):
             return self._fuse_classical([batch], [None], database)
         # (a frame the forward call's poll refuses was raised BEFORE its net / integrate were enqueued: it is not among the
         # skipped ones, it follows them - _fuse_guarded)
-        self._fuse_guarded(batch, database, recover=self._guard_policy() == 'f32')
+        sem_ids = self._fuse_guarded(batch, database, recover=self._guard_policy() == 'f32')
         self._fuse_colors([batch], database)
+        self._fuse_labels([batch], [sem_ids], database)
 
     # ---- FUSION_MODEL.fuse_color: the frames' colour images into the scenes' colour volumes (color.py) -----------------------
     def _color_options(self):
@@ -649,9 +653,40 @@ class Pipeline(torch.nn.Module):
             database.integrate_color(b['frame_id'][0].split('/')[0], b['image'].to(self.device), frame.unsqueeze(0),
                                      b['intrinsics'][0], b['extrinsics'][0], mask=mask.unsqueeze(0), **kw)
 
+    # ---- FUSION_MODEL.fuse_label_probs: the frames' label images as one-hot votes into the scenes' class distributions ---------
+    def _label_options(self):
+        """None (FUSION_MODEL.fuse_label_probs off, the default) or the keywords of Database.integrate_label_probs: label_band
+        (default DATA.init_value)."""
+        fm = self.config.FUSION_MODEL
+        if not fm.get('fuse_label_probs', False):
+            return None
+        if not self.config.DATA.semantics:
+            raise ValueError('Pipeline: FUSION_MODEL.fuse_label_probs needs DATA.semantics (label images and a class count)')
+        return dict(band=fm.get('label_band', None) or self.config.DATA.init_value)
+
+    def _fuse_labels(self, batches, label_images, database):
+        """The learned modes' label-vote step: the label image of every frame, in order, as a one-hot vote
+        (label_probs.integrate_label_probs(labels=...)) into its scene's class-distribution volume with the depth frame, mask
+        and pose its frame step used, on the current stream.  ``label_images[i]``: the ids the frame step of batch i fused
+        (u8, h*w; ``_fuse_frame`` returns them - with ``semantic_strategy: predict`` the 2-D network is not run a second time),
+        or None: ``batch['semantic_gt']``, the label image of strategy 'gt'.  ids_est / scores are not touched here:
+        Database.decide_labels() writes them."""
+        kw = self._label_options()
+        if kw is None:
+            return
+        for b, ids in zip(batches, label_images):
+            frame, mask = self._frames(b, filtered=False)
+            if ids is None:
+                if self.config.DATA.semantic_strategy != 'gt':
+                    raise ValueError('Pipeline: fuse_label_probs has no label image for this frame (semantic_strategy predict)')
+                ids = b['semantic_gt']
+            labels = ids.to(self.device).to(torch.uint8).reshape((1,) + tuple(frame.shape))
+            database.integrate_label_probs(b['frame_id'][0].split('/')[0], frame.unsqueeze(0), b['intrinsics'][0], b['extrinsics'][0],
+                                           mask=mask.unsqueeze(0), labels=labels, **kw)
+
     def _fuse_frame(self, batch, database, slot=0, semantics=None, fingerprint=None):
         """One frame step on the current stream with the device state of ``slot``; ``semantics`` = (sem_ids, scores) computed
-        by the caller (fuse_many) instead of here."""
+        by the caller (fuse_many) instead of here.  Returns the frame's label image sem_ids (u8 [h*w], None without semantics)."""
         self._refuse_tripped_guard('Pipeline.fuse')
         profiled = slot == 0 and semantics is None
         seg0 = self._mark_segmentation() if profiled else None
@@ -690,6 +725,7 @@ class Pipeline(torch.nn.Module):
                       mode=self._integrate_mode, mask=mask)  # filtered frame of pipeline.py:196 formed in the kernels
         mark()
         self._commit_frame(database, scene_id, volume)
+        return sem_ids
 
     # ---- FUSION_MODEL.name 'tsdf': classical projective TSDF averaging, no network (projective.py) -------------------------
     def _fuse_classical(self, batches, sems, database):
@@ -698,7 +734,8 @@ class Pipeline(torch.nn.Module):
         ``_lib.PROJECTIVE_MAX_VIEWS`` views (the same bits as a call per frame), and the same side effects on ``database``.
         ``sems[i]``: the frame's (sem_ids, scores) from a batched 2-D pass, or None.  FUSION_MODEL keys: truncation
         (default DATA.init_value), max_weight (128), carve (False); with fuse_color, the images of a run go into the scene's
-        colour volume as one call as well."""
+        colour volume as one call as well, and with fuse_label_probs its label images (the sem_ids the depth call fuses) into
+        the scene's class-distribution volume."""
         from . import projective
         fm = self.config.FUSION_MODEL
         kw = dict(truncation=fm.get('truncation', None) or self.config.DATA.init_value,
@@ -706,6 +743,7 @@ class Pipeline(torch.nn.Module):
         self._refuse_tripped_guard('Pipeline.fuse')  # (the labels of a 2-D pass that tripped the guard must not reach a volume)
         sem = bool(self.config.DATA.semantics)
         color_kw = self._color_options()
+        label_kw = self._label_options()
         run, run_key = [], None
 
         def flush():
@@ -725,6 +763,10 @@ class Pipeline(torch.nn.Module):
                 database.integrate_color(scene_id, torch.cat([r[6] for r in run]), torch.stack([r[0] for r in run]),
                                          torch.stack([r[2] for r in run]), torch.stack([r[3] for r in run]),
                                          mask=torch.stack([r[1] for r in run]), **color_kw)
+            if label_kw is not None:
+                database.integrate_label_probs(scene_id, torch.stack([r[0] for r in run]), torch.stack([r[2] for r in run]),
+                                               torch.stack([r[3] for r in run]), mask=torch.stack([r[1] for r in run]),
+                                               labels=torch.stack([r[4] for r in run]), **label_kw)
             del run[:]
 
         for b, s in zip(batches, sems):
@@ -751,10 +793,16 @@ class Pipeline(torch.nn.Module):
         already run this way).  With ``semantic_strategy: predict`` the 2-D network of the S frames runs first, on the current
         stream (one engine).  The reference has no counterpart: its drivers fuse one frame at a time
         (test_fusion.py:68-80).  With FUSION_MODEL.fuse_color the frames' colour calls follow on the current stream, after the
-        join."""
+        join, and with FUSION_MODEL.fuse_label_probs their label votes - for ``semantic_strategy: gt``; the learned modes refuse
+        'predict' here (the ids of the batched 2-D pass stay inside the side-by-side frame steps; ``fuse`` and ``fuse_sequence``
+        take it, and so does the classical mode)."""
+        if not self._classical and self._label_options() is not None and self.config.DATA.semantic_strategy == 'predict':
+            raise ValueError('Pipeline.fuse_many: FUSION_MODEL.fuse_label_probs with semantic_strategy "predict" is supported by '
+                             'fuse and fuse_sequence only (and by FUSION_MODEL.name "tsdf")')
         self._fuse_many_frames(batches, database, device)
-        if not self._classical:  # (the classical frame steps bring their colour calls along)
+        if not self._classical:  # (the classical frame steps bring their colour and label calls along)
             self._fuse_colors(batches, database)
+            self._fuse_labels(batches, [None] * len(batches), database)
 
     def _fuse_many_frames(self, batches, database, device):
         self.device = torch.device(device)

@@ -322,3 +322,15 @@ def softmax_max(logits):
     _lib.check(lib.ojf_seg_softmax_max(lp, ls, C, B * H * W, scores.data_ptr(), ids.data_ptr(), _lib.stream_ptr(logits.device)),
                'ojf_seg_softmax_max')
     return scores, ids
+
+
+def softmax(logits):
+    """torch.softmax(logits, 1) of an NHWC view [B, C, H, W] -> f32 [B*H*W, stride] rows (stride = C rounded up to 4; the
+    floats behind the classes are zero): the distribution whose row maximum and first arg max ``softmax_max`` returns."""
+    lib = _lib.load()
+    B, C, H, W = logits.shape
+    stride = (C + 3) // 4 * 4
+    probs = torch.zeros((B * H * W, stride), dtype=torch.float32, device=logits.device)
+    lp, ls = _rows(logits)
+    _lib.check(lib.ojf_seg_softmax(lp, ls, C, B * H * W, probs.data_ptr(), stride, _lib.stream_ptr(logits.device)), 'ojf_seg_softmax')
+    return probs
