@@ -155,6 +155,7 @@ struct ConvArgs {
     // grouped launch fetched 40 MB for a 24.6-MB input, profiles/r05_final_traffic_pmc.txt); in class order the halo is one
     // row on either side of the band.  Which block computes which pixels changes, nothing else: the same bits.
     int row_perm = 0, perm_q = 0, perm_rem = 0;  // r (0: off), h / r, h % r
+    const f32x4 *wp_rows = nullptr;  // the layer's weights in tap-row order (conv_f16x3_rows_kernel), NULL: not packed for it
 };
 
 // position `pr` of the row order (y mod r, y div r) -> row y; classes c < h % r have h / r + 1 rows, the others h / r
@@ -270,8 +271,9 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs &a, const f32x4 (&a
 // scale pointers): the same operations on the same values in the same order, i.e. the same bits, in ~1/3 of the
 // instructions (the grouped 19 -> 19 convolutions issue 9 VALU per MFMA and half of a wave's instructions were its
 // prologue and epilogue: r03_final_inst_counters.txt).  The host picks it per launch (conv_lean_ok).
+// tile0[m]: first pixel of the wave's 16-pixel tile m
 template <int MT, int NT>
-__device__ __forceinline__ void conv_epilogue_lean(const ConvArgs &a, const f32x4 (&acc)[MT][NT], int strip, int i16, int g,
+__device__ __forceinline__ void conv_epilogue_lean(const ConvArgs &a, const f32x4 (&acc)[MT][NT], const int (&tile0)[MT], int i16, int g,
                                                    const f32x4 (&bvec)[NT], const f32x4 (&rvec)[NT])
 {
     const float slope = act_slope(a.act);
@@ -282,7 +284,7 @@ __device__ __forceinline__ void conv_epilogue_lean(const ConvArgs &a, const f32x
         if (og >= a.og_store) continue;
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
-            const int p = strip + m * 16 + i16;
+            const int p = tile0[m] + i16;
             const f32x4 lin4 = fma4(acc[m][n], rvec[n], bvec[n]);
             const f32x4 v = leaky_max4(lin4, slope);
             if (p < a.npix) {
@@ -722,9 +724,157 @@ __global__ __launch_bounds__(256, (MT == 2 && NT == 2 && LEAN) ? 4 : 1) void con
             rvec[n] = *reinterpret_cast<const f32x4 *>(a.rinv + (size_t)n * 16 + 4 * g);
         }
     }
-    if constexpr (LEAN) conv_epilogue_lean<MT, NT>(a, acc, strip, i16, g, bvec, rvec);
-    else conv_epilogue<MT, NT, true>(a, acc, strip, i16, g, bvec, rvec);
+    if constexpr (LEAN) {
+        int tile0[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) tile0[m] = strip + m * 16;
+        conv_epilogue_lean<MT, NT>(a, acc, tile0, i16, g, bvec, rvec);
+    } else {
+        conv_epilogue<MT, NT, true>(a, acc, strip, i16, g, bvec, rvec);
+    }
     }  // (pixel blocks of a persistent block)
+}
+
+// ------------------------------------------------------------------------------------------------
+// Row-pair form of the banded, lean, split-plane grouped 3x3 launches (the four branches' dilated 19 -> 19 convolutions).
+// conv_f16x3_kernel gives a wave 32 consecutive pixels of one row: its two tiles fetch three tap rows each, "every operand
+// once per tap" (24 one-KB loads per wave).  Here a wave's two tiles are the same 16 columns of two rows that are neighbours in
+// the launch's row order - (y mod r, y div r) under row_perm, y otherwise - i.e. `dil` apart inside a dilation class: each is a
+// tap row of the other, so the pair reads FOUR source rows instead of six (16 loads), and the registers of tile 1's row are
+// tile 0's operands one tap row later.  Pairs that are not `dil` apart (a pair straddling two classes, dil >= h) run the same
+// code on six rows.
+//   band position sb -> pair k = sb / (w / 64), column group c = sb % (w / 64); wave v owns columns 64 c + 16 v .. + 15;
+//   tile m is row perm_row(2 k + m) (plain 2 k + m without row_perm).  With w % 64 == 0 and h even (the host checks) there
+//   are (h / 2)(w / 64) positions - the very nblocks of the old form: grid, bands and the persistent walk are the same.
+// K is walked by tap row ky = 0, 1, 2, two supersteps of 16 slots each, slot = kx * c4 + cg (3 c4 <= 16; the slots behind
+// are dead: zero weights, their loads masked out of range): lane group g owns slots 2g, 2g + 1 of the first and 8 + 2g,
+// 9 + 2g of the second superstep - four float4 (16 registers) per source row, whose plane offsets and tap columns never
+// change: no tap table.
+// The weights are a stream of their own (PackedConv::wp_rows, 6 supersteps = 24 KB, copied to LDS once per block).
+// A pixel's sum does not depend on the path: both accumulate ky = 0, 1, 2 from the same fragments and skip exactly the
+// tap rows outside the image (no loads, no MFMAs).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256, 3) void conv_f16x3_rows_kernel(const ConvGroup grp)
+{
+    constexpr int NT = 2, CS = 6;
+    const ConvArgs &a = grp.g[blockIdx.y];
+    int sb = xcd_band_block(blockIdx.x, gridDim.x);
+    int sb_end = sb + 1, sb_step = 1;
+    if (grp.band) {  // persistent: as in conv_f16x3_kernel
+        const int x = blockIdx.x & 7, j = blockIdx.x >> 3;
+        sb = x * grp.band + j;
+        sb_end = (x + 1) * grp.band;
+        sb_step = (int)(gridDim.x >> 3);
+    }
+    if (sb >= grp.nblocks) return;  // padding block
+    __shared__ f32x4 wl[CS * NT * 128];
+#pragma unroll
+    for (int i = 0; i < CS * NT * 128 / 256; ++i) wl[i * 256 + threadIdx.x] = a.wp_rows[i * 256 + threadIdx.x];
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i16 = lane & 15, g = lane >> 4;
+    // this lane's four slots: byte offset of (plane, tap column) relative to the pixel, and the tap column's bit (0: dead slot)
+    int soff[4];
+    unsigned sbit[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int slot = (j >> 1) * 8 + 2 * g + (j & 1);
+        const int kx = fast_div(slot, a.c4, a.c4_magic), cg = slot - kx * a.c4;
+        const bool on = kx < 3;
+        soff[j] = on ? ((a.in_g0 + cg) * a.npix + (kx - 1) * a.dil) * 16 : 0;
+        sbit[j] = on ? 1u << kx : 0u;
+    }
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<f32x4 *>(a.in), 0, (a.in_g0 + a.c4) * a.npix * 16, 0x00020000);
+    f32x4 bvec[NT], rvec[NT];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+        bvec[n] = *reinterpret_cast<const f32x4 *>(a.bias + (size_t)n * 16 + 4 * g);
+        rvec[n] = *reinterpret_cast<const f32x4 *>(a.rinv + (size_t)n * 16 + 4 * g);
+    }
+    const int cgroups = a.w >> 6;
+    __syncthreads();  // the weights
+
+    for (; sb < sb_end && sb < grp.nblocks; sb += sb_step) {
+        const int k = sb / cgroups, px = (sb - k * cgroups) * 64 + wave * 16 + i16;
+        int row0 = 2 * k, row1 = 2 * k + 1;
+        if (a.row_perm) {
+            row0 = perm_row(row0, a.row_perm, a.perm_q, a.perm_rem);
+            row1 = perm_row(row1, a.row_perm, a.perm_q, a.perm_rem);
+        }
+        unsigned cm = 0;  // bit kx: tap column kx of this lane's pixel lies inside the image
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) cm |= ((unsigned)(px + (kx - 1) * a.dil) < (unsigned)a.w ? 1u : 0u) << kx;
+        unsigned sinv[4];  // all ones for a slot that reads nothing: the buffer load then returns zeros
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sinv[j] = (cm & sbit[j]) ? 0u : 0xffffffffu;
+
+        // one source row: four loads per lane; a row outside the image costs nothing (and is never consumed)
+        auto fetch = [&](f32x4(&x)[4], int r) {
+            if ((unsigned)r < (unsigned)a.h) {
+                const int p16 = (r * a.w + px) * 16;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    x[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)(soff[j] + p16) | sinv[j], 0, 0));
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) x[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        };
+        f32x4 acc[2][NT];
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int n = 0; n < NT; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // tap row ky: tile 0 consumes source row x0 (if it lies inside the image: on0), tile 1 x1 - the same weight fragments
+        auto mac = [&](int ky, const f32x4(&x0)[4], bool on0, const f32x4(&x1)[4], bool on1) {
+            if (!on0 && !on1) return;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                f32x4 wh[NT], wlo[NT];
+#pragma unroll
+                for (int n = 0; n < NT; ++n) {
+                    wh[n] = wl[((ky * 2 + s) * NT + n) * 128 + lane];
+                    wlo[n] = wl[((ky * 2 + s) * NT + n) * 128 + 64 + lane];
+                }
+                f16x8 xh, xl;
+                if (on0) {
+                    unpack_split(x0[2 * s], x0[2 * s + 1], xh, xl);
+#pragma unroll
+                    for (int n = 0; n < NT; ++n) acc[0][n] = mfma_f16x3(wh[n], wlo[n], xh, xl, acc[0][n]);
+                }
+                if (on1) {
+                    unpack_split(x1[2 * s], x1[2 * s + 1], xh, xl);
+#pragma unroll
+                    for (int n = 0; n < NT; ++n) acc[1][n] = mfma_f16x3(wh[n], wlo[n], xh, xl, acc[1][n]);
+                }
+            }
+        };
+        auto inside = [&](int r) { return (unsigned)r < (unsigned)a.h; };
+        const int d = a.dil;
+        f32x4 xa[4], xb[4], xc[4], xd[4];
+        if (row1 == row0 + d) {  // (wave-uniform) four source rows: row0 - d, row0, row1, row1 + d
+            fetch(xa, row0 - d);
+            fetch(xb, row0);
+            fetch(xc, row1);
+            fetch(xd, row1 + d);
+            mac(0, xa, inside(row0 - d), xb, true);
+            mac(1, xb, true, xc, true);
+            mac(2, xc, true, xd, inside(row1 + d));
+        } else {  // independent tiles: six source rows
+            fetch(xa, row0 - d);
+            fetch(xb, row1 - d);
+            fetch(xc, row0);
+            fetch(xd, row1);
+            mac(0, xa, inside(row0 - d), xb, inside(row1 - d));
+            fetch(xa, row0 + d);
+            fetch(xb, row1 + d);
+            mac(1, xc, true, xd, true);
+            mac(2, xa, inside(row0 + d), xb, inside(row1 + d));
+        }
+        const int tile0[2] = {row0 * a.w + px - i16, row1 * a.w + px - i16};
+        conv_epilogue_lean<2, NT>(a, acc, tile0, i16, g, bvec, rvec);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1582,6 +1732,7 @@ struct PackedConv {
     float *wp = nullptr;    // device; layout depends on arith
     float *bias = nullptr;  // device, n_ot*16 floats
     float *rinv = nullptr;  // device, n_ot*16 floats (split-fp16 only)
+    float *wp_rows = nullptr;  // device; split-fp16 3x3 layers of two output tiles with 3 c4 <= 16: the tap-row stream (rows_form_packed)
     int c_in_phys = 0, c_out_phys = 0, taps = 1, dil = 1, n_ot = 0;
     int arith = OJF_ARITH_F32, nsteps = 0;  // supersteps: 4 (fp32) or 8 (split-fp16) K entries each
 };
@@ -1739,6 +1890,12 @@ static int upload(const std::vector<float> &h, float **d)
     return 0;
 }
 
+// layers that get a second weight stream for the row-pair form of the grouped launches (launch_conv_args decides per launch)
+static inline bool rows_form_packed(int arith, int taps, int c4, int n_ot)
+{
+    return arith == OJF_ARITH_F16X3 && taps == 9 && 3 * c4 <= 16 && n_ot == 2;
+}
+
 static int finish(const ConvBuilder &b, PackedConv &pc, int arith = OJF_ARITH_F32)
 {
     if (b.c_in_phys % 4) return fail("conv packing: c_in_phys must be a multiple of 4");
@@ -1753,7 +1910,7 @@ static int finish(const ConvBuilder &b, PackedConv &pc, int arith = OJF_ARITH_F3
     const int nsteps = (groups + per - 1) / per;
     if (nsteps > kMaxSteps) return fail("conv packing: K too large for the tap table");
     pc.nsteps = nsteps;
-    std::vector<float> wp, bias((size_t)pc.n_ot * 16, 0.0f);
+    std::vector<float> wp, bias((size_t)pc.n_ot * 16, 0.0f), rs_rows;
     if (arith == OJF_ARITH_F16X3) {
         std::vector<float> rs((size_t)pc.n_ot * 16, 1.0f), rinv((size_t)pc.n_ot * 16, 1.0f);
         for (int oc = 0; oc < b.c_out_phys; ++oc) {
@@ -1764,6 +1921,7 @@ static int finish(const ConvBuilder &b, PackedConv &pc, int arith = OJF_ARITH_F3
             rinv[oc] = 1.0f / rs[oc];
         }
         if (upload(rinv, &pc.rinv)) return -2;
+        rs_rows = rs;
         // [S][ot][hi|lo][lane] x 8 halfs; dead (all-zero) supersteps behind for the chunk copies
         const int nsp = nsteps + kPad16;
         wp.assign((size_t)nsp * pc.n_ot * 128 * 4, 0.0f);
@@ -1794,6 +1952,24 @@ static int finish(const ConvBuilder &b, PackedConv &pc, int arith = OJF_ARITH_F3
                 }
     }
     for (int o = 0; o < b.c_out_phys; ++o) bias[o] = b.B[o];
+    if (rows_form_packed(arith, b.taps, c4, pc.n_ot)) {
+        // the same hi / lo halves of the same scaled weights in the K order of conv_f16x3_rows_kernel: superstep 2 ky + s,
+        // slot 8 s + 2 (lane >> 4) + (j >> 2) = kx * c4 + cg; slots from 3 c4 on stay zero
+        std::vector<float> wr((size_t)6 * pc.n_ot * 128 * 4, 0.0f);
+        _Float16 *hp = reinterpret_cast<_Float16 *>(wr.data());
+        for (int S = 0; S < 6; ++S)
+            for (int ot = 0; ot < pc.n_ot; ++ot)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int j = 0; j < 8; ++j) {
+                        const int oc = ot * 16 + (lane & 15), slot = 8 * (S & 1) + 2 * (lane >> 4) + (j >> 2);
+                        if (oc >= b.c_out_phys || slot >= 3 * c4) continue;
+                        const int t = 3 * (S >> 1) + slot / c4, cg = slot % c4;
+                        const float v = rs_rows[oc] * b.W[((size_t)oc * b.taps + t) * b.c_in_phys + 4 * cg + (j & 3)];
+                        const size_t base = ((size_t)S * pc.n_ot + ot) * 2 * 64 * 8;
+                        split_weight(v, hp[base + (size_t)lane * 8 + j], hp[base + 64 * 8 + (size_t)lane * 8 + j]);
+                    }
+        if (upload(wr, &pc.wp_rows)) return -2;
+    }
     if (upload(wp, &pc.wp)) return -2;
     if (upload(bias, &pc.bias)) return -2;
     return 0;
@@ -1804,7 +1980,8 @@ static void release(PackedConv &pc)
     if (pc.wp) (void)hipFree(pc.wp);
     if (pc.bias) (void)hipFree(pc.bias);
     if (pc.rinv) (void)hipFree(pc.rinv);
-    pc.wp = pc.bias = pc.rinv = nullptr;
+    if (pc.wp_rows) (void)hipFree(pc.wp_rows);
+    pc.wp = pc.bias = pc.rinv = pc.wp_rows = nullptr;
 }
 
 static inline f32x4 *planes(float *p) { return reinterpret_cast<f32x4 *>(p); }
@@ -2318,6 +2495,10 @@ static int launch_conv_args(const ConvArgs *args, int n, int nt, hipStream_t st,
         fprintf(stderr, "ojf_net %s | n %d mt %d nt %d grid_x %u nblocks %d grid16_x %u band %d lean %d perm %s\n", kLaunchNames[conv_launch(arith, n)],
                 n, mt, nt, grid.x, grp.nblocks, grid16.x, grp.band, lean ? 1 : 0, perm);
     }
+    // Row-pair form (conv_f16x3_rows_kernel): decided for the launch as a whole; the grid, the bands and the trace line above are
+    // those of the old form - with w % 64 == 0 and h even, (h / 2)(w / 64) pairs-by-column-groups == nblocks.
+    bool rows = arith == OJF_ARITH_F16X3 && n_ins == n && mt == 2 && nt == 2 && lean && grp.nblocks > 0 && args[0].w % 64 == 0 && args[0].h % 2 == 0;
+    for (int i = 0; i < n && rows; ++i) rows = args[i].wp_rows && args[i].taps == 9 && 3 * args[i].c4 <= 16;
     if ((n_ins || n_outs) && (arith != OJF_ARITH_F16X3 || (n_ins && (n_ins != n || mt != 2 || nt != 2))))
         return fail("conv: split planes are a format of the split-fp16 grouped 3x3 launches only");
 #define OJF_LAUNCH16(MT_, NT_)                                                                                      \
@@ -2328,7 +2509,8 @@ static int launch_conv_args(const ConvArgs *args, int n, int nt, hipStream_t st,
     if (arith == OJF_ARITH_F16X3 && mt == 2) {
         switch (nt) {
             case 2:
-                if (n_ins && lean) hipLaunchKernelGGL((conv_f16x3_kernel<2, 2, true, 0, true, true>), grid16, block, tab_bytes, st, grp);
+                if (rows) hipLaunchKernelGGL(conv_f16x3_rows_kernel, grid16, block, 0, st, grp);
+                else if (n_ins && lean) hipLaunchKernelGGL((conv_f16x3_kernel<2, 2, true, 0, true, true>), grid16, block, tab_bytes, st, grp);
                 else if (n_ins) hipLaunchKernelGGL((conv_f16x3_kernel<2, 2, true, 0, false, true>), grid16, block, tab_bytes, st, grp);
                 else OJF_LAUNCH16(2, 2);
                 break;
@@ -2374,6 +2556,7 @@ static void fill_conv_args(ConvArgs &a, const PackedConv &pc, const float *in, i
     a.accum = 0; a.dscale = nullptr;
     a.in = planes(in); a.out = planes(out); a.out_rows = nullptr;
     a.wp = planes(pc.wp); a.bias = bias ? bias : pc.bias; a.rinv = pc.rinv;
+    a.wp_rows = planes(pc.wp_rows);
     a.in_g0 = in_g0; a.out_g0 = out_g0; a.rows_stride = 0; a.rows_n = 0;
     a.h = h; a.w = w; a.npix = h * w;
     a.taps = pc.taps; a.dil = pc.dil;
