@@ -723,6 +723,42 @@ int ojf_rasterize_attributes(const float *vertices_dev, int nv, const int *faces
                              const uint8_t *vertex_rgba_dev /* u8[nv][4] or NULL */, uint8_t *labels_dev /* u8[n,h,w] or NULL */,
                              uint8_t *rgba_dev /* u8[n,h,w,4] or NULL */, ojf_stream_t stream);
 
+/* ---- RESAMPLE (re-box, resample and merge fused volumes; no counterpart in the reference) ------------------------------
+ * Every voxel (i,j,k) of a destination grid [dX,dY,dZ] reads the source grid [sX,sY,sZ] at the index coordinates
+ *   g = M (i,j,k) + c (M_host f64[9] row-major, c_host f64[3]; rounded once to fp32; voxel (i,j,k) of the source sits at
+ *   g = (i,j,k)): the trilinear mean over the 8 corners around g that lie inside the source grid, have a trilinear weight
+ *   > 0 and are observed (source weight > 0; every in-grid corner when there is no weight volume), renormalised by the sum
+ *   ws of their trilinear weights.  A voxel is covered when ws >= 0.5 and its new weight does not round to +0; a g with a
+ *   coordinate that is non-finite, < -1 or > its axis' size covers nothing.  For a rigid map x_s = R x_d + t between the
+ *   boxes, M = R res_d / res_s and c = (R (origin_d + res_d / 2) + t - origin_s) / res_s - 1/2.
+ * ojf_resample_volumes: the fp16 TSDF, fp16 weights (both NULL: the ground-truth form, every voxel observed), u8 ids and
+ *   fp16 scores (all four set or all four NULL) of a scene.  T' and W' are the renormalised means of the counting corners;
+ *   id' and score' are those of the counting corner with the largest trilinear weight (the first of equals in corner order
+ *   000..111, bits x, y, z).
+ * ojf_resample_records: a record volume fp16 [X,Y,Z,S] whose channel Cw is the weight - the colour volume (S = 4, Cw = 3;
+ *   2-byte aligned) or a label volume (S a multiple of 8 up to 264, Cw = n_classes; 16-byte aligned).  Channels 0..Cw-1
+ *   take the renormalised mean, channel Cw the mean weight; channels behind Cw are neither read nor written.
+ * mode OJF_RESAMPLE_REPLACE: every destination voxel is written once; an uncovered one takes init_value, weight 0, id 0,
+ *   score 0 (record channels 0..Cw: 0).  mode OJF_RESAMPLE_MERGE (needs the weight volumes): an uncovered voxel is left
+ *   alone; a covered one takes the running mean T = (W_d T_d + W' T') / (W_d + W') (T' where W_d == 0),
+ *   W = min(W_d + W', max_weight), and id' / score' where score' > score_d.  1 <= max_weight <= 65504 in both modes.
+ * One lane (a group of lanes for records of 4 chunks and more) per destination voxel: no atomics, no workspace, the same
+ *   bits on every run.  One kernel each, never waits.  Bad arguments (null or mismatched pointers, non-positive sizes,
+ *   more than 2^31-1 voxels, a source that overlaps a destination in memory, non-finite M / c / init_value, an unknown
+ *   mode, max_weight, S, Cw, alignment) are refused before any HIP call.  The exact fp32 operation order is in
+ *   csrc/ojf_resample.hip. */
+#define OJF_RESAMPLE_REPLACE 0
+#define OJF_RESAMPLE_MERGE 1
+int ojf_resample_volumes(const uint16_t *src_tsdf_dev, const uint16_t *src_weights_dev /* or NULL */,
+                         const uint8_t *src_ids_dev /* or NULL */, const uint16_t *src_scores_dev /* or NULL */, int sX, int sY,
+                         int sZ, uint16_t *dst_tsdf_dev, uint16_t *dst_weights_dev, uint8_t *dst_ids_dev, uint16_t *dst_scores_dev,
+                         int dX, int dY, int dZ, const double *M_host /* f64[9] */, const double *c_host /* f64[3] */,
+                         float init_value, int mode, float max_weight, ojf_stream_t stream);
+int ojf_resample_records(const uint16_t *src_dev /* fp16 [sX,sY,sZ,S] */, int sX, int sY, int sZ,
+                         uint16_t *dst_dev /* fp16 [dX,dY,dZ,S] */, int dX, int dY, int dZ, int S, int Cw,
+                         const double *M_host /* f64[9] */, const double *c_host /* f64[3] */, int mode, float max_weight,
+                         ojf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

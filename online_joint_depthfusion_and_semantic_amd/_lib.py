@@ -50,6 +50,7 @@ PROJECTIVE_MAX_VIEWS = 32  # include/ojf.h OJF_PROJECTIVE_MAX_VIEWS
 COLOR_MAX_VIEWS = 32  # include/ojf.h OJF_COLOR_MAX_VIEWS
 RASTER_MAX_VIEWS = 32  # include/ojf.h OJF_RASTER_MAX_VIEWS
 LABEL_MAX_VIEWS = 32  # include/ojf.h OJF_LABEL_MAX_VIEWS
+RESAMPLE_REPLACE, RESAMPLE_MERGE = 0, 1  # include/ojf.h OJF_RESAMPLE_REPLACE / OJF_RESAMPLE_MERGE
 
 
 class ExtractJob(ctypes.Structure):
@@ -182,6 +183,11 @@ SIGNATURES = {
     'ojf_rasterize': (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
     # vertices, nv, faces, nf, n, K, E, h, w, face, face labels, vertex rgba, labels, rgba, stream
     'ojf_rasterize_attributes': (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # source tsdf, weights, ids, scores, sX, sY, sZ, destination tsdf, weights, ids, scores, dX, dY, dZ, M, c, init_value, mode,
+    # max_weight, stream
+    'ojf_resample_volumes': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _f, _i, _f, _vp]),
+    # source records, sX, sY, sZ, destination records, dX, dY, dZ, S, Cw, M, c, mode, max_weight, stream
+    'ojf_resample_records': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _f, _vp]),
 }
 
 _LIB = None

@@ -410,6 +410,115 @@ class Database(torch.utils.data.Dataset):
                 raise ValueError('Database.decide_labels: the volumes of {!r} are not resident on the device (to_torch())'.format(s))
             label_probs.decide_labels(vol, self.n_classes, ids, scores)
 
+    # ---- the box: re-box, resample, merge (resample.py) ------------------------------------------------------
+    def _estimated_volumes(self, scene_id, who):
+        """The estimated volumes of a scene as resample.resample_scene takes them; host state is refused."""
+        vols = {'tsdf': self.scenes_est[scene_id].volume, 'weights': self.fusion_weights[scene_id]}
+        if self.semantics:
+            vols.update(ids=self.ids_est[scene_id].volume, scores=self.scores[scene_id].volume)
+        if self.colors.get(scene_id) is not None:
+            vols['colors'] = self.colors[scene_id]
+        if self.label_probs.get(scene_id) is not None:
+            vols.update(label_probs=self.label_probs[scene_id], n_classes=self.n_classes)
+        if not all(_is_dev(v) for k, v in vols.items() if k != 'n_classes'):
+            raise ValueError('Database.{}: the volumes of {!r} are not resident on the device (to_torch())'.format(who, scene_id))
+        return vols
+
+    def _origin64(self, scene_id):
+        o = self.origin[scene_id]
+        return (o.detach().cpu().numpy() if torch.is_tensor(o) else np.asarray(o)).astype(np.float64).reshape(3)
+
+    def resample(self, scene_id, origin=None, shape=None, resolution=None, transform=None):
+        """Re-box every volume of a scene (resample.resample_scene, replace mode): the new box has ``origin``, ``shape`` and
+        ``resolution`` (each defaults to what the scene has); ``transform`` ([3,4] or [4,4], default identity) maps points of
+        the new box's world to the old one's.  The estimated TSDF / weights / ids / scores, the colour and class-distribution
+        volumes read the observed voxels of the old box (trilinear, labels from the nearest observed voxel); the ground-truth
+        volumes read every voxel of it.  What the old box does not cover holds the initial value / weight 0 / label 0.
+        ``origin``, ``resolution`` and the bbox / origin of every Voxelgrid of the scene follow."""
+        from . import resample as rs
+        est = self._estimated_volumes(scene_id, 'resample')
+        gt = self.scenes_gt[scene_id].volume
+        ids_gt = self.ids_gt[scene_id].volume if self.semantics and self.semantic_grid else None
+        if not _is_dev(gt) or not (ids_gt is None or _is_dev(ids_gt)):
+            raise ValueError('Database.resample: the volumes of {!r} are not resident on the device (to_torch())'.format(scene_id))
+        if gt.dtype != torch.float16:
+            raise ValueError('Database.resample: the ground-truth volume of {!r} must be fp16, got {}'.format(scene_id, gt.dtype))
+        old_origin, old_res = self._origin64(scene_id), float(self.resolution[scene_id])
+        new_origin = old_origin if origin is None else np.asarray(ops._origin_array(origin))
+        new_res = old_res if resolution is None else float(resolution)
+        new_shape = tuple(gt.shape) if shape is None else tuple(shape)
+        kw = dict(src_origin=old_origin, src_resolution=old_res, dst_shape=new_shape, dst_origin=new_origin, dst_resolution=new_res,
+                  transform=transform, init_value=self.initial_value)
+        new = rs.resample_scene(est, **kw)
+        truth = {'tsdf': gt}
+        if ids_gt is not None:  # (the nearest rule needs a score volume beside the ids: zeros)
+            truth.update(ids=ids_gt, scores=torch.zeros_like(gt))
+        new_gt = rs.resample_scene(truth, **kw)
+        new_shape = tuple(new['tsdf'].shape)
+
+        bbox = np.stack([new_origin, new_origin + np.array(new_shape, dtype=np.float64) * new_res], axis=1)
+        self.origin[scene_id] = torch.from_numpy(new_origin.copy())
+        self.resolution[scene_id] = new_res
+        grids = [(self.scenes_est[scene_id], new['tsdf']), (self.scenes_gt[scene_id], new_gt['tsdf'])]
+        self.fusion_weights[scene_id] = new['weights']
+        if self.semantics:
+            grids += [(self.ids_est[scene_id], new['ids']), (self.scores[scene_id], new['scores'])]
+            if ids_gt is not None:
+                grids.append((self.ids_gt[scene_id], new_gt['ids']))
+        for grid, volume in grids:
+            grid.resolution = new_res
+            grid.from_array(volume, bbox)
+        if 'colors' in new:
+            self.colors[scene_id] = new['colors']
+        if 'label_probs' in new:
+            self.label_probs[scene_id] = new['label_probs']
+
+    def recentre(self, scene_id, point):
+        """Shift the box of a scene by whole voxels so that the voxel holding the world point ``point`` becomes the centre voxel
+        (index N // 2 on every axis); returns the integer shift (i, j, k) in voxels.  A whole-voxel shift is exact: every voxel
+        that stays inside the box keeps its bits, the voxels that come in hold the initial value / weight 0 / label 0.  The call
+        a live driver makes when the tracked camera nears a face of the box."""
+        o, res = self._origin64(scene_id), float(self.resolution[scene_id])
+        shape = np.array(self.scenes_est[scene_id].volume.shape, dtype=np.int64)
+        p = np.asarray(ops._origin_array(point))
+        if not np.isfinite(p).all():
+            raise ValueError('Database.recentre: non-finite point')
+        shift = np.floor((p - o) / res).astype(np.int64) - shape // 2
+        if shift.any():
+            self.resample(scene_id, origin=o + shift.astype(np.float64) * res)
+        else:
+            self._estimated_volumes(scene_id, 'recentre')  # (host state is refused all the same)
+        return tuple(int(s) for s in shift)
+
+    def merge(self, dst_scene, src_scene, transform=None, max_weight=None):
+        """Merge the estimated volumes of ``src_scene`` into those of ``dst_scene`` in place (resample.resample_scene, merge
+        mode): where the source is observed the destination takes the running mean of both by their weights, the label of the
+        higher score, and the sum of the weights up to ``max_weight`` (default: 65504 for the geometry, 64 for colour and class
+        distributions); elsewhere it is left alone.  ``transform`` maps points of the destination's world to the source's (the
+        tracked pose between two sessions; default: one world).  A colour or class-distribution volume only the source has is
+        created in the destination; ``decide_labels`` is left to the caller."""
+        from . import color, label_probs, resample as rs
+        if dst_scene == src_scene:
+            raise ValueError('Database.merge: a scene cannot be merged into itself')
+        src = self._estimated_volumes(src_scene, 'merge')
+        dst = self._estimated_volumes(dst_scene, 'merge')
+        shape, dev = tuple(dst['tsdf'].shape), dst['tsdf'].device
+        fresh = {}
+        if 'colors' in src and 'colors' not in dst:
+            fresh['colors'] = dst['colors'] = color.new_volume(shape, dev)
+        if 'label_probs' in src and 'label_probs' not in dst:
+            fresh['label_probs'] = dst['label_probs'] = label_probs.new_volume(shape, self.n_classes, dev)
+            dst['n_classes'] = self.n_classes
+        into = {k: v for k, v in dst.items() if k in src}
+        rs.resample_scene(src, src_origin=self._origin64(src_scene), src_resolution=float(self.resolution[src_scene]), dst_shape=shape,
+                          dst_origin=self._origin64(dst_scene), dst_resolution=float(self.resolution[dst_scene]), transform=transform,
+                          into=into, init_value=self.initial_value, max_weight=max_weight)
+        if 'colors' in fresh:  # (a refused call leaves a scene without a volume without one)
+            self.colors[dst_scene] = fresh['colors']
+        if 'label_probs' in fresh:
+            self.label_probs[dst_scene] = fresh['label_probs']
+        self.state[dst_scene] = self.state[dst_scene] or self.state[src_scene]
+
     def save_to_workspace(self, workspace, mode, save_mode='ply'):
         """database.py:141-177: every scene that holds integrated frames goes to the workspace's output directory as
         ``<scene>.tsdf_<mode>.hf5`` / ``.weights_<mode>.hf5`` / ``.semantic_<mode>.hf5`` ('tsdf'), ``<scene>_<mode>.ply``
