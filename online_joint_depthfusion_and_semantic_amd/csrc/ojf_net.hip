@@ -54,8 +54,8 @@
 // head's tail computing its half of the last entry GEMM.  Other inputs take the general paths: dense_pair_kernel per Block
 // (w % 8 != 0), generic convolutions (fp32 arithmetic, other growth rates), the general VortexPooling flow with the
 // global-average branch on a side stream and an unfused tail / head (topologies without chain-layer forms).
-// Environment switches: OJF_NET_GRAPH=1 (opt-in hipGraph replay); test-only, each set by one test of tests/test_net_gpu.py:
-// OJF_NO_DENSE_CHAIN=1 (pair kernels instead of the chain kernel), OJF_BRANCH_KERNEL=1 / OJF_SUBCONV=1 (ojf_net_branch.h).
+// Environment switches: OJF_NET_GRAPH=1 (opt-in hipGraph replay); test-only, set by tests/test_net_gpu.py:
+// OJF_NO_DENSE_CHAIN=1 (pair kernels instead of the chain kernel).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -1794,11 +1794,11 @@ static int guard_take(int *skipped, bool clear)
 // The names are one table: the launch sites pass an index, the forward plan (plan_launches / ojf_net_plan) lists the same indices.
 enum Launch {
     L_DENSE_CHAIN, L_DENSE_PAIR, L_CONV_F16X3, L_CONV_F16X3_GROUPED, L_CONV_MFMA, L_COLSUM, L_GAVE_BIAS, L_ENTRY1X1, L_POOL_PYRAMID,
-    L_VORTEX_BRANCH, L_SUBCONV, L_TAIL, L_TAIL_ENTRY, L_TAIL_HALF_ENTRY, L_TAIL_HEAD, L_COUNT
+    L_TAIL, L_TAIL_ENTRY, L_TAIL_HALF_ENTRY, L_TAIL_HEAD, L_COUNT
 };
 static const char *const kLaunchNames[L_COUNT] = {
     "dense_chain_kernel", "dense_pair_kernel", "conv_f16x3_kernel", "conv_f16x3_kernel (grouped)", "conv_mfma_kernel", "colsum_kernel",
-    "gave_bias_kernel", "entry1x1_kernel", "pool_pyramid_kernel", "vortex_branch_kernel", "subconv_kernel", "vortex_tail_kernel",
+    "gave_bias_kernel", "entry1x1_kernel", "pool_pyramid_kernel", "vortex_tail_kernel",
     "vortex_tail_kernel (+ next entry GEMM)", "vortex_tail_kernel (+ half of the next entry GEMM)", "vortex_tail_kernel (+ prediction head)",
 };
 // a generic convolution launch of n (<= 4) problems (launch_conv_args)
@@ -2246,192 +2246,6 @@ static int launch_chain(const PackedChain &pc, float *x, int h, int w, hipStream
     return launch_chain_t<12, 8, 8>(a, st);
 }
 
-// ---- the four branches of a VortexPooling in one persistent launch (vortex_branch_kernel, ojf_net_branch.h) -----------
-}  // namespace ojf
-#include "ojf_net_branch.h"
-namespace ojf {
-
-struct PackedBranches {
-    float *w = nullptr, *vec = nullptr;
-    int4 *items = nullptr;
-    int n_items = 0;
-    int4 *sub_items = nullptr;  // subconv_kernel's table
-    int n_sub = 0;
-    int dil[4] = {0, 0, 0, 0};
-};
-
-static void release(PackedBranches &pb)
-{
-    if (pb.w) (void)hipFree(pb.w);
-    if (pb.vec) (void)hipFree(pb.vec);
-    if (pb.items) (void)hipFree(pb.items);
-    if (pb.sub_items) (void)hipFree(pb.sub_items);
-    pb = PackedBranches();
-}
-
-// The item table of vortex_branch_kernel for an h x w frame (ojf_net_branch.h): per branch the kind with the fewest MFMA
-// pixel tiles, the table sorted by kind; inside a branch the phases of a tile 8 items apart (same XCD: measured 82 against
-// 95 us per frame for the kernel with the sub-images of a tile dealt to neighbouring blocks, i.e. to eight L2s).
-static std::vector<int4> branch_items(const int (&dil)[4], int h, int w)
-{
-    struct Plan { int br, kind, ntx, nty, cost; };
-    std::vector<Plan> plans;
-    for (int br = 0; br < 4; ++br) {
-        const int d = dil[br], smw = (w + d - 1) / d, smh = (h + d - 1) / d;
-        Plan p{br, 0, 0, 0, 0};
-        if (smw <= BranchK2::TW && smh <= BranchK2::TH) {
-            p.kind = 2; p.ntx = p.nty = 1;
-        } else {
-            const int ntx = (smw + 19) / 20, n0 = (smh + BranchK0::TH - 1) / BranchK0::TH, n1 = (smh + BranchK1::TH - 1) / BranchK1::TH;
-            const int c0 = n0 * (BranchK0::TILES_A + BranchK0::TILES_B), c1 = n1 * (BranchK1::TILES_A + BranchK1::TILES_B);
-            p.kind = c1 < c0 ? 1 : 0; p.ntx = ntx; p.nty = c1 < c0 ? n1 : n0;
-        }
-        plans.push_back(p);
-    }
-    std::vector<int4> items;
-    for (int kind = 0; kind < 3; ++kind)
-        for (const Plan &p : plans) {
-            if (p.kind != kind) continue;
-            const int d = dil[p.br];
-            std::vector<int> phases;  // px | py << 16 of the non-empty sub-images
-            for (int py = 0; py < d && py < h; ++py)
-                for (int px = 0; px < d && px < w; ++px) phases.push_back(px | (py << 16));
-            const int head = p.br | (kind << 4);
-            if (kind == 2) {
-                for (size_t i = 0; i < phases.size(); i += 2)
-                    items.push_back(int4{head, phases[i], i + 1 < phases.size() ? phases[i + 1] : -1, 0});
-                continue;
-            }
-            const int tw = 20, th = kind == 1 ? BranchK1::TH : BranchK0::TH, nt = p.ntx * p.nty;
-            for (int t0 = 0; t0 < nt; t0 += 8) {
-                const int n = nt - t0 < 8 ? nt - t0 : 8;
-                for (int ph : phases)
-                    for (int c = 0; c < n; ++c) {
-                        // full groups: position c of an eight holds the tile whose number is congruent to the item's index mod 8
-                        const int t = n == 8 ? t0 + (int)(items.size() & 7u) : t0 + c;
-                        items.push_back(int4{head, ph, -1, ((t % p.ntx) * tw) | (((t / p.ntx) * th) << 16)});
-                    }
-            }
-        }
-    return items;
-}
-
-// The item table of subconv_kernel (one block per item): per branch the kind with the fewest MFMA pixel tiles; inside a branch
-// the phases of a tile 8 items apart (blocks land on XCD blockIdx % 8: the r x r sub-images of one image region share an L2).
-static std::vector<int4> subconv_items(const int (&dil)[4], int h, int w)
-{
-    struct Kind { int tw, th, tiles; };
-    const Kind kinds[4] = {{SubK0::TW, SubK0::TH, SubK0::TILES}, {SubK1::TW, SubK1::TH, SubK1::TILES}, {SubK2::TW, SubK2::TH, SubK2::TILES},
-                           {SubK3::TW, SubK3::TH, SubK3::TILES}};
-    std::vector<int4> items;
-    for (int br = 0; br < 4; ++br) {
-        const int d = dil[br], smw = (w + d - 1) / d, smh = (h + d - 1) / d;
-        int best = 0;
-        long best_cost = -1;
-        for (int k = 0; k < 4; ++k) {
-            const long cost = (long)((smw + kinds[k].tw - 1) / kinds[k].tw) * ((smh + kinds[k].th - 1) / kinds[k].th) * kinds[k].tiles;
-            if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = k; }
-        }
-        const Kind &K = kinds[best];
-        const int ntx = (smw + K.tw - 1) / K.tw, nty = (smh + K.th - 1) / K.th, nt = ntx * nty, head = br | (best << 4);
-        std::vector<int> phases;
-        for (int py = 0; py < d && py < h; ++py)
-            for (int px = 0; px < d && px < w; ++px) phases.push_back(px | (py << 16));
-        for (int t0 = 0; t0 < nt; t0 += 8) {
-            const int n = nt - t0 < 8 ? nt - t0 : 8;
-            for (int ph : phases)
-                for (int c = 0; c < n; ++c) {
-                    const int t = n == 8 ? t0 + (int)(items.size() & 7u) : t0 + c;
-                    items.push_back(int4{head, ph, -1, ((t % ntx) * K.tw) | (((t / ntx) * K.th) << 16)});
-                }
-        }
-    }
-    return items;
-}
-
-// ba[br] / bb[br]: the two dilated 3x3 of branch br (20 -> 20 channels)
-static int finish_branches(const std::vector<ConvBuilder> &ba, const std::vector<ConvBuilder> &bb, int h, int w, PackedBranches &pb)
-{
-    if (ba.size() != 4 || bb.size() != 4) return fail("branch packing: four branches expected");
-    std::vector<float> vec(4 * 128, 0.0f), wts;
-    for (int br = 0; br < 4; ++br) {
-        const ConvBuilder &a = ba[br], &b = bb[br];
-        if (a.taps != 9 || b.taps != 9 || a.dil != b.dil || a.dil < 1 || a.c_in_phys != 4 * kChainNG || a.c_out_phys != 4 * kChainNG ||
-            b.c_in_phys != 4 * kChainNG || b.c_out_phys != 4 * kChainNG)
-            return fail("branch packing: unsupported layer shapes");
-        pb.dil[br] = a.dil;
-        auto scales = [&](const ConvBuilder &cb, int off) {
-            std::vector<float> rs(32, 1.0f);
-            for (int oc = 0; oc < cb.c_out_phys; ++oc) {
-                float mx = 0.0f;
-                const float *row = cb.W.data() + (size_t)oc * cb.taps * cb.c_in_phys;
-                for (int i = 0; i < cb.taps * cb.c_in_phys; ++i) mx = std::fmax(mx, std::fabs(row[i]));
-                rs[oc] = row_scale(mx);
-                vec[(size_t)br * 128 + off + oc] = cb.B[oc];
-            }
-            for (int oc = 0; oc < 32; ++oc) vec[(size_t)br * 128 + off + 32 + oc] = 1.0f / rs[oc];
-            return rs;
-        };
-        const std::vector<float> ra = scales(a, 0), rb = scales(b, 64);
-        pack_chain_step(a, ra, 0, wts);
-        pack_chain_step(b, rb, 0, wts);
-    }
-    const std::vector<int4> items = branch_items(pb.dil, h, w);
-    if (items.empty() || items.size() > (1u << 20)) return fail("branch packing: bad item count");
-    pb.n_items = (int)items.size();
-    if (upload(wts, &pb.w) || upload(vec, &pb.vec)) return -2;
-    OJF_HIP(hipMalloc(reinterpret_cast<void **>(&pb.items), items.size() * sizeof(int4)));
-    OJF_HIP(hipMemcpy(pb.items, items.data(), items.size() * sizeof(int4), hipMemcpyHostToDevice));
-    const std::vector<int4> sub = subconv_items(pb.dil, h, w);
-    if (sub.empty() || sub.size() > (1u << 22)) return fail("branch packing: bad subconv item count");
-    pb.n_sub = (int)sub.size();
-    OJF_HIP(hipMalloc(reinterpret_cast<void **>(&pb.sub_items), sub.size() * sizeof(int4)));
-    OJF_HIP(hipMemcpy(pb.sub_items, sub.data(), sub.size() * sizeof(int4), hipMemcpyHostToDevice));
-    return 0;
-}
-
-// one dilated 3x3 of the four branches (second = 0 / 1): in[br] split planes, out[br] split planes or fp32 (5 groups each)
-static int launch_subconv(const PackedBranches &pb, const float *const *in, float *const *out, int second, bool out_split, int h, int w,
-                          hipStream_t st)
-{
-    static bool configured = false;
-    if (!configured) {
-        OJF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&subconv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSubLdsBytes));
-        configured = true;
-    }
-    SubArgs a;
-    for (int br = 0; br < 4; ++br) { a.in[br] = planes(in[br]); a.out[br] = planes(out[br]); a.dil[br] = pb.dil[br]; }
-    a.w = planes(pb.w); a.vec = pb.vec; a.items = pb.sub_items;
-    a.second = second; a.out_split = out_split ? 1 : 0;
-    a.h = h; a.w_img = w; a.npix = h * w;
-    a.ovf = overflow_flag();
-    hipLaunchKernelGGL(subconv_kernel, dim3(pb.n_sub), dim3(256), kSubLdsBytes, st, a);
-    mark_launch(L_SUBCONV, st);
-    return check_hip(hipGetLastError(), "subconv_kernel launch");
-}
-
-// in[br]: split planes of the branch inputs; out: fp32 planes, branch br at groups [5 br, 5 br + 5)
-static int launch_branches(const PackedBranches &pb, const float *const *in, float *out, int h, int w, hipStream_t st)
-{
-    static bool configured = false;
-    if (!configured) {
-        OJF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&vortex_branch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)kBranchLdsBytes));
-        configured = true;
-    }
-    BranchArgs a;
-    for (int br = 0; br < 4; ++br) { a.in[br] = planes(in[br]); a.dil[br] = pb.dil[br]; }
-    a.out = planes(out);
-    a.w = planes(pb.w); a.vec = pb.vec; a.items = pb.items; a.n_items = pb.n_items;
-    a.h = h; a.w_img = w; a.npix = h * w;
-    a.ovf = overflow_flag();
-    const int cus = device_cu_count();
-    const int grid = cus > 0 && cus < pb.n_items ? cus : pb.n_items;
-    hipLaunchKernelGGL(vortex_branch_kernel, dim3(grid), dim3(64 * kBranchWaves), kBranchLdsBytes, st, a);
-    mark_launch(L_VORTEX_BRANCH, st);
-    return check_hip(hipGetLastError(), "vortex_branch_kernel launch");
-}
-
 // Launches n (<= 4) independent convolutions with the same number of output tiles as ONE grid
 // (blockIdx.y = problem): the four branches of a VortexPooling run together instead of as four
 // under-filled launches with their own ramp-up and tail.
@@ -2647,7 +2461,6 @@ static void append_chain_bias(std::vector<float> &dst, int arith, int nt_out, in
 // of the step's enum, its case in plan_forward and plan_launches, its packing and its case in the executor.
 struct NetShape {
     int version, P, gf, sem, h, w, arith;
-    bool same_dil[3];  // VortexPooling k: the two 3x3 of every branch share a dilation (the reference's do: 1, 3, 9, 27)
     int c, cs, heads, pool_in, os, npix;  // derived (net_shape): channels of a Block and their padded slot, (gf+1)*c and its slot
     int c_in_phys(int k) const { return k < 2 ? (gf + 1) * cs : heads * os; }  // input planes of VortexPooling k (2 = the last one)
 };
@@ -2658,7 +2471,6 @@ static const char *net_shape(NetShape &s, int version, int n_points, int growth,
     if (version != 2 && version != 3) return "version must be 2 or 3";
     if (n_points < 1 || growth < 1 || h <= 0 || w <= 0) return "bad sizes";
     s.version = version; s.P = n_points; s.gf = growth; s.sem = use_semantics ? 1 : 0; s.h = h; s.w = w; s.arith = arith;
-    s.same_dil[0] = s.same_dil[1] = s.same_dil[2] = true;
     s.c = 2 * n_points + 1 + (version == 2 ? s.sem : 0);
     s.cs = round_up(s.c, 4);
     s.heads = (version == 3 && s.sem) ? 2 : 1;
@@ -2669,13 +2481,12 @@ static const char *net_shape(NetShape &s, int version, int n_points, int growth,
     return nullptr;
 }
 
-// The three test-only switches, read once per process (the tests that set them start child processes)
-struct NetSwitches { bool no_dense_chain, branch_kernel, subconv; };
-static const NetSwitches &net_switches()
+// The test-only switch OJF_NO_DENSE_CHAIN (set = present in the environment), read once per process (the tests that set it start
+// child processes)
+static bool no_dense_chain()
 {
-    auto on = [](const char *name) { const char *v = getenv(name); return v != nullptr && atoi(v) != 0; };
-    static const NetSwitches sw = {getenv("OJF_NO_DENSE_CHAIN") != nullptr, on("OJF_BRANCH_KERNEL"), on("OJF_SUBCONV")};
-    return sw;
+    static const bool set = getenv("OJF_NO_DENSE_CHAIN") != nullptr;
+    return set;
 }
 
 // Shape predicates: each form of the packing code exists exactly where its predicate holds.
@@ -2691,19 +2502,13 @@ static bool chain_flow_form(const NetShape &s, int k) { return entry_tiles(s.c_i
 // dense Blocks as dense_pair_kernel launches / as one dense_chain_kernel launch
 static bool pair_form(const NetShape &s) { return s.arith == OJF_ARITH_F16X3 && s.cs <= 24; }
 static bool chain_form(const NetShape &s) { return pair_form(s) && s.cs == 4 * kChainNG && s.gf <= kChainMaxLayers; }
-// both 3x3 of the four branches packed for vortex_branch_kernel / subconv_kernel (finish_branches; its item tables are never
-// empty for a frame of at least one pixel)
-static bool branch_form(const NetShape &s, int k)
-{
-    return s.arith == OJF_ARITH_F16X3 && s.cs == 4 * kChainNG && entry_tiles(s.c_in_phys(k), s.cs) != 0 && s.same_dil[k];
-}
 // growth channels of the prediction head as chain layers inside the last tail (19 / 20), 0 = layer by layer
 static int chain_kind_of(const NetShape &s) { return s.P == 9 && s.gf == 5 && (s.c == 19 || s.c == 20) ? s.c : 0; }
 // One dense_chain_kernel launch per head instead of gf dense_pair_kernel launches: the dense-growth buffers then hold split
 // planes, which only the chain-flow entry kernel reads.
 static bool chain_dense_form(const NetShape &s)
 {
-    if (s.arith != OJF_ARITH_F16X3 || net_switches().no_dense_chain) return false;
+    if (s.arith != OJF_ARITH_F16X3 || no_dense_chain()) return false;
     //  frames the chain kernel is not the right tool for fall back to one dense_pair_kernel launch per Block:
     //  * more tiles than the flag array holds (frames beyond ~2.6 Mpixel used to fail in ojf_net_forward);
     //  * w % 8 != 0: a 128-byte line of a plane is 8 pixels, so a line then straddles two image rows - pixels of tiles
@@ -2717,7 +2522,7 @@ static bool chain_dense_form(const NetShape &s)
 
 enum DenseKind { DENSE_CHAIN, DENSE_PAIRS, DENSE_CONVS };
 enum EntryKind { ENTRY_KERNEL, ENTRY_BY_PREV_TAIL, ENTRY_GENERIC };
-enum BranchKind { BRANCH_GROUPED, BRANCH_GROUPED_SIDE0, BRANCH_KERNEL, BRANCH_SUBCONV };
+enum BranchKind { BRANCH_GROUPED, BRANCH_GROUPED_SIDE0 };
 enum TailKind { TAIL_UNFUSED, TAIL_ALONE, TAIL_ENTRY, TAIL_HALF_ENTRY, TAIL_HEAD };
 
 struct VortexStep {
@@ -2750,7 +2555,6 @@ struct ForwardPlan {
 // nullptr, or the refusal (ojf_net_create fails with it)
 static const char *plan_forward(const NetShape &s, ForwardPlan *plan)
 {
-    const NetSwitches &sw = net_switches();
     const bool h16 = s.arith == OJF_ARITH_F16X3, two = s.heads == 2, fused = fused_tail_form(s.cs, s.os);
     ForwardPlan &p = *plan;
     p.dense = chain_dense_form(s) ? DENSE_CHAIN : pair_form(s) ? DENSE_PAIRS : DENSE_CONVS;
@@ -2771,9 +2575,7 @@ static const char *plan_forward(const NetShape &s, ForwardPlan *plan)
         v.split = h16 && v.chain_flow;
         v.z2 = last && halves;
         v.half = -1;
-        if (v.split && branch_form(s, v.vortex) && sw.branch_kernel) v.branches = BRANCH_KERNEL;
-        else if (v.split && branch_form(s, v.vortex) && sw.subconv) v.branches = BRANCH_SUBCONV;
-        else v.branches = v.chain_flow || s.npix < 32768 ? BRANCH_GROUPED : BRANCH_GROUPED_SIDE0;  // (small frames: the stream hand-over costs more than it hides)
+        v.branches = v.chain_flow || s.npix < 32768 ? BRANCH_GROUPED : BRANCH_GROUPED_SIDE0;  // (small frames: the stream hand-over costs more than it hides)
         if (!fused) v.tail = TAIL_UNFUSED;
         else if (last) v.tail = p.chain_kind ? TAIL_HEAD : TAIL_ALONE;
         else if (halves) { v.tail = TAIL_HALF_ENTRY; v.half = v.vortex; }
@@ -2805,8 +2607,6 @@ static std::vector<Launch> plan_launches(const NetShape &s, const ForwardPlan &p
         else if (v.entry == ENTRY_KERNEL) out.push_back(L_ENTRY1X1);
         out.push_back(L_POOL_PYRAMID);
         switch (v.branches) {
-        case BRANCH_KERNEL: out.push_back(L_VORTEX_BRANCH); break;
-        case BRANCH_SUBCONV: out.insert(out.end(), 2, L_SUBCONV); break;
         case BRANCH_GROUPED: out.insert(out.end(), 2, conv_launch(s.arith, 4)); break;
         case BRANCH_GROUPED_SIDE0: out.insert(out.end(), 2, conv1); out.insert(out.end(), 2, conv_launch(s.arith, 3)); break;
         }
@@ -2833,7 +2633,6 @@ struct Vortex {
     // one 8-tile -> 5 layer per head (columns [hd * os, (hd + 1) * os) of the stacked weights, no bias, no activation): each head's
     // tail runs ITS half on its register-resident result; the pool pyramid adds the halves (and forms branch 0)
     float *entry_wh[2] = {nullptr, nullptr}, *entry_bh[2] = {nullptr, nullptr}, *bias0 = nullptr;
-    PackedBranches branches;  // both 3x3 of the four branches for vortex_branch_kernel (split-fp16, 20-channel slots)
 };
 
 }  // namespace ojf
@@ -2969,7 +2768,6 @@ static int build_vortex(ojf_net *net, int k, const ojf_conv_layer *L, int c_in, 
         }
     }
     const std::vector<int> id_c = slot_map(c, c, cs);
-    std::vector<ConvBuilder> bas, bbs;
     for (int br = 0; br < 4; ++br) {
         const ojf_conv_layer &la = L[2 + 4 * br], &lb = L[3 + 4 * br], &l1 = L[4 + 4 * br];
         if (la.c_in != c || la.c_out != c || lb.c_in != c || lb.c_out != c || l1.c_in != c || l1.c_out != out)
@@ -2979,10 +2777,7 @@ static int build_vortex(ojf_net *net, int k, const ojf_conv_layer *L, int c_in, 
         bb.add(lb, 0, c, id_c, 0, true);
         b1.add(l1, 0, c, id_c, 0, true);
         if (finish(ba, v.b3a[br], net->arith) || finish(bb, v.b3b[br], net->arith) || finish(b1, v.b1[br], net->arith)) return -2;
-        bas.push_back(ba);
-        bbs.push_back(bb);
     }
-    if (branch_form(net->shape, k) && finish_branches(bas, bbs, net->h, net->w, v.branches)) return -2;
     {   // final 1x1 over [gave | b0 | b1 | b2 | b3]; the gave columns become a per-frame bias
         const ojf_conv_layer &lf = L[17];
         ConvBuilder b(4 * os, os, 1, 1);
@@ -3035,7 +2830,6 @@ static void free_vortex(Vortex &v)
         release(v.b1[b]);
         if (v.pool_bias[b]) (void)hipFree(v.pool_bias[b]);
     }
-    release(v.branches);
     float *ptrs[] = {v.Wg, v.bg, v.Wfg, v.bf, v.bias_final, v.tail_w, v.tail_b1, v.tail_rinv, v.entry_w, v.entry_b,
                      v.entry_wh[0], v.entry_wh[1], v.entry_bh[0], v.entry_bh[1], v.bias0};
     for (float *p : ptrs)
@@ -3132,21 +2926,7 @@ static int run_vortex(ojf_net *net, const VortexStep &s, hipStream_t st, const C
         OJF_HIP(hipGetLastError());
     }
     const float *bin[4] = {s.z2 ? sc.Q0 : sc.Z, sc.Q1, sc.Q2, sc.Q3};
-    if (s.branches == BRANCH_KERNEL) {  // both 3x3 of all four branches: one launch (ojf_net_branch.h)
-        // (measured equal to the two grouped launches, not faster - 82 against 79-80 us per frame, profiles/r04_pair_experiments.txt -
-        // so it is opt-in: OJF_BRANCH_KERNEL=1)
-        if (launch_branches(v.branches, bin, sc.V, h, w, st)) return -2;
-    } else if (s.branches == BRANCH_SUBCONV) {  // LDS-staged sub-image blocks: one launch per 3x3 (ojf_net_branch.h)
-        float *u[4], *vv[4];
-        const float *uc[4];
-        for (int br = 0; br < 4; ++br) {
-            u[br] = sc.U + (size_t)br * c4 * 4 * net->npix;
-            uc[br] = u[br];
-            vv[br] = sc.V + (size_t)br * c4 * 4 * net->npix;
-        }
-        if (launch_subconv(v.branches, bin, u, 0, true, h, w, st)) return -2;
-        if (launch_subconv(v.branches, uc, vv, 1, false, h, w, st)) return -2;
-    } else {   // the four branches' dilated 3x3 pairs: two grouped launches (all first convs, then all second convs)
+    {   // the four branches' dilated 3x3 pairs: two grouped launches (all first convs, then all second convs)
         ConvArgs ga[4], gb[4];
         for (int br = 0; br < 4; ++br) {
             fill_conv_args(ga[br], v.b3a[br], bin[br], 0, sc.U, br * c4, nullptr, OJF_ACT_RELU, net->cs, 1.0f, h, w);
@@ -3315,14 +3095,6 @@ OJF_API int ojf_net_create(ojf_net **out, int version, int n_points, int growth,
             if (!std::isfinite(L[i].bias_host[k])) return fail("ojf_net_create: non-finite bias");
     }
 
-    {   // the dilations of the VortexPoolings' 3x3 pairs: vortex k's 18 layers follow its head's 2*growth dense layers
-        const int base[3] = {2 * growth, 2 * (2 * growth + 18) - 18, shape.heads * (2 * growth + 18)};
-        for (int k = 0; k < 3; ++k) {
-            if (k == 1 && shape.heads == 1) continue;
-            for (int br = 0; br < 4; ++br)
-                if (L[base[k] + 2 + 4 * br].dilation != L[base[k] + 3 + 4 * br].dilation) shape.same_dil[k] = false;
-        }
-    }
     ForwardPlan plan;
     if (const char *why = plan_forward(shape, &plan)) return refuse("ojf_net_create", why);
 

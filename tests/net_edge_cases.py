@@ -97,7 +97,7 @@ Step = collections.namedtuple('Step', 'vortex chain_flow entry entry_ntin branch
 
 
 def plan_forward(s):
-    """-> (dense kind, steps, head_layers): plan_forward with the three test-only switches off"""
+    """-> (dense kind, steps, head_layers): plan_forward with the test-only switch off"""
     two, fused = s.heads == 2, fused_tail_form(s.cs, s.os)
     dense = 'chain' if chain_dense_form(s) else 'pairs' if pair_form(s) else 'convs'
     kind = chain_kind_of(s)

@@ -1,12 +1,11 @@
 """The case table of the fusion net's forward plan: the smallest shapes at which each decision of the plan flips, and the launch
 sequence of each - RECORDED from ojf_net_profile of the commit before the plan existed (tools/net_sha.py on an MI355X, every row
-in both arithmetics; the three switch rows in child processes), never from ojf_net_plan.  Shared by tests/test_net_plan_host.py
+in both arithmetics; the switch row in a child process), never from ojf_net_plan.  Shared by tests/test_net_plan_host.py
 (ojf_net_plan against this table, no GPU) and tests/test_net_gpu.py (ojf_net_profile against ojf_net_plan).
 Keys: version, use_semantics, n_points, growth (as the C ABI counts it: growth_factor - 1), h, w, arithmetic."""
 CHAIN, PAIR = ['dense_chain_kernel'], ['dense_pair_kernel']
 CONV16, GROUPED, CONV32 = ['conv_f16x3_kernel'], ['conv_f16x3_kernel (grouped)'], ['conv_mfma_kernel']
 COLSUM, GAVE, ENTRY, PYRAMID = ['colsum_kernel'], ['gave_bias_kernel'], ['entry1x1_kernel'], ['pool_pyramid_kernel']
-BRANCH, SUBCONV = ['vortex_branch_kernel'], ['subconv_kernel']
 TAIL, TAIL_ENTRY = ['vortex_tail_kernel'], ['vortex_tail_kernel (+ next entry GEMM)']
 TAIL_HALF, TAIL_HEAD = ['vortex_tail_kernel (+ half of the next entry GEMM)'], ['vortex_tail_kernel (+ prediction head)']
 
@@ -49,9 +48,7 @@ PLANS = {
     (3, 0, 8, 6, 40, 56, 'f32'): CONV32 * 12 + ENTRY + PYRAMID + CONV32 * 2 + TAIL_ENTRY + PYRAMID + CONV32 * 2 + TAIL + CONV32 * 13,
 }
 
-# (3, 0, 9, 5, 24, 32, 'f16x3') under each of the three test-only switches (read once per process)
+# (3, 0, 9, 5, 24, 32, 'f16x3') under the test-only switch (read once per process)
 SWITCH_PLANS = {
     'OJF_NO_DENSE_CHAIN': PAIR * 5 + ENTRY + PYRAMID + GROUPED * 2 + TAIL_ENTRY + PYRAMID + GROUPED * 2 + TAIL_HEAD,
-    'OJF_BRANCH_KERNEL': CHAIN + ENTRY + PYRAMID + BRANCH + TAIL_ENTRY + PYRAMID + BRANCH + TAIL_HEAD,
-    'OJF_SUBCONV': CHAIN + ENTRY + PYRAMID + SUBCONV * 2 + TAIL_ENTRY + PYRAMID + SUBCONV * 2 + TAIL_HEAD,
 }

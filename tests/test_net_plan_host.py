@@ -1,7 +1,8 @@
 """CPU: the fusion net's forward plan (ojf_net_plan: the planner ojf_net_create runs, on a bare shape - no device) against the launch
-sequences recorded from the commit before the plan existed (net_plan_cases.py), its refusals, and the three test-only switches
-(read once per process: child processes)."""
+sequences recorded from the commit before the plan existed (net_plan_cases.py), its refusals, the test-only switch (read once per
+process: child processes) and the retired switches, which change nothing."""
 import ctypes
+import json
 import os
 import subprocess
 import sys
@@ -54,6 +55,30 @@ def test_switches_change_the_plan_as_they_change_the_run(switch):
     got = out.stdout.split('\n')[:-1]
     assert got == cases.SWITCH_PLANS[switch]
     assert got != cases.PLANS[(3, 0, 9, 5, 24, 32, 'f16x3')]
+
+
+_ALL_ROWS_SCRIPT = """
+import json, sys
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + '/tests')
+from online_joint_depthfusion_and_semantic_amd.engine import FusionNetEngine
+import net_plan_cases as cases
+print(json.dumps([FusionNetEngine.plan(v, p, g, s, h, w, a) for v, s, p, g, h, w, a in cases.PLANS]))
+"""
+
+
+def test_retired_switches_are_inert():
+    """OJF_BRANCH_KERNEL=1 and OJF_SUBCONV=1 once selected vortex_branch_kernel / subconv_kernel (removed).  With both
+    set, every row of the table and the row of the remaining switch still plan what the table records."""
+    env = {k: v for k, v in os.environ.items() if k not in cases.SWITCH_PLANS}
+    env.update(OJF_BRANCH_KERNEL='1', OJF_SUBCONV='1')
+    out = subprocess.run([sys.executable, '-c', _ALL_ROWS_SCRIPT, ROOT], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert dict(zip(cases.PLANS, json.loads(out.stdout))) == cases.PLANS
+    for switch, plan in cases.SWITCH_PLANS.items():
+        out = subprocess.run([sys.executable, '-c', _SWITCH_SCRIPT, ROOT], env=dict(env, **{switch: '1'}), capture_output=True, text=True,
+                             timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        assert out.stdout.split('\n')[:-1] == plan
 
 
 def _refused(*args):

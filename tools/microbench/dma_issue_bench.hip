@@ -1,5 +1,5 @@
-// What does it cost a wave to ASK for data on gfx950?  (round 4: the persistent LDS-resident kernels - dense_chain_kernel,
-// vortex_branch_kernel - lose 20-35 % of every step to the waves that fetch the next window, see profiles/r04_pair_experiments.txt.)
+// What does it cost a wave to ASK for data on gfx950?  (round 4: the persistent LDS-resident kernels - dense_chain_kernel and
+// the since-removed vortex_branch_kernel - lost 20-35 % of every step to the waves that fetch the next window, see profiles/r04_pair_experiments.txt.)
 // One block of 16 waves per CU (150 KB of LDS requested).  `nm` waves run an MFMA + ds_read_b128 loop (what the computing waves of
 // those kernels do), `nl` waves each issue `nops` memory instructions of one kind back to back and stamp s_memtime before the
 // first, after the last has been ISSUED, and after all have RETURNED:
