@@ -208,6 +208,24 @@ int ojf_conv2d(const float *in_dev, int in_stride, int in_off, float *out_dev, i
                int out_off, const ojf_conv_layer *layer_host, int act, int h, int w,
                ojf_stream_t stream);
 
+/* Test entry point: exactly the pool pyramid launch of a VortexPooling in the net's forward pass (same kernel, same grid rule),
+ * on caller-supplied device buffers.  Planes: [group][h*w] float4, 16-byte aligned.  z_dev: the entry GEMM's 4*c4 groups, branch
+ * b = 1..3 pre-activation = groups [b*c4, (b+1)*c4); q<b>_dev (c4 groups each) = ReLU(pool^b(z) + bias<b>_dev[c4*4]), pool =
+ * 3x3 average, zero padding, always / 9.  With z2_dev (two-head nets) z + z2 is pooled and q0_dev = ReLU(z + z2 + bias0_dev) of
+ * groups [0, c4).  split_out: the outputs are split planes ({4 fp16 high halves | 4 low halves} per float4).
+ * colsums_dev (optional): one block of the launch also folds the global-average branch into the final convolution's bias -
+ *   mean[c] = (sum over 16 shards) * 2^-20 / (h*w), NaN where the channel's flag is set, c < cphys
+ *   g[t] = bg[t] + sum_c wg_t[c][t] mean[c] (fmaf chain, c ascending; wg_t [cphys][c_out]),
+ *   bias_out[t] = bf[t] + sum_j wfg_t[j][t] g[j] (likewise; wfg_t [c_out][c_out]) for t < c_out, 0 for c_out <= t < bias_len
+ * - and leaves the sums zeroed.  Both matrices are read as whole float4: 16-byte aligned, allocated up to a multiple of 16 bytes.
+ * colsums_dev: int64 fix[16][256] (2^-20 fixed point), then uint32 bad[256].
+ * Asynchronous on `stream`. */
+int ojf_pool_pyramid(const float *z_dev, const float *z2_dev, float *q1_dev, float *q2_dev, float *q3_dev, float *q0_dev,
+                     const float *bias1_dev, const float *bias2_dev, const float *bias3_dev, const float *bias0_dev, int h, int w,
+                     int c4, int split_out, void *colsums_dev, const float *wg_t_dev, const float *bg_dev,
+                     const float *wfg_t_dev, const float *bf_dev, int cphys, int c_out, float *bias_out_dev, int bias_len,
+                     ojf_stream_t stream);
+
 /* ---- SEGCONV: convolutions of the 2-D semantic front-end (AdapNet++) ---------------------------
  * One prepacked layer = nn.Conv2d (groups 1, square kernel <= 7, any stride / dilation / zero padding) with what
  * follows it in modules/adapnet.py folded in: eval-mode BatchNorm as scale_host[c_out] (multiplied into the weights)

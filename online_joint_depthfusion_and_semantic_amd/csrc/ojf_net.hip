@@ -1189,6 +1189,7 @@ struct ColSums {
     long long fix[kColShards][kColMax];
     unsigned bad[kColMax];
 };
+static_assert(sizeof(ColSums) == kColShards * kColMax * 8 + kColMax * 4, "the layout include/ojf.h gives for ojf_pool_pyramid");
 constexpr int colsum_row(int nt) { return nt > 8 ? 256 : 128; }  // floats per wave row of block_colsum's LDS scratch
 
 template <int MT, int NT, int NA>
@@ -1438,7 +1439,8 @@ __global__ __launch_bounds__(kChainThreads, kChainBlocks) void vortex_tail_kerne
 // times by nn.AvgPool2d(3, 1, 1) (zero padding, count_include_pad: always / 9), then bias + ReLU.  One launch:
 // a block takes a 32x8-pixel tile of ONE channel group, stages it with a halo of b pixels in LDS and applies the b
 // pooling levels there (every level is zero outside the image, like the padded intermediate tensors of the
-// reference); the intermediate levels never reach HBM.  Summation order per level = row-major taps, as before.
+// reference); the intermediate levels never reach HBM.  Summation order per level = row-major taps, as before, then one
+// correctly rounded division by 9 (div9).  Where the launch's time goes: profiles/pool_pyramid_launch.txt.
 // (used by gave_bias_block below; declared here because the pyramid launch carries one)
 struct GaveArgs {
     const float *partial;   // general flow: nparts rows of pstride floats, added in row order
@@ -1467,6 +1469,20 @@ struct PyramidArgs {
 };
 
 constexpr int kPoolTW = 32, kPoolTH = 8, kPoolStride = kPoolTW + 6;
+constexpr int kPoolPH = 2;  // outputs per thread and level, a column (4: 82 VGPRs, five blocks per CU instead of eight)
+static_assert((kPoolTW + 4) * ((kPoolTH + 4 + kPoolPH - 1) / kPoolPH) <= 256, "one pass of the block covers the widest level");
+
+// x / 9.0f, correctly rounded, in five instructions instead of the compiler's division sequence (scale, reciprocal, four fused steps,
+// fix-up: the divisions were a quarter of the pooling blocks' run time): q = RN(x * RN(1/9)) is within an ulp, the residual x - 9 q is
+// exact in one fma, and q + residual * RN(1/9) rounds to RN(x / 9).  Compared with x / 9.0f over ALL 2^32 bit patterns on the host
+// (denormals included): equal bit for bit except for -0 and the infinities, where q == x (and only there) - those return x.  NaN stays NaN.
+__device__ __forceinline__ float div9(float x)
+{
+    const float r = 1.0f / 9.0f;
+    const float q = x * r;
+    const float f = __builtin_fmaf(__builtin_fmaf(-9.0f, q, x), r, q);
+    return q == x ? x : f;
+}
 
 // LV = pooling levels of this block's channel group: region sizes are compile-time (the per-element index
 // divisions become multiplies)
@@ -1480,60 +1496,103 @@ __device__ __forceinline__ void pool_pyramid_body(const PyramidArgs &a, f32x4 (&
     const f32x4 *plane = a.z + (size_t)(LV * a.c4 + cg) * npix;
     const f32x4 *plane2 = a.z2 ? a.z2 + (size_t)(LV * a.c4 + cg) * npix : nullptr;  // (uniform)
     const f32x4 zero{0.f, 0.f, 0.f, 0.f};
-    {
-        constexpr int W0 = kPoolTW + 2 * LV, H0 = kPoolTH + 2 * LV;
+    {   // the tile with its halo: every load is requested before the first one is waited for
+        constexpr int W0 = kPoolTW + 2 * LV, H0 = kPoolTH + 2 * LV, N0 = (W0 * H0 + 255) / 256;
+        f32x4 v[N0];
+        int at[N0];  // pixel, -1 outside the image (or past the region)
 #pragma unroll
-        for (int i0 = 0; i0 < W0 * H0; i0 += 256) {
-            const int i = i0 + threadIdx.x;
-            if (i >= W0 * H0) break;
+        for (int k = 0; k < N0; ++k) {
+            const int i = k * 256 + threadIdx.x;
             const int ly = i / W0, lx = i - ly * W0;
             const int gy = y0 - LV + ly, gx = x0 - LV + lx;
-            const bool in = (unsigned)gy < (unsigned)a.h && (unsigned)gx < (unsigned)a.w;
-            f32x4 v = in ? plane[gy * a.w + gx] : zero;
-            if (plane2 && in) v += plane2[gy * a.w + gx];
-            buf[0][ly * kPoolStride + lx] = v;
+            const bool in = i < W0 * H0 && (unsigned)gy < (unsigned)a.h && (unsigned)gx < (unsigned)a.w;
+            at[k] = in ? gy * a.w + gx : -1;
+            v[k] = in ? plane[at[k]] : zero;
+        }
+        if (plane2) {
+#pragma unroll
+            for (int k = 0; k < N0; ++k)
+                if (at[k] >= 0) v[k] += plane2[at[k]];
+        }
+#pragma unroll
+        for (int k = 0; k < N0; ++k) {
+            const int i = k * 256 + threadIdx.x;
+            const int ly = i / W0, lx = i - ly * W0;
+            if (i < W0 * H0) buf[0][ly * kPoolStride + lx] = v[k];
         }
     }
     __syncthreads();
+    // A thread forms a column of kPoolPH outputs of a level from registers: the kPoolPH + 2 source rows of three values each are read once
+    // (3 (PH + 2) / PH LDS reads per output instead of 9) and every output adds its nine taps in row-major order, as before.
 #pragma unroll
     for (int l = 1; l <= LV; ++l) {
         const int halo = LV - l;  // halo of this level's region; the source region has halo + 1
-        const int Wl = kPoolTW + 2 * halo, Hl = kPoolTH + 2 * halo;
+        const int Wl = kPoolTW + 2 * halo, Hl = kPoolTH + 2 * halo, NP = (Hl + kPoolPH - 1) / kPoolPH;
+        const bool whole = Hl % kPoolPH == 0;  // no ragged last patch
         const f32x4 *src = buf[(l - 1) & 1];
+        const int i = threadIdx.x;
+        if (i < Wl * NP) {
+            const int pr = i / Wl, lx = i - pr * Wl, ly0 = pr * kPoolPH;
+            f32x4 acc[kPoolPH];
 #pragma unroll
-        for (int i0 = 0; i0 < Wl * Hl; i0 += 256) {
-            const int i = i0 + threadIdx.x;
-            if (i >= Wl * Hl) break;
-            const int ly = i / Wl, lx = i - ly * Wl;
-            const int gy = y0 - halo + ly, gx = x0 - halo + lx;
-            const bool in = (unsigned)gy < (unsigned)a.h && (unsigned)gx < (unsigned)a.w;
-            f32x4 s = zero;
+            for (int o = 0; o < kPoolPH; ++o) acc[o] = zero;
 #pragma unroll
-            for (int dy = 0; dy < 3; ++dy)
+            for (int r = 0; r < kPoolPH + 2; ++r) {
+                if (whole || ly0 + r < Hl + 2) {
+                    const f32x4 *row = src + (ly0 + r) * kPoolStride + lx;
+                    const f32x4 t0 = row[0], t1 = row[1], t2 = row[2];
 #pragma unroll
-                for (int dx = 0; dx < 3; ++dx) s += src[(ly + dy) * kPoolStride + lx + dx];
-            s = s / 9.0f;
-            if (l < LV) {
-                buf[l & 1][ly * kPoolStride + lx] = in ? s : zero;
-            } else if (in) {
-                s += *reinterpret_cast<const f32x4 *>(a.bias[LV - 1] + 4 * cg);
+                    for (int o = 0; o < kPoolPH; ++o)
+                        if (r - o >= 0 && r - o <= 2) {  // tap row r - o of output o
+                            acc[o] += t0;
+                            acc[o] += t1;
+                            acc[o] += t2;
+                        }
+                }
+            }
+            const int gx = x0 - halo + lx;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) s[j] = s[j] < 0.0f ? 0.0f : s[j];  // keeps NaN, like torch.relu
-                a.q[LV - 1][(size_t)cg * npix + gy * a.w + gx] = a.split_out ? split_pack4(s) : s;
+            for (int o = 0; o < kPoolPH; ++o) {
+                const int ly = ly0 + o, gy = y0 - halo + ly;
+                if (!whole && ly >= Hl) break;
+                const bool in = (unsigned)gy < (unsigned)a.h && (unsigned)gx < (unsigned)a.w;
+                f32x4 s;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) s[j] = div9(acc[o][j]);
+                if (l < LV) {
+                    buf[l & 1][ly * kPoolStride + lx] = in ? s : zero;
+                } else if (in) {
+                    s += *reinterpret_cast<const f32x4 *>(a.bias[LV - 1] + 4 * cg);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) s[j] = s[j] < 0.0f ? 0.0f : s[j];  // keeps NaN, like torch.relu
+                    a.q[LV - 1][(size_t)cg * npix + gy * a.w + gx] = a.split_out ? split_pack4(s) : s;
+                }
             }
         }
         if (l < LV) __syncthreads();
     }
 }
 
-__device__ __forceinline__ void gave_bias_block(const GaveArgs &a, float *mean, float *gv);
+constexpr int kGaveLds = 128 + 256 * 3;  // float4 of LDS gave_bias_block works in
+__device__ __forceinline__ void gave_bias_block(const GaveArgs &a, float *lds);
 
-__global__ __launch_bounds__(256) void pool_pyramid_kernel(const PyramidArgs a)
+#ifdef OJF_POOL_STAMPS  // profiling build only (tools/pool_stamps.py): wall-clock stamps (100 MHz) of every block's start and end, thread 0
+constexpr int kPoolStampBlocks = 8192;
+__device__ unsigned long long g_pool_stamps[kPoolStampBlocks][2];
+#define POOL_STAMP(i) do { const unsigned b_ = blockIdx.y * gridDim.x + blockIdx.x; if (threadIdx.x == 0 && b_ < (unsigned)kPoolStampBlocks - 8) g_pool_stamps[b_][i] = wall_clock64(); } while (0)
+// phases of the block that folds the global-average branch, in the last eight rows: 0 start, 1 mean formed, 2 first mat-vec done, 3 end
+#define FOLD_STAMP(i) do { if (threadIdx.x == 0) g_pool_stamps[kPoolStampBlocks - 8 + (i)][0] = wall_clock64(); } while (0)
+#else
+#define POOL_STAMP(i) do { } while (0)
+#define FOLD_STAMP(i) do { } while (0)
+#endif
+
+__device__ __forceinline__ void pool_pyramid_block(const PyramidArgs &a, f32x4 (&buf)[2][kPoolStride * (kPoolTH + 6)])
 {
-    __shared__ f32x4 buf[2][kPoolStride * (kPoolTH + 6)];
-    if (banded_block_x() >= a.tiles) {  // one of the padding blocks: the global-average branch -> bias of the final conv (hidden behind the pools)
-        if (blockIdx.y == 0 && banded_block_x() == a.tiles && a.fold_gave)
-            gave_bias_block(a.gave, reinterpret_cast<float *>(buf), reinterpret_cast<float *>(buf) + 256);
+    static_assert(2 * kPoolStride * (kPoolTH + 6) >= kGaveLds, "the fold block works in the pools' LDS");
+    if (banded_block_x() >= a.tiles) {  // one of the padding blocks: the global-average branch -> bias of the final conv
+        // (it starts with the launch and has to end before the pools do: its weights stream in, see gave_bias_block)
+        if (blockIdx.y == 0 && banded_block_x() == a.tiles && a.fold_gave) gave_bias_block(a.gave, reinterpret_cast<float *>(buf));
         return;
     }
     // levels of this block's group.  The groups are dispatched in blockIdx.y order: the three-level blocks (three cascaded pools from one
@@ -1557,6 +1616,14 @@ __global__ __launch_bounds__(256) void pool_pyramid_kernel(const PyramidArgs a)
     if (lv == 1) pool_pyramid_body<1>(a, buf, cg);
     else if (lv == 2) pool_pyramid_body<2>(a, buf, cg);
     else pool_pyramid_body<3>(a, buf, cg);
+}
+
+__global__ __launch_bounds__(256) void pool_pyramid_kernel(const PyramidArgs a)
+{
+    __shared__ f32x4 buf[2][kPoolStride * (kPoolTH + 6)];
+    POOL_STAMP(0);
+    pool_pyramid_block(a, buf);
+    POOL_STAMP(1);
 }
 
 constexpr int kSumBlocks = 32;
@@ -1587,22 +1654,110 @@ __global__ __launch_bounds__(256) void colsum_kernel(const f32x4 *in, int g0, in
 //   mean -> 1x1 conv (+BN folded) -> g[c_out];  bias' = bias_final + W_final[:, gave columns] @ g
 // `partial`: nparts rows of pstride floats (per-block channel sums), added in row order.
 
-__device__ __forceinline__ void gave_bias_block(const GaveArgs &a, float *mean /* LDS [256] */, float *gv /* LDS [256] */)
+//
+// The two mat-vecs keep one fmaf chain per output (input channels ascending); only the way the weights arrive differs from
+// one-load-per-step chains (16 dependent global round trips per mat-vec, 0.5-0.7 us each: the whole pyramid launch waited for
+// this block).  No weight address depends on data, so the block streams both matrices, one after the other, as flat 16-byte
+// loads of all 256 threads in chunks of kGaveChunk float4: two chunks are in flight in registers from the top of the block
+// (before the channel sums come back) while the chains consume the chunk that sits in LDS.
+constexpr int kGavePer = 3, kGaveChunk = 256 * kGavePer;  // float4 per thread and per chunk
+static_assert(kGaveLds == 128 + kGaveChunk, "float4: mean[256], gv[256], the chunk");
+
+struct GaveStream {
+    const float *W[2];  // WgT, WfgT
+    int rows[2];        // cphys, c_out
+    int chunks[2];
+    int c_out, R;       // a chunk = R whole rows (a multiple of 4: every chunk starts on a float4), R * c_out <= 4 * kGaveChunk floats
+};
+
+// Every load is unconditional (addresses clamped into the matrix, chunks past the end fetch the last one again): with loads
+// under branches the compiler waits for ALL loads in flight before it writes a chunk to LDS, the younger chunk's included, and
+// the stream is one round trip per chunk again.
+__device__ __forceinline__ void gave_fetch(const GaveStream &gs, int g, f32x4 (&r)[kGavePer])
+{
+    g = min(g, gs.chunks[0] + gs.chunks[1] - 1);
+    const int m = g < gs.chunks[0] ? 0 : 1, k = m ? g - gs.chunks[0] : g;
+    const int f0 = k * gs.R * gs.c_out, last = (gs.rows[m] * gs.c_out - 1) & ~3;  // the matrix's last float4 (its allocation is rounded up)
+    const float *W = gs.W[m];
+#pragma unroll
+    for (int i = 0; i < kGavePer; ++i) r[i] = *reinterpret_cast<const f32x4 *>(W + min(f0 + 4 * (i * 256 + (int)threadIdx.x), last));
+}
+
+// chunk g: registers -> LDS, the registers take chunk g + 2, the chains advance over the rows of the chunk
+__device__ __forceinline__ void gave_step(const GaveArgs &a, const GaveStream &gs, int g, f32x4 (&r)[kGavePer], f32x4 *stage,
+                                          const float *mean, float *gv, float &s, float bf)
 {
     const int t = threadIdx.x;
-    if (a.fixed) {
-        if (t < kColMax) {
-            long long q = 0;
+    if (g >= gs.chunks[0] + gs.chunks[1]) return;  // (uniform)
+    const int m = g < gs.chunks[0] ? 0 : 1, k = m ? g - gs.chunks[0] : g;
+    __syncthreads();  // the chains are done with the previous chunk
 #pragma unroll
-            for (int sh = 0; sh < kColShards; ++sh) {
-                q += a.fixed->fix[sh][t];
-                a.fixed->fix[sh][t] = 0;  // this block is the only reader; the next writers come later in stream order
+    for (int i = 0; i < kGavePer; ++i) stage[i * 256 + t] = r[i];
+    if (m == 1 && k == 0) {  // first mat-vec complete: its result is the second one's input
+        gv[t] = t < a.c_out ? s : 0.0f;
+        s = bf;
+        FOLD_STAMP(2);
+    }
+    gave_fetch(gs, g + 2, r);
+    __syncthreads();
+    if (t < a.c_out) {
+        const int n = min(gs.R, gs.rows[m] - k * gs.R);  // (uniform) rows of this chunk
+        const float *x = (m ? gv : mean) + k * gs.R, *wl = reinterpret_cast<const float *>(stage) + t;
+#pragma unroll 8
+        for (int c = 0; c < n; ++c) s = __builtin_fmaf(wl[c * a.c_out], x[c], s);
+    }
+}
+
+__device__ __forceinline__ void gave_bias_block(const GaveArgs &a, float *lds /* LDS [4 * kGaveLds], 16-byte aligned */)
+{
+    float *mean = lds, *gv = lds + 256;
+    f32x4 *stage = reinterpret_cast<f32x4 *>(lds + 512);
+    const int t = threadIdx.x;
+    GaveStream gs;
+    gs.W[0] = a.WgT; gs.W[1] = a.WfgT;
+    gs.rows[0] = a.cphys; gs.rows[1] = a.c_out;
+    gs.c_out = a.c_out; gs.R = (4 * kGaveChunk / a.c_out) & ~3;  // c_out <= 256: R >= 12
+    for (int m = 0; m < 2; ++m) gs.chunks[m] = (gs.rows[m] + gs.R - 1) / gs.R;
+    FOLD_STAMP(0);
+    f32x4 r0[kGavePer], r1[kGavePer];
+    gave_fetch(gs, 0, r0);
+    gave_fetch(gs, 1, r1);
+    const float bg = t < a.c_out ? a.bg[t] : 0.0f, bf = t < a.c_out ? a.bf[t] : 0.0f;
+    if (a.fixed) {
+        // (sixteen shard loads per thread in flight beside the two weight chunks cost the kernel its eight blocks per CU: 82 VGPRs)
+        long long *qs = reinterpret_cast<long long *>(stage);  // (free until the first chunk lands)
+        static_assert(kColMax == 256, "one thread per channel");
+        const bool bad = a.fixed->bad[t] != 0;
+        a.fixed->bad[t] = 0;
+        long long q = 0;
+        if (a.cphys <= 128) {  // one round trip: two threads per channel, eight shards each; integer sums do not depend on the order
+            const int ch = t & 127, s0 = (t >> 7) * 8;
+            long long part[8];
+#pragma unroll
+            for (int sh = 0; sh < 8; ++sh) part[sh] = a.fixed->fix[s0 + sh][ch];
+#pragma unroll
+            for (int sh = 0; sh < 8; ++sh) {
+                q += part[sh];
+                a.fixed->fix[s0 + sh][ch] = 0;  // this block is the only reader; the next writers come later in stream order
             }
-            const bool bad = a.fixed->bad[t] != 0;
-            a.fixed->bad[t] = 0;
-            const float sum = (float)((double)q * (1.0 / (double)kColScale));
-            mean[t] = t < a.cphys ? (bad ? __builtin_nanf("") : sum / (float)a.npix) : 0.0f;
+            if (t >= 128) qs[ch] = q;
+            __syncthreads();
+            if (t < 128) q += qs[t];
+        } else {
+#pragma unroll 1
+            for (int s0 = 0; s0 < kColShards; s0 += 8) {
+                long long part[8];
+#pragma unroll
+                for (int sh = 0; sh < 8; ++sh) part[sh] = a.fixed->fix[s0 + sh][t];
+#pragma unroll
+                for (int sh = 0; sh < 8; ++sh) {
+                    q += part[sh];
+                    a.fixed->fix[s0 + sh][t] = 0;
+                }
+            }
         }
+        const float sum = (float)((double)q * (1.0 / (double)kColScale));
+        mean[t] = t < a.cphys ? (bad ? __builtin_nanf("") : sum / (float)a.npix) : 0.0f;
     } else if (a.cphys <= 128) {  // two threads per channel (rows split in halves) keep 256 loads in flight; fixed order
         const int ch = t & 127, half = t >> 7;
         float s = 0.0f;
@@ -1622,32 +1777,22 @@ __device__ __forceinline__ void gave_bias_block(const GaveArgs &a, float *mean /
         }
         mean[t] = s / (float)a.npix;
     }
-    __syncthreads();
-    float s1 = 0.0f;
-    if (t < a.c_out) {
-        s1 = a.bg[t];
-#pragma unroll 8
-        for (int c = 0; c < a.cphys; ++c) s1 = __builtin_fmaf(a.WgT[(size_t)c * a.c_out + t], mean[c], s1);
+    FOLD_STAMP(1);
+    // s: g[t] = bg[t] + sum_c WgT[c][t] * mean[c], then bias'[t] = bf[t] + sum_j WfgT[j][t] * g[j]; each step starts with a barrier
+    float s = bg;
+    const int total = gs.chunks[0] + gs.chunks[1];
+    for (int g = 0; g < total; g += 2) {
+        gave_step(a, gs, g, r0, stage, mean, gv, s, bf);
+        gave_step(a, gs, g + 1, r1, stage, mean, gv, s, bf);
     }
-    __syncthreads();
-    gv[t] = s1;
-    __syncthreads();
-    if (t < a.bias_len) {
-        float s = 0.0f;
-        if (t < a.c_out) {
-            s = a.bf[t];
-#pragma unroll 8
-            for (int j = 0; j < a.c_out; ++j) s = __builtin_fmaf(a.WfgT[(size_t)j * a.c_out + t], gv[j], s);
-        }
-        a.bias_out[t] = s;
-    }
+    if (t < a.bias_len) a.bias_out[t] = t < a.c_out ? s : 0.0f;
+    FOLD_STAMP(3);
 }
 
 __global__ __launch_bounds__(256) void gave_bias_kernel(const GaveArgs a)
 {
-    __shared__ float mean[256];
-    __shared__ float gv[256];
-    gave_bias_block(a, mean, gv);
+    __shared__ f32x4 lds[kGaveLds];
+    gave_bias_block(a, reinterpret_cast<float *>(lds));
 }
 
 struct PrepArgs {
@@ -2783,7 +2928,8 @@ static int build_vortex(ojf_net *net, int k, const ojf_conv_layer *L, int c_in, 
         ConvBuilder b(4 * os, os, 1, 1);
         b.add(lf, out, 5 * out, slot_map(4 * out, out, os), 0, false);
         if (finish(b, v.fin, net->arith)) return -2;
-        std::vector<float> Wg((size_t)out * c_in_phys, 0.0f), bg(out), Wfg((size_t)out * out), bf(out);
+        // (the two matrices rounded up to whole float4: gave_bias_block streams them as flat 16-byte loads)
+        std::vector<float> Wg(((size_t)out * c_in_phys + 3) / 4 * 4, 0.0f), bg(out), Wfg(((size_t)out * out + 3) / 4 * 4, 0.0f), bf(out);
         for (int o = 0; o < out; ++o) {  // stored transposed: [input][output]
             for (int ci = 0; ci < c_in; ++ci) Wg[(size_t)in_map[ci] * out + o] = L[0].weight_host[(size_t)o * c_in + ci];
             bg[o] = L[0].bias_host[o];
@@ -2844,6 +2990,16 @@ static GaveArgs gave_args(const ojf_net *net, const Vortex &v, const float *part
     ga.WgT = v.Wg; ga.bg = v.bg; ga.WfgT = v.Wfg; ga.bf = v.bf; ga.c_out = net->pool_in;
     ga.bias_out = v.bias_final; ga.bias_len = v.fin.n_ot * 16;
     return ga;
+}
+
+// The pool pyramid launch of filled arguments (h, w, c4, fold_gave, z2 set; tiles is derived here).  grid.x: the tiles (+ the
+// global-average block of the chain flow) rounded up to a multiple of 8 (XCD bands); grid.y: three branches' groups, four with z2
+static dim3 launch_pyramid(PyramidArgs &pa, hipStream_t st)
+{
+    pa.tiles = ((pa.w + kPoolTW - 1) / kPoolTW) * ((pa.h + kPoolTH - 1) / kPoolTH);
+    const dim3 pgrid(round_up(pa.tiles + (pa.fold_gave ? 1 : 0), 8), (pa.z2 ? 4 : 3) * pa.c4);
+    hipLaunchKernelGGL(pool_pyramid_kernel, pgrid, dim3(256), 0, st, pa);
+    return pgrid;
 }
 
 static int chain_blocks(const ojf_net *net) { return ((net->npix + 15) / 16 + ojf::kChainWaves - 1) / ojf::kChainWaves; }  // blocks of the MT = 1 chain kernels
@@ -2913,14 +3069,11 @@ static int run_vortex(ojf_net *net, const VortexStep &s, hipStream_t st, const C
         pa.q[0] = planes(sc.Q1); pa.q[1] = planes(sc.Q2); pa.q[2] = planes(sc.Q3);
         for (int b = 0; b < 3; ++b) pa.bias[b] = v.pool_bias[b + 1];
         pa.h = h; pa.w = w; pa.c4 = c4;
-        pa.tiles = ((w + kPoolTW - 1) / kPoolTW) * ((h + kPoolTH - 1) / kPoolTH);
         pa.gave = gave_args(net, v, nullptr, 0, 0, s.z2 ? net->colsum3 : sc.colsum);
         pa.fold_gave = s.chain_flow ? 1 : 0;
         pa.split_out = s.split ? 1 : 0;
         if (s.z2) { pa.z2 = planes(net->sc[1].Z); pa.q0 = planes(sc.Q0); pa.bias0 = v.bias0; }
-        // grid.x: the tiles (+ the global-average block of the chain flow) rounded up to a multiple of 8 (XCD bands)
-        const dim3 pgrid(round_up(pa.tiles + (s.chain_flow ? 1 : 0), 8), (s.z2 ? 4 : 3) * c4);
-        hipLaunchKernelGGL(pool_pyramid_kernel, pgrid, dim3(256), 0, st, pa);
+        const dim3 pgrid = launch_pyramid(pa, st);
         if (net_trace_on()) fprintf(stderr, "ojf_net %s | tiles %d grid_x %u grid_y %u\n", kLaunchNames[L_POOL_PYRAMID], pa.tiles, pgrid.x, pgrid.y);
         mark_launch(L_POOL_PYRAMID, st);
         OJF_HIP(hipGetLastError());
@@ -3614,6 +3767,43 @@ OJF_API int ojf_conv2d(const float *in, int in_stride, int in_off, float *out, i
     release(pc);
     return rc;
 }
+
+OJF_API int ojf_pool_pyramid(const float *z, const float *z2, float *q1, float *q2, float *q3, float *q0, const float *bias1,
+                             const float *bias2, const float *bias3, const float *bias0, int h, int w, int c4, int split_out,
+                             void *colsums, const float *wg_t, const float *bg, const float *wfg_t, const float *bf, int cphys,
+                             int c_out, float *bias_out, int bias_len, ojf_stream_t stream)
+{
+    using namespace ojf;
+    if (!z || !q1 || !q2 || !q3 || !bias1 || !bias2 || !bias3) return fail("ojf_pool_pyramid: null pointer argument");
+    if (z2 && (!q0 || !bias0)) return fail("ojf_pool_pyramid: z2 needs q0 and bias0");
+    if (h < 1 || w < 1 || c4 < 1 || c4 > 64 || (int64_t)h * w > (1 << 24)) return fail("ojf_pool_pyramid: bad frame size or group count");
+    PyramidArgs pa;
+    pa.z = planes(z); pa.z2 = z2 ? planes(z2) : nullptr;
+    pa.q[0] = planes(q1); pa.q[1] = planes(q2); pa.q[2] = planes(q3); pa.q0 = z2 ? planes(q0) : nullptr;
+    pa.bias[0] = bias1; pa.bias[1] = bias2; pa.bias[2] = bias3; pa.bias0 = z2 ? bias0 : nullptr;
+    pa.h = h; pa.w = w; pa.c4 = c4;
+    pa.split_out = split_out ? 1 : 0;
+    pa.fold_gave = colsums ? 1 : 0;
+    pa.gave = GaveArgs{};
+    if (colsums) {
+        if (!wg_t || !bg || !wfg_t || !bf || !bias_out) return fail("ojf_pool_pyramid: null pointer argument (fold)");
+        if (cphys < 1 || cphys > kColMax || c_out < 1 || c_out > 256 || bias_len < 0 || bias_len > 256)
+            return fail("ojf_pool_pyramid: fold sizes beyond one block (256)");
+        GaveArgs &ga = pa.gave;
+        ga.partial = nullptr; ga.fixed = static_cast<ColSums *>(colsums); ga.nparts = 0; ga.pstride = 0; ga.cphys = cphys; ga.npix = h * w;
+        ga.WgT = wg_t; ga.bg = bg; ga.WfgT = wfg_t; ga.bf = bf; ga.c_out = c_out;
+        ga.bias_out = bias_out; ga.bias_len = bias_len;
+    }
+    launch_pyramid(pa, as_stream(stream));
+    return check_hip(hipGetLastError(), "ojf_pool_pyramid launch");
+}
+
+#ifdef OJF_POOL_STAMPS
+extern "C" __attribute__((visibility("default"))) int ojf_debug_pool_stamps(void *host_dst, size_t bytes)
+{
+    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(ojf::g_pool_stamps), bytes < sizeof(ojf::g_pool_stamps) ? bytes : sizeof(ojf::g_pool_stamps));
+}
+#endif
 
 #include "ojf_net_train.h"
 #include "ojf_train_net.h"
