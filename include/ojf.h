@@ -741,6 +741,53 @@ int ojf_rasterize_attributes(const float *vertices_dev, int nv, const int *faces
                              const uint8_t *vertex_rgba_dev /* u8[nv][4] or NULL */, uint8_t *labels_dev /* u8[n,h,w] or NULL */,
                              uint8_t *rgba_dev /* u8[n,h,w,4] or NULL */, ojf_stream_t stream);
 
+/* ---- MESH DISTANCE (exact Euclidean distance from voxel centres to a triangle mesh; the reference runs a distance
+ *      transform over a voxelised mesh) ----------------------------------------------------------------------------------
+ * ojf_mesh_distance: for every voxel of the box (origin_host f64[3], resolution, X, Y, Z; voxel (i, j, k) has its centre
+ *   at the fp32 rounding of origin + (index + 0.5) * resolution, the frame of extract / integrate / render /
+ *   ojf_fuse_projective) the distance to the mesh vertices_dev f32[nv][3] / faces_dev i32[nf][3] where it is at most band,
+ *   and the nearest face.  The squared distance d2 to a triangle is the fp32 minimum of the three segment candidates
+ *   (parameter clamped to [0, 1], 0 for an edge of zero length) and, where the triangle has area and the three edge
+ *   functions are >= 0, the plane candidate h*h / n.n: a zero-area face is its edges, nothing divides by zero.  A voxel
+ *   keeps the minimum of (bits(d2) << 32) | face over the faces with d2 <= (float)band * (float)band: the nearest face, ties
+ *   to the lower index.  distance_dev f32[X,Y,Z] = sqrtf(d2), +inf where no face is that near; face_dev i32[X,Y,Z], -1
+ *   there.  A face with an index outside [0, nv) or a non-finite vertex is skipped.  The outputs do not depend on how the
+ *   triangles are binned or visited: the same bits on every run and for every order of the faces (up to the face index at
+ *   exact ties).
+ *   Triangles are binned into bricks of 8 x 8 x 8 voxels (count, scan, fill: integer atomics only) and one workgroup per
+ *   brick gathers the minimum over its list.  The number of (triangle, brick) pairs is not known in advance: call once with
+ *   capacity = 0 (pairs_dev, distance_dev, face_dev may be NULL) to get *count_dev = that number, then again with pairs_dev
+ *   u32[capacity], capacity >= that number.  *count_dev (u64, may be NULL) always receives the full number; with a smaller
+ *   capacity the lists are cut short, the outputs are unspecified and nothing is written out of bounds.
+ *   workspace_dev: ojf_mesh_distance_workspace_bytes(X, Y, Z) bytes (per-brick counts, offsets, cursors), 8-byte aligned.
+ *   phases: OJF_MESH_DISTANCE_ALL, or - for measurement - a subset of the phase bits, run in the order bin, scan, fill,
+ *   gather on the workspace and the lists that earlier calls with the same arguments left.  Never waits.
+ * ojf_mesh_distance_sign: signed_dev f32[X,Y,Z] = +-distance_dev by the angle-weighted pseudonormal of the closest
+ *   feature of the voxel's face_dev (same mesh and box as the call that wrote them): the face itself (the sign of h), an
+ *   edge (edge_normals_dev f32[ne][3] at face_edges_dev i32[nf][3], entry k for the edge from vertex k to vertex k + 1) or
+ *   a vertex (vertex_normals_dev f32[nv][3]); negative where (voxel - closest point) . N < 0, +inf where face_dev < 0.
+ *   Positive outside a closed, consistently outward-wound, non-self-intersecting mesh; meaningless for anything else.
+ *   One kernel, never waits.
+ * Bad arguments (sizes, X*Y*Z or 3*nf >= 2^31, non-finite origin / resolution / band, band <= 0, null required pointers, a
+ *   workspace that is too small) are refused before any HIP call.  The exact fp32 operation order is in
+ *   csrc/ojf_mesh_distance.hip. */
+#define OJF_MESH_DISTANCE_BIN 1
+#define OJF_MESH_DISTANCE_SCAN 2
+#define OJF_MESH_DISTANCE_FILL 4
+#define OJF_MESH_DISTANCE_GATHER 8
+#define OJF_MESH_DISTANCE_ALL 15
+size_t ojf_mesh_distance_workspace_bytes(int X, int Y, int Z);
+int ojf_mesh_distance(const float *vertices_dev /* f32[nv][3] */, int nv, const int *faces_dev /* i32[nf][3] */, int nf,
+                      const double *origin_host, double resolution, int X, int Y, int Z, float band, int phases,
+                      void *workspace_dev, size_t workspace_bytes, uint32_t *pairs_dev /* u32[capacity] */, uint32_t capacity,
+                      uint64_t *count_dev, float *distance_dev /* f32[X,Y,Z] */, int *face_dev /* i32[X,Y,Z] */,
+                      ojf_stream_t stream);
+int ojf_mesh_distance_sign(const float *vertices_dev, int nv, const int *faces_dev, int nf, const double *origin_host,
+                           double resolution, int X, int Y, int Z, const float *distance_dev, const int *face_dev,
+                           const float *vertex_normals_dev /* f32[nv][3] */, const float *edge_normals_dev /* f32[ne][3] */,
+                           int ne, const int *face_edges_dev /* i32[nf][3] */, float *signed_dev /* f32[X,Y,Z] */,
+                           ojf_stream_t stream);
+
 /* ---- RESAMPLE (re-box, resample and merge fused volumes; no counterpart in the reference) ------------------------------
  * Every voxel (i,j,k) of a destination grid [dX,dY,dZ] reads the source grid [sX,sY,sZ] at the index coordinates
  *   g = M (i,j,k) + c (M_host f64[9] row-major, c_host f64[3]; rounded once to fp32; voxel (i,j,k) of the source sits at

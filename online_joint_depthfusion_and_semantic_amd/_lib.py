@@ -51,6 +51,7 @@ COLOR_MAX_VIEWS = 32  # include/ojf.h OJF_COLOR_MAX_VIEWS
 RASTER_MAX_VIEWS = 32  # include/ojf.h OJF_RASTER_MAX_VIEWS
 LABEL_MAX_VIEWS = 32  # include/ojf.h OJF_LABEL_MAX_VIEWS
 RESAMPLE_REPLACE, RESAMPLE_MERGE = 0, 1  # include/ojf.h OJF_RESAMPLE_REPLACE / OJF_RESAMPLE_MERGE
+MESH_DISTANCE_BIN, MESH_DISTANCE_SCAN, MESH_DISTANCE_FILL, MESH_DISTANCE_GATHER, MESH_DISTANCE_ALL = 1, 2, 4, 8, 15  # OJF_MESH_DISTANCE_*
 
 
 class ExtractJob(ctypes.Structure):
@@ -184,6 +185,13 @@ SIGNATURES = {
     'ojf_rasterize': (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
     # vertices, nv, faces, nf, n, K, E, h, w, face, face labels, vertex rgba, labels, rgba, stream
     'ojf_rasterize_attributes': (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'ojf_mesh_distance_workspace_bytes': (_sz, [_i, _i, _i]),
+    # vertices, nv, faces, nf, origin, resolution, X, Y, Z, band, phases, workspace, workspace_bytes, pairs, capacity, count,
+    # distance, face, stream
+    'ojf_mesh_distance': (_i, [_vp, _i, _vp, _i, _vp, _d, _i, _i, _i, _f, _i, _vp, _sz, _vp, _c.c_uint32, _vp, _vp, _vp, _vp]),
+    # vertices, nv, faces, nf, origin, resolution, X, Y, Z, distance, face, vertex normals, edge normals, ne, face edges,
+    # signed, stream
+    'ojf_mesh_distance_sign': (_i, [_vp, _i, _vp, _i, _vp, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     # source tsdf, weights, ids, scores, sX, sY, sZ, destination tsdf, weights, ids, scores, dX, dY, dZ, M, c, init_value, mode,
     # max_weight, stream
     'ojf_resample_volumes': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _f, _i, _f, _vp]),

@@ -175,14 +175,22 @@ class MeshStream:
 
 
 def ground_truth_grid(vertices, faces, *, origin, resolution, shape, truncation, intrinsics, extrinsics, image_shape,
-                      face_labels=None, max_weight=128.0, near=0.0):
+                      face_labels=None, max_weight=128.0, near=0.0, distance='projective'):
     """Ground-truth volumes of a mesh: the views are rasterised and fused by ``projective.integrate_depth(carve=True)``,
     with the face labels where given.  origin / resolution / shape (X, Y, Z): the volume, in the frame of extract /
     integrate / render; intrinsics / extrinsics / image_shape (h, w): the views, as for ``rasterize`` - they should see
     every surface from the free side.  Returns device (tsdf fp16 [X,Y,Z], labels u8 [X,Y,Z]); voxels no view reached
-    (weight 0) hold -truncation and label 0: the "solid" value datasets.py pads ground-truth grids with."""
+    (weight 0) hold -truncation and label 0: the "solid" value datasets.py pads ground-truth grids with.
+
+    distance='projective' (the default): the fused values as they are - distances along the optical axes.
+    distance='euclidean': the views give only the sign - positive where a view reached the voxel and the fused value is
+    > 0, negative everywhere else; the value is sign·min(d, truncation) with d the exact distance to the mesh
+    (``mesh_distance.distance_field(band=truncation)``), and the label that of the nearest face where d < truncation, 0
+    elsewhere: a Euclidean TSDF, and labels that do not depend on the list of poses."""
     if not (torch.is_tensor(vertices) and vertices.is_cuda):
         raise ValueError('ground_truth_grid: vertices must be a cuda tensor [nv,3]')
+    if distance not in ('projective', 'euclidean'):
+        raise ValueError("ground_truth_grid: distance must be 'projective' or 'euclidean'")
     dev = vertices.device
     truncation = float(truncation)
     X, Y, Z = (int(s) for s in shape)
@@ -198,6 +206,13 @@ def ground_truth_grid(vertices, faces, *, origin, resolution, shape, truncation,
     unseen = weights == 0
     tsdf.masked_fill_(unseen, -truncation)
     ids.masked_fill_(unseen, 0)
+    if distance == 'euclidean':
+        from .mesh_distance import distance_field
+        field = distance_field(vertices, faces, origin=origin, resolution=resolution, shape=(X, Y, Z), band=truncation,
+                               face_labels=face_labels)
+        d = field['distance'].clamp(max=float(np.float32(truncation)))
+        tsdf = torch.where(tsdf > 0, d, -d).to(torch.float16)  # (unseen voxels hold -truncation: negative)
+        ids = torch.where(field['distance'] < truncation, field['labels'], torch.zeros_like(ids)) if sem else torch.zeros_like(ids)
     return tsdf, ids
 
 

@@ -1,0 +1,158 @@
+"""CPU: the numpy restatement of the mesh distance field (mesh_distance_ref.py, the definition in
+csrc/ojf_mesh_distance.hip) against a float64 brute force by another route, against the analytic scene, and on degenerate
+input; the sign by pseudonormals against analytic solids.  The GPU tests pin the kernels to this restatement bit for bit.
+
+Measured on x86-64 (max |d_f32 - d_f64| over the voxels in the band): room 4.129e-8 m, closed box
+1.517e-7 m, bumpy patch 2.310e-8 m; room against |scene_sdf| inside the room: 9.537e-8 m (the float64 brute force has the
+same 9.537e-8: the fp32 rounding of the vertices).  The computation is deterministic; the bounds below are twice these."""
+import numpy as np
+import pytest
+
+from online_joint_depthfusion_and_semantic_amd import synthetic
+import mesh_distance_ref as ref
+import raster_ref
+
+F = np.float32
+BOX_GRID = dict(origin=np.array([-1.5, -1.2, -0.9]), res=0.09, shape=(32, 32, 32))
+PATCH_ORIGIN = np.array([-1.45, -1.12, -0.33])
+
+
+def _cases():
+    o, r = ref.room32_spec()
+    return {
+        'room': (raster_ref.room_mesh(), o, r, ref.ROOM32['shape'], ref.ROOM32['band'], 2 * 4.129e-8),
+        'box': (ref.closed_box(), BOX_GRID['origin'], BOX_GRID['res'], BOX_GRID['shape'], 0.3, 2 * 1.517e-7),
+        'patch': (raster_ref.bumpy_patch(), PATCH_ORIGIN, 0.15, (20, 15, 6), 0.2, 2 * 2.310e-8),
+    }
+
+
+@pytest.mark.parametrize('name', ['room', 'box', 'patch'])
+def test_restatement_against_the_float64_brute_force(name):
+    mesh, origin, res, shape, band, bound = _cases()[name]
+    d, f = ref.cached_field('host_' + name, mesh, origin, res, shape, band)
+    y = ref.distance_f64(ref.centres_f64(origin, res, shape), mesh['vertices'], mesh['faces']).reshape(shape)
+    hit = np.isfinite(d)
+    err = float(np.abs(d[hit].astype(np.float64) - y[hit]).max())
+    print('{}: {:.1f} % of the voxels in the band, max |d_f32 - d_f64| = {:.4e} m (bound {:.4e})'.format(name, 100 * hit.mean(), err, bound))
+    assert 0.25 < hit.mean() < 0.6
+    if name == 'room':
+        assert abs(hit.mean() - 0.32) < 0.01
+    assert err <= bound
+    assert ((f >= 0) == hit).all() and (d[hit] >= 0).all()
+    # the band is cut where the definition cuts it, up to the same error
+    assert (y[~hit] > band - bound).all() and (y[hit] < band + bound).all()
+    # the nearest face is a nearest face: its own float64 distance is the minimum, up to the error
+    for v in np.flatnonzero(hit.ravel())[::97]:
+        one = ref.distance_f64(ref.centres_f64(origin, res, shape)[v:v + 1], mesh['vertices'], mesh['faces'][f.ravel()[v]][None])
+        assert abs(one[0] - y.ravel()[v]) <= bound
+
+
+def test_room_against_the_analytic_scene():
+    mesh, origin, res, shape, band, _ = _cases()['room']
+    d, _ = ref.cached_field('host_room', mesh, origin, res, shape, band)
+    P = ref.centres_f64(origin, res, shape)
+    inside = ((P > synthetic.ROOM_MIN) & (P < synthetic.ROOM_MAX)).all(axis=1).reshape(shape)
+    assert inside.sum() == 16200
+    sdf = np.abs(synthetic.scene_sdf(P)).reshape(shape)
+    m = inside & np.isfinite(d)
+    err = float(np.abs(d[m] - sdf[m]).max())
+    print('room: {} voxel centres inside, {} in the band, max |d - |scene_sdf|| = {:.4e} m'.format(inside.sum(), m.sum(), err))
+    assert m.sum() > 5000 and err <= 2 * 9.537e-8
+    assert (sdf[inside & ~np.isfinite(d)] > band - 2e-7).all()
+
+
+def test_sign_by_pseudonormals_on_the_closed_box():
+    mesh = ref.closed_box()
+    g = BOX_GRID
+    d, f = ref.distance_field(mesh['vertices'], mesh['faces'], g['origin'], g['res'], g['shape'], 10.0)
+    s = ref.signed_distance(mesh['vertices'], mesh['faces'], g['origin'], g['res'], g['shape'], d, f)
+    want = ref.box_sdf(ref.centres_f64(g['origin'], g['res'], g['shape'])).reshape(g['shape'])
+    assert np.isfinite(s).all() and not (want == 0).any()
+    assert int(((s >= 0) != (want >= 0)).sum()) == 0
+    assert 5000 < (s < 0).sum() < 8000  # 6 292 of 32 768 centres lie inside
+    assert np.abs(s - want).max() <= 2 * 2.869e-7  # measured 2.869e-7 (corners: three roundings of the box's vertices)
+
+
+def test_sign_by_pseudonormals_on_the_icosphere():
+    mesh = ref.icosphere()
+    origin, res, shape = np.array([-1.3, -1.4, -1.2]), 0.08, (32, 32, 32)
+    d, f = ref.distance_field(mesh['vertices'], mesh['faces'], origin, res, shape, 10.0)
+    s = ref.signed_distance(mesh['vertices'], mesh['faces'], origin, res, shape, d, f)
+    P = ref.centres_f64(origin, res, shape)
+    # float64 truth for a convex solid: inside <=> behind every face's plane
+    V = mesh['vertices'].astype(np.float64)[mesh['faces']]
+    n = np.cross(V[:, 1] - V[:, 0], V[:, 2] - V[:, 0])
+    n /= np.linalg.norm(n, axis=1)[:, None]
+    plane = ((P[:, None, :] - V[None, :, 0]) * n[None]).sum(-1).max(axis=1).reshape(shape)
+    assert not (plane == 0).any()
+    assert int(((s >= 0) != (plane > 0)).sum()) == 0 and 4000 < (s < 0).sum() < 5000
+    y = ref.distance_f64(P, mesh['vertices'], mesh['faces']).reshape(shape)
+    assert np.abs(np.abs(s) - y).max() <= 2 * 1.692e-7  # measured 1.692e-7
+
+
+def test_the_sign_is_for_closed_meshes_only():
+    """The documented limit: the room with inward walls plus its three solids, which share faces with the walls, is a union
+    of overlapping closed pieces, not one closed mesh - pseudonormals get 495 of the 16 200 in-room voxel centres wrong
+    (measured; every one of them within reach of a solid's side that lies in a wall).  Such scenes take their sign from views."""
+    mesh = raster_ref.room_mesh()
+    faces = mesh['faces'].copy()
+    faces[:12] = faces[:12][:, ::-1]  # the walls wound so that free space is outside
+    origin, res = ref.room32_spec()
+    shape = ref.ROOM32['shape']
+    d, f = ref.distance_field(mesh['vertices'], faces, origin, res, shape, 10.0)
+    s = ref.signed_distance(mesh['vertices'], faces, origin, res, shape, d, f)
+    P = ref.centres_f64(origin, res, shape)
+    inside = ((P > synthetic.ROOM_MIN) & (P < synthetic.ROOM_MAX)).all(axis=1).reshape(shape)
+    sdf = synthetic.scene_sdf(P).reshape(shape)
+    wrong = ((s >= 0) != (sdf >= 0)) & inside
+    print('room as a union of closed pieces: {} of {} in-room voxels get the wrong sign'.format(int(wrong.sum()), int(inside.sum())))
+    assert 100 < wrong.sum() < 1000  # not a few stray ties, and not the whole room: a real, local failure
+    # each solid on its own is a closed mesh, and its sign is right everywhere
+    for k in range(1, 4):
+        one = mesh['faces'][12 * k:12 * (k + 1)]
+        d1, f1 = ref.distance_field(mesh['vertices'], one, origin, res, shape, 10.0)
+        s1 = ref.signed_distance(mesh['vertices'], one, origin, res, shape, d1, f1)
+        lo, hi = synthetic._SOLIDS[k - 1]
+        want = ref.box_sdf(P, lo, hi).reshape(shape)
+        assert not ((s1 >= 0) != (want >= 0))[want != 0].any()
+
+
+def test_pseudonormals_of_a_closed_mesh():
+    from online_joint_depthfusion_and_semantic_amd.mesh_distance import pseudonormals
+    mesh = ref.closed_box()
+    vn, en, fe = pseudonormals(mesh['vertices'], mesh['faces'])
+    assert vn.dtype == F and en.dtype == F and fe.dtype == np.int32 and en.shape == (18, 3) and fe.shape == (12, 3)
+    assert (np.bincount(fe.ravel(), minlength=18) == 2).all()  # closed: every edge has two faces
+    centre = 0.5 * (np.asarray(ref.BOX_LO) + np.asarray(ref.BOX_HI))
+    out = mesh['vertices'].astype(np.float64) - centre
+    assert ((vn * out).sum(axis=1) > 0).all()  # outward at every corner
+    # a corner of a box: three right angles' worth of normals, each pi/2 - whichever way its sides are cut
+    assert np.allclose(np.abs(vn), np.pi / 2, atol=1e-5)
+
+
+def test_degenerate_input():
+    m = raster_ref.edge_cases()
+    cases = raster_ref.EDGE_FACES
+    origin, res, shape = np.array([0.4, -3.4, -2.2]), 0.25, (28, 20, 28)
+    d, f = ref.cached_field('edge', m, origin, res, shape, 0.6)
+    y = ref.distance_f64(ref.centres_f64(origin, res, shape), m['vertices'], m['faces']).reshape(shape)
+    hit = np.isfinite(d)
+    # (coordinates up to 6.5 m: 1e-6 m is 2.5 ulp of fp32 there, the error of a handful of roundings; measured 2.3e-7)
+    assert np.abs(d[hit] - y[hit]).max() <= 1e-6
+    won = set(np.unique(f[hit]).tolist())
+    assert cases['zero_area'][0] in won  # a zero-area face is its edges
+    for skipped in cases['out_of_range'] + cases['nan_vertex']:
+        assert skipped not in won
+    assert cases['duplicate'][0] in won and cases['duplicate'][1] not in won  # the lower index wins
+    # the zero-area face alone: the distance to its segment
+    zf = m['faces'][cases['zero_area'][0]]
+    a, b = m['vertices'][zf[0]].astype(np.float64), m['vertices'][zf[2]].astype(np.float64)
+    d1, f1 = ref.distance_field(m['vertices'], zf[None], origin, res, shape, 0.6)
+    P = ref.centres_f64(origin, res, shape)
+    t = np.clip(((P - a) * (b - a)).sum(1) / ((b - a) ** 2).sum(), 0, 1)
+    seg = np.linalg.norm(P - (a + t[:, None] * (b - a)), axis=1).reshape(shape)
+    assert np.isfinite(d1).sum() > 20 and np.abs(d1[np.isfinite(d1)] - seg[np.isfinite(d1)]).max() <= 1e-6
+    # nothing but skipped faces: nothing anywhere
+    bad = m['faces'][list(cases['out_of_range'] + cases['nan_vertex'])]
+    d2, f2 = ref.distance_field(m['vertices'], bad, origin, res, shape, 100.0)
+    assert np.isinf(d2).all() and (f2 == -1).all()
