@@ -8,13 +8,10 @@ The reference has no counterpart.
 The volume frame is the one extract, integrate, render and projective use (voxel (i,j,k) centred at origin + (i+0.5, j+0.5,
 k+0.5)·res).  Packing a float image into bytes is host-side plumbing and not part of the definition.
 """
-import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, views
 from .ops import _origin_array
-from .projective import _cameras, _images
-from .render import _poses
 
 
 def new_volume(shape, device):
@@ -69,39 +66,20 @@ def integrate_color(colors, *, origin, resolution, image, depth, intrinsics, ext
     ``_lib.COLOR_MAX_VIEWS`` go in several kernel calls, with the same bits as one view per call."""
     _lib.require_gpu()
     lib = _lib.load()
-    X, Y, Z = _volume(colors, 'integrate_color')
+    who = 'integrate_color'
+    X, Y, Z = _volume(colors, who)
     dev = colors.device
-    if not (torch.is_tensor(depth) and depth.device == dev and depth.dim() in (2, 3)):
-        raise ValueError('integrate_color: depth must be a [h,w] or [n,h,w] tensor on the volume\'s device')
-    depth = depth.to(torch.float32)
-    if depth.dim() == 2:
-        depth = depth.unsqueeze(0)
-    depth = depth.contiguous()
+    depth = views.depth_frames(who, depth, dev)
     n, h, w = depth.shape
-    if n < 1:
-        raise ValueError('integrate_color: no depth map')
-    band, max_weight, near = float(band), float(max_weight), float(near)
-    if not (0.0 < band < float('inf')) or not (1.0 <= max_weight <= 2048.0) or not (0.0 <= near < float('inf')):
-        raise ValueError('integrate_color: band > 0, 1 <= max_weight <= 2048 and near >= 0 expected, got {}, {}, {}'.format(
-            band, max_weight, near))
-    try:
-        K, E = _cameras(intrinsics, extrinsics, n)
-        mask = _images(mask, 'mask', torch.uint8, n, h, w, dev)
-    except ValueError as err:
-        raise ValueError(str(err).replace('integrate_depth', 'integrate_color')) from None
-    if not (np.isfinite(K).all() and np.isfinite(E).all()):
-        raise ValueError('integrate_color: non-finite intrinsics or extrinsics')
-    if np.any(K[:, [1, 3, 6, 7]] != 0.0) or np.any(K[:, 8] != 1.0):
-        raise ValueError('integrate_color: pinhole intrinsics [fx 0 cx; 0 fy cy; 0 0 1] expected')
+    band, max_weight, near = views.running_mean_options(who, 'band', band, max_weight, near)
+    n, K, E = views.cameras(who, intrinsics, extrinsics, n)
+    mask = views.images(who, mask, 'mask', torch.uint8, n, h, w, dev)
     image = pack_image(image, n, h, w, dev)
     org = _origin_array(origin)
     stream = _lib.stream_ptr(dev)
-    step = _lib.COLOR_MAX_VIEWS
-    for v0 in range(0, n, step):
-        v1 = min(n, v0 + step)
-        Kc, Ec = np.ascontiguousarray(K[v0:v1]), np.ascontiguousarray(E[v0:v1])
+    for v0, v1, Kc, Ec in views.chunks(n, _lib.COLOR_MAX_VIEWS, K, E):
         rc = lib.ojf_fuse_color(_lib.ptr(colors), X, Y, Z, org.ctypes.data, float(resolution), v1 - v0, Kc.ctypes.data,
-                                Ec.ctypes.data, _lib.ptr(depth[v0:v1]), _lib.ptr(None if mask is None else mask[v0:v1]),
+                                Ec.ctypes.data, _lib.ptr(depth[v0:v1]), _lib.ptr(views.part(mask, v0, v1)),
                                 _lib.ptr(image[v0:v1]), h, w, band, max_weight, near, stream)
         _lib.check(rc, 'ojf_fuse_color')
 
@@ -132,27 +110,17 @@ def render_color(colors, *, origin, resolution, intrinsics, extrinsics, depth):
     without depth (0, negative, non-finite) and points with nothing coloured near them are 0, alpha included."""
     _lib.require_gpu()
     lib = _lib.load()
-    X, Y, Z = _volume(colors, 'render_color')
+    who = 'render_color'
+    X, Y, Z = _volume(colors, who)
     dev = colors.device
-    if not (torch.is_tensor(depth) and depth.device == dev and depth.dim() in (2, 3)):
-        raise ValueError('render_color: depth must be a [h,w] or [n,h,w] tensor on the volume\'s device')
-    depth = depth.to(torch.float32)
-    if depth.dim() == 2:
-        depth = depth.unsqueeze(0)
-    depth = depth.contiguous()
-    try:
-        n, Ki, E = _poses(intrinsics, extrinsics)
-    except ValueError as err:
-        raise ValueError(str(err).replace('render:', 'render_color:')) from None
-    if n != depth.shape[0] or n < 1:
+    depth = views.depth_frames(who, depth, dev)
+    n, Ki, E = views.inverse_cameras(who, intrinsics, extrinsics)
+    if n != depth.shape[0]:
         raise ValueError('render_color: {} poses for {} depth images'.format(n, depth.shape[0]))
     h, w = depth.shape[1:]
     org = _origin_array(origin)
     out = torch.empty((n, h, w, 4), dtype=torch.uint8, device=dev)
-    step = _lib.RENDER_MAX_VIEWS
-    for v0 in range(0, n, step):
-        v1 = min(n, v0 + step)
-        Kc, Ec = np.ascontiguousarray(Ki[v0:v1]), np.ascontiguousarray(E[v0:v1])
+    for v0, v1, Kc, Ec in views.chunks(n, _lib.RENDER_MAX_VIEWS, Ki, E):
         rc = lib.ojf_color_render(_lib.ptr(colors), X, Y, Z, org.ctypes.data, float(resolution), v1 - v0, Kc.ctypes.data,
                                   Ec.ctypes.data, _lib.ptr(depth[v0:v1]), h, w, _lib.ptr(out[v0:v1]), _lib.stream_ptr(dev))
         _lib.check(rc, 'ojf_color_render')

@@ -42,6 +42,7 @@
 // Read-out: one lane per output, every output written once; the 8 corners are 8-byte loads (2-byte loads for a volume
 // off the 8-byte grid).
 #include "ojf_projview.h"
+#include "ojf_renderview.h"
 
 namespace ojf {
 
@@ -200,26 +201,20 @@ __global__ __launch_bounds__(kColorBlock) void color_sample_kernel(ColorVolume C
     rgba[i] = sample_color(C, g);
 }
 
-struct ColorRenderView {  // ojf_render's view
-    float Ki[9];
-    float R[9];  // E[:, :3], row-major
-    float o[3];  // fp32((E[:,3] - origin) / res)
-};
-
 struct ColorRenderLaunch {
     ColorVolume C;
     const float *depth;  // of the launch's first view
     uint32_t *rgba;
     int h, w;
     float res;
-    ColorRenderView v[kColorRenderViewsPerLaunch];
+    RenderView v[kColorRenderViewsPerLaunch];
 };
 
 __global__ __launch_bounds__(kColorBlock) void color_render_kernel(ColorRenderLaunch L)
 {
     const uint32_t i = blockIdx.x * kColorBlock + threadIdx.x;  // pixel of view blockIdx.y
     if (i >= (uint32_t)(L.h * L.w)) return;
-    const ColorRenderView &V = L.v[blockIdx.y];
+    const RenderView &V = L.v[blockIdx.y];
     const size_t pix = (size_t)blockIdx.y * (size_t)(L.h * L.w) + i;
     const float t = L.depth[pix];
     uint32_t out = 0;
@@ -240,13 +235,6 @@ __global__ __launch_bounds__(kColorBlock) void color_render_kernel(ColorRenderLa
     L.rgba[pix] = out;
 }
 
-static int check_color_volume(const char *who, int X, int Y, int Z)
-{
-    if (X <= 0 || Y <= 0 || Z <= 0) return refuse(who, "non-positive volume size");
-    if ((int64_t)X * Y * Z > 0x7fffffffLL) return refuse(who, "volume too large");
-    return 0;
-}
-
 }  // namespace ojf
 
 OJF_API int ojf_fuse_color(uint16_t *color, int X, int Y, int Z, const double *origin, double res, int n, const double *K,
@@ -262,15 +250,14 @@ OJF_API int ojf_fuse_color(uint16_t *color, int X, int Y, int Z, const double *o
     ColorLaunch L;
     ColorArgs &A = L.a;
     A.color = color;
-    A.im.depth = depth; A.im.mask = mask; A.im.h = h; A.im.w = w; A.im.near = near;
-    A.im.cmax = (float)(w - 1); A.im.rmax = (float)(h - 1);
+    fill_proj_images(A.im, depth, mask, h, w, near);
     A.image = reinterpret_cast<const uint32_t *>(image);
     A.total = (uint32_t)((int64_t)X * Y * Z);
     A.groups = (A.total + kColorGroup - 1) / kColorGroup;
     A.Y = Y; A.Z = Z; A.n = n;
     A.vec = ((uintptr_t)color & 15) == 0;  // anything else goes element by element
     A.band = band; A.max_weight = max_weight;
-    for (int v = 0; v < n; ++v) make_proj_view(K + 9 * v, E + 12 * v, origin, res, L.v[v]);
+    make_proj_views(K, E, origin, res, n, L.v);
     const uint32_t blocks = (A.groups + kColorBlock - 1) / kColorBlock;
     hipLaunchKernelGGL(color_kernel, dim3(blocks), dim3(kColorBlock), 0, as_stream(stream), L);
     OJF_HIP(hipGetLastError());
@@ -283,7 +270,7 @@ OJF_API int ojf_color_sample(const uint16_t *color, int X, int Y, int Z, const f
     using namespace ojf;
     const char *who = "ojf_color_sample";
     if (!color || !points || !rgba) return refuse(who, "null pointer argument");
-    if (int rc = check_color_volume(who, X, Y, Z)) return rc;
+    if (int rc = check_volume_size(who, X, Y, Z)) return rc;
     if (n < 1 || n > 0x7fffffffULL) return refuse(who, "n must be 1..2^31-1 points");
     if (((uintptr_t)color & 1) || ((uintptr_t)points & 3) || ((uintptr_t)rgba & 3))
         return refuse(who, "color_dev must be 2-byte, points_dev and rgba_dev 4-byte aligned");
@@ -303,7 +290,7 @@ OJF_API int ojf_color_render(const uint16_t *color, int X, int Y, int Z, const d
     const char *who = "ojf_color_render";
     if (!color || !origin || !Kinv || !E || !depth || !rgba) return refuse(who, "null pointer argument");
     if (n < 1 || n > OJF_RENDER_MAX_VIEWS) return refuse(who, "n must be 1..OJF_RENDER_MAX_VIEWS views");
-    if (int rc = check_color_volume(who, X, Y, Z)) return rc;
+    if (int rc = check_volume_size(who, X, Y, Z)) return rc;
     if (h <= 0 || w <= 0) return refuse(who, "non-positive image size");
     if ((int64_t)n * h * w > 0x7fffffffLL) return refuse(who, "images too large");
     bool finite = all_finite(origin, 3) && std::isfinite(res);
@@ -321,15 +308,7 @@ OJF_API int ojf_color_render(const uint16_t *color, int X, int Y, int Z, const d
         const int nv = n - v0 < kColorRenderViewsPerLaunch ? n - v0 : kColorRenderViewsPerLaunch;
         L.depth = depth + (size_t)v0 * h * w;
         L.rgba = reinterpret_cast<uint32_t *>(rgba) + (size_t)v0 * h * w;
-        for (int j = 0; j < nv; ++j) {
-            ColorRenderView &V = L.v[j];
-            const float *Kj = Kinv + 9 * (v0 + j), *Ej = E + 12 * (v0 + j);
-            for (int i = 0; i < 9; ++i) V.Ki[i] = Kj[i];
-            for (int i = 0; i < 3; ++i) {
-                for (int k = 0; k < 3; ++k) V.R[3 * i + k] = Ej[4 * i + k];
-                V.o[i] = (float)(((double)Ej[4 * i + 3] - origin[i]) / res);
-            }
-        }
+        for (int j = 0; j < nv; ++j) make_render_view(Kinv + 9 * (v0 + j), E + 12 * (v0 + j), origin, res, L.v[j]);
         hipLaunchKernelGGL(color_render_kernel, dim3(blocks, nv), dim3(kColorBlock), 0, as_stream(stream), L);
         OJF_HIP(hipGetLastError());
     }

@@ -175,13 +175,12 @@ OJF_API int ojf_fuse_label_probs(uint16_t *vol, int n_classes, int X, int Y, int
     LabelLaunch L;
     LabelArgs &A = L.a;
     A.vol = vol;
-    A.im.depth = depth; A.im.mask = mask; A.im.h = h; A.im.w = w; A.im.near = near;
-    A.im.cmax = (float)(w - 1); A.im.rmax = (float)(h - 1);
+    fill_proj_images(A.im, depth, mask, h, w, near);
     A.probs = probs; A.labels = labels;
     A.total = (uint32_t)((int64_t)X * Y * Z);
     A.Y = Y; A.Z = Z; A.n = n; A.C = n_classes; A.S = 8 * ((n_classes + 8) / 8); A.prob_stride = prob_stride;
     A.band = band; A.max_weight = max_weight;
-    for (int v = 0; v < n; ++v) make_proj_view(K + 9 * v, E + 12 * v, origin, res, L.v[v]);
+    make_proj_views(K, E, origin, res, n, L.v);
     const uint32_t blocks = (A.total + kLabelBlock - 1) / kLabelBlock;
     if (probs) hipLaunchKernelGGL(label_fuse_kernel<true>, dim3(blocks), dim3(kLabelBlock), 0, as_stream(stream), L);
     else hipLaunchKernelGGL(label_fuse_kernel<false>, dim3(blocks), dim3(kLabelBlock), 0, as_stream(stream), L);
@@ -196,8 +195,7 @@ OJF_API int ojf_label_decide(const uint16_t *vol, int n_classes, int X, int Y, i
     const char *who = "ojf_label_decide";
     if (!vol || !ids || !scores) return refuse(who, "null pointer argument");
     if (int rc = check_label_volume(who, vol, n_classes)) return rc;
-    if (X <= 0 || Y <= 0 || Z <= 0) return refuse(who, "non-positive volume size");
-    if ((int64_t)X * Y * Z > 0x7fffffffLL) return refuse(who, "volume too large");
+    if (int rc = check_volume_size(who, X, Y, Z)) return rc;
     if ((uintptr_t)scores & 1) return refuse(who, "scores_dev must be 2-byte aligned");
     DecideArgs A;
     A.vol = vol; A.ids = ids; A.scores = scores;

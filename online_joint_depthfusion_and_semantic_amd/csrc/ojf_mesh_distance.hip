@@ -542,8 +542,7 @@ static int check_mesh_box(const char *who, const float *vertices, int nv, const 
     if (!vertices || !faces || !origin) return refuse(who, "null pointer argument");
     if (nv < 1 || nf < 1) return refuse(who, "non-positive mesh size (nv, nf)");
     if ((int64_t)nf * 3 > 0x7fffffffLL || (int64_t)nv * 3 > 0x7fffffffLL) return refuse(who, "mesh too large");
-    if (X <= 0 || Y <= 0 || Z <= 0) return refuse(who, "non-positive volume size");
-    if ((int64_t)X * Y * Z > 0x7fffffffLL) return refuse(who, "volume too large");
+    if (int rc = check_volume_size(who, X, Y, Z)) return rc;
     if (!all_finite(origin, 3) || !std::isfinite(res)) return refuse(who, "non-finite origin or resolution");
     if (!(res > 0.0)) return refuse(who, "resolution must be > 0");
     if (((uintptr_t)vertices & 3) || ((uintptr_t)faces & 3)) return refuse(who, "vertices_dev and faces_dev must be 4-byte aligned");

@@ -206,15 +206,15 @@ OJF_API int ojf_fuse_projective(uint16_t *tsdf, uint16_t *wgt, uint8_t *ids, uin
     ProjLaunch L;
     ProjArgs &A = L.a;
     A.tsdf = tsdf; A.wgt = wgt; A.ids = ids; A.scores = scores;
-    A.im.depth = depth; A.im.mask = mask; A.labels = labels; A.lscores = lscores;
+    fill_proj_images(A.im, depth, mask, h, w, near);
+    A.labels = labels; A.lscores = lscores;
     A.total = (uint32_t)((int64_t)X * Y * Z);
     A.groups = (A.total + kProjGroup - 1) / kProjGroup;
-    A.Y = Y; A.Z = Z; A.im.h = h; A.im.w = w; A.n = n; A.carve = carve;
+    A.Y = Y; A.Z = Z; A.n = n; A.carve = carve;
     // the wide accesses need 16-byte aligned fp16 volumes and an 8-byte aligned id volume; anything else goes element by element
     A.vec = (((uintptr_t)tsdf | (uintptr_t)wgt | (uintptr_t)scores) & 15) == 0 && ((uintptr_t)ids & 7) == 0;
-    A.trunc = trunc; A.max_weight = max_weight; A.im.near = near;
-    A.im.cmax = (float)(w - 1); A.im.rmax = (float)(h - 1);
-    for (int v = 0; v < n; ++v) make_proj_view(K + 9 * v, E + 12 * v, origin, res, L.v[v]);
+    A.trunc = trunc; A.max_weight = max_weight;
+    make_proj_views(K, E, origin, res, n, L.v);
     const uint32_t blocks = (A.groups + kProjBlock - 1) / kProjBlock;
     hipLaunchKernelGGL(projective_kernel, dim3(blocks), dim3(kProjBlock), 0, as_stream(stream), L);
     OJF_HIP(hipGetLastError());

@@ -1,7 +1,8 @@
-// What the voxel-projective sweeps (ojf_projective.hip, ojf_color.hip) share: the per-view constants the host prepares in
-// f64 and steps 1-3 of the definition in ojf_projective.hip's header - voxel -> camera point -> nearest pixel -> depth
-// and mask tests.  One text for both kernels, so that colour lands in exactly the voxels the depth of the same frame
-// reaches.  The operation order is normative (see there); nothing here may be re-associated.
+// What the voxel-projective sweeps (ojf_projective.hip, ojf_color.hip, ojf_labels.hip) share: the per-view constants the
+// host prepares in f64 and steps 1-3 of the definition in ojf_projective.hip's header - voxel -> camera point -> nearest
+// pixel -> depth and mask tests.  One text for all kernels, so that colour and label votes land in exactly the voxels the
+// depth of the same frame reaches.  The operation order is normative (see there); nothing here may be re-associated.
+// The host checks at the end are also what the other volume operators ask of a box (check_volume_size, all_finite).
 #pragma once
 #include "ojf_common.h"
 
@@ -78,14 +79,21 @@ static inline bool all_finite(const double *p, int n)
     return true;
 }
 
-// What both entry points ask of their volume, images and cameras; 0 or fail("<who>: ...").
+// What every entry point asks of an [X,Y,Z] box: positive sizes and a voxel count a 31-bit index reaches; 0 or refuse(who, ...).
+static inline int check_volume_size(const char *who, int X, int Y, int Z)
+{
+    if (X <= 0 || Y <= 0 || Z <= 0) return refuse(who, "non-positive volume size");
+    if ((int64_t)X * Y * Z > 0x7fffffffLL) return refuse(who, "volume too large");
+    return 0;
+}
+
+// What the sweeps' entry points ask of their volume, images and cameras; 0 or refuse(who, ...).
 static inline int check_projective_views(const char *who, int X, int Y, int Z, const double *origin, double res, int n,
                                          int max_views, const double *K, const double *E, int h, int w, float max_weight,
                                          float near)
 {
     if (n < 1 || n > max_views) return refuse(who, "n must be 1..MAX_VIEWS views");
-    if (X <= 0 || Y <= 0 || Z <= 0) return refuse(who, "non-positive volume size");
-    if ((int64_t)X * Y * Z > 0x7fffffffLL) return refuse(who, "volume too large");
+    if (int rc = check_volume_size(who, X, Y, Z)) return rc;
     if (h <= 0 || w <= 0) return refuse(who, "non-positive image size");
     if ((int64_t)n * h * w > 0x7fffffffLL || h > (1 << 24) || w > (1 << 24)) return refuse(who, "images too large");
     if (!(max_weight >= 1.0f && max_weight <= 2048.0f)) return refuse(who, "max_weight must be in 1..2048");
@@ -111,6 +119,17 @@ static inline void make_proj_view(const double *Kv, const double *Ev, const doub
         V.b[a] = (float)((Ev[a] * gm[0] + Ev[4 + a] * gm[1]) + Ev[8 + a] * gm[2]);
     }
     V.fx = (float)Kv[0]; V.fy = (float)Kv[4]; V.cx = (float)Kv[2]; V.cy = (float)Kv[5];
+}
+
+static inline void make_proj_views(const double *K, const double *E, const double *origin, double res, int n, ProjView *V)
+{
+    for (int v = 0; v < n; ++v) make_proj_view(K + 9 * v, E + 12 * v, origin, res, V[v]);
+}
+
+static inline void fill_proj_images(ProjImages &I, const float *depth, const uint8_t *mask, int h, int w, float near)
+{
+    I.depth = depth; I.mask = mask; I.h = h; I.w = w; I.near = near;
+    I.cmax = (float)(w - 1); I.rmax = (float)(h - 1);
 }
 
 }  // namespace ojf

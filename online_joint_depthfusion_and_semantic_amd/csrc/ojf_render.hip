@@ -34,7 +34,7 @@
 // z-contiguous volume), four tiles per block, blockIdx.y = view.  Blocks banded over the XCDs like extract.  The march
 // loop is divergent per lane and ends for the wave when its last lane is done.  No LDS, no atomics, every output written
 // once: the same bits on every run and for every n.
-#include "ojf_common.h"
+#include "ojf_renderview.h"
 
 #include <math.h>
 
@@ -42,12 +42,6 @@ namespace ojf {
 
 constexpr int kRenderTilesPerBlock = 4;
 constexpr int kRenderViewsPerLaunch = 32;  // keeps the by-value views well inside the kernel-argument segment
-
-struct RenderView {
-    float Ki[9];
-    float R[9];  // E[:, :3], row-major
-    float o[3];  // fp32((E[:,3] - origin) / res)
-};
 
 struct RenderArgs {
     const uint16_t *tsdf;
@@ -262,15 +256,7 @@ OJF_API int ojf_render(const uint16_t *tsdf, const uint16_t *wgt, const uint8_t 
     for (int v0 = 0; v0 < n; v0 += kRenderViewsPerLaunch) {
         const int nv = n - v0 < kRenderViewsPerLaunch ? n - v0 : kRenderViewsPerLaunch;
         A.view0 = v0;
-        for (int j = 0; j < nv; ++j) {
-            RenderView &V = L.v[j];
-            const float *Kj = Kinv + 9 * (v0 + j), *Ej = E + 12 * (v0 + j);
-            for (int i = 0; i < 9; ++i) V.Ki[i] = Kj[i];
-            for (int i = 0; i < 3; ++i) {
-                for (int k = 0; k < 3; ++k) V.R[3 * i + k] = Ej[4 * i + k];
-                V.o[i] = (float)(((double)Ej[4 * i + 3] - origin[i]) / res);
-            }
-        }
+        for (int j = 0; j < nv; ++j) make_render_view(Kinv + 9 * (v0 + j), E + 12 * (v0 + j), origin, res, L.v[j]);
         hipLaunchKernelGGL(render_kernel, dim3((blocks + 7) / 8 * 8, nv), dim3(64 * kRenderTilesPerBlock), 0, as_stream(stream), L);
         OJF_HIP(hipGetLastError());
     }

@@ -335,8 +335,8 @@ static int check_resample(const char *who, int sX, int sY, int sZ, int dX, int d
                           float max_weight, ResampleMap &P)
 {
     if (!M || !c) return refuse(who, "null pointer argument");
-    if (sX <= 0 || sY <= 0 || sZ <= 0 || dX <= 0 || dY <= 0 || dZ <= 0) return refuse(who, "non-positive volume size");
-    if ((int64_t)sX * sY * sZ > 0x7fffffffLL || (int64_t)dX * dY * dZ > 0x7fffffffLL) return refuse(who, "volume too large");
+    if (int rc = check_volume_size(who, sX, sY, sZ)) return rc;
+    if (int rc = check_volume_size(who, dX, dY, dZ)) return rc;
     if (mode != OJF_RESAMPLE_REPLACE && mode != OJF_RESAMPLE_MERGE) return refuse(who, "unknown mode");
     if (!all_finite(M, 9) || !all_finite(c, 3)) return refuse(who, "non-finite M or c");
     for (int i = 0; i < 9; ++i) P.M[i] = (float)M[i];

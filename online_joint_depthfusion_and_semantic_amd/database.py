@@ -8,6 +8,7 @@ Pipeline mutates them in place.  ``to_numpy()`` moves the state to the host exac
 reference's (database.py:383-393), after which ``filter`` / ``evaluate`` run on numpy arrays;
 while the state is on the device they run as HIP kernels (ojf_volume_*).
 """
+import contextlib
 import os
 
 import numpy as np
@@ -38,6 +39,10 @@ class Voxelgrid:
 
 def _is_dev(v):
     return torch.is_tensor(v) and v.is_cuda
+
+
+def _to_dev(x, device):
+    return None if x is None else torch.as_tensor(x).to(device)
 
 
 class Database(torch.utils.data.Dataset):
@@ -274,6 +279,23 @@ class Database(torch.utils.data.Dataset):
             vol = torch.from_numpy(np.ascontiguousarray(vol))
         return vol.to(device='cuda', dtype=dtype).contiguous()
 
+    def _resident(self, scene_id, who, *volumes, optional=()):
+        """Refuse host state: ``volumes``, and those of ``optional`` that exist, must be on the device."""
+        if not all(_is_dev(v) for v in volumes + tuple(v for v in optional if v is not None)):
+            raise ValueError('Database.{}: the volumes of {!r} are not resident on the device (to_torch())'.format(who, scene_id))
+
+    @staticmethod
+    @contextlib.contextmanager
+    def _side_volume(store, scene_id, make):
+        """A scene's side volume in ``store`` (colors, label_probs) for the call in the ``with`` body: the stored one, or
+        ``make()`` on first use, which is kept only if the body went through - a refused call leaves a scene without a side
+        volume without one."""
+        vol = store.get(scene_id)
+        if vol is None:
+            vol = make()
+        yield vol  # (a refusal in the body leaves from here)
+        store[scene_id] = vol
+
     def _color_volume(self, scene_id, who):
         if self.colors.get(scene_id) is None:
             raise ValueError('Database.{}: scene {!r} has no colour volume (integrate_color)'.format(who, scene_id))
@@ -339,13 +361,10 @@ class Database(torch.utils.data.Dataset):
         ``projective.integrate_depth`` (truncation - default: the initial value -, max_weight, near, carve)."""
         from . import projective
         tsdf, w = self.scenes_est[scene_id].volume, self.fusion_weights[scene_id]
-        if not (_is_dev(tsdf) and _is_dev(w)):
-            raise ValueError('Database.integrate_depth: the volumes of {!r} are not resident on the device (to_torch())'.format(scene_id))
+        self._resident(scene_id, 'integrate_depth', tsdf, w)
         kw.setdefault('truncation', self.initial_value)
         sem = bool(self.semantics) and labels is not None
-
-        def dev(x):
-            return None if x is None else torch.as_tensor(x).to(tsdf.device)
+        dev = lambda x: _to_dev(x, tsdf.device)  # noqa: E731
         projective.integrate_depth(tsdf, w, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]),
                                    depth=dev(depth), intrinsics=intrinsics, extrinsics=extrinsics, mask=dev(mask),
                                    ids=self.ids_est[scene_id].volume if sem else None,
@@ -360,17 +379,12 @@ class Database(torch.utils.data.Dataset):
         max_weight, near).  Geometry and labels are not touched."""
         from . import color
         tsdf = self.scenes_est[scene_id].volume
-        if not _is_dev(tsdf) or not (self.colors.get(scene_id) is None or _is_dev(self.colors[scene_id])):
-            raise ValueError('Database.integrate_color: the volumes of {!r} are not resident on the device (to_torch())'.format(scene_id))
+        self._resident(scene_id, 'integrate_color', tsdf, optional=(self.colors.get(scene_id),))
         kw.setdefault('band', self.initial_value)
-        fresh = self.colors.get(scene_id) is None
-        vol = color.new_volume(tsdf.shape, tsdf.device) if fresh else self.colors[scene_id]
-
-        def dev(x):
-            return None if x is None else torch.as_tensor(x).to(tsdf.device)
-        color.integrate_color(vol, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]), image=dev(image),
-                              depth=dev(depth), intrinsics=intrinsics, extrinsics=extrinsics, mask=dev(mask), **kw)
-        self.colors[scene_id] = vol  # (a refused call leaves a scene without a colour volume without one)
+        dev = lambda x: _to_dev(x, tsdf.device)  # noqa: E731
+        with self._side_volume(self.colors, scene_id, lambda: color.new_volume(tsdf.shape, tsdf.device)) as vol:
+            color.integrate_color(vol, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]), image=dev(image),
+                                  depth=dev(depth), intrinsics=intrinsics, extrinsics=extrinsics, mask=dev(mask), **kw)
 
     def integrate_label_probs(self, scene_id, depth, intrinsics, extrinsics, mask=None, probs=None, labels=None, **kw):
         """Fuse the label observations of one or more frames into the scene's class-distribution volume (label_probs.py;
@@ -382,18 +396,13 @@ class Database(torch.utils.data.Dataset):
         if not self.semantics:
             raise ValueError('Database.integrate_label_probs: the database has no semantics (n_classes)')
         tsdf = self.scenes_est[scene_id].volume
-        if not _is_dev(tsdf) or not (self.label_probs.get(scene_id) is None or _is_dev(self.label_probs[scene_id])):
-            raise ValueError('Database.integrate_label_probs: the volumes of {!r} are not resident on the device (to_torch())'.format(scene_id))
+        self._resident(scene_id, 'integrate_label_probs', tsdf, optional=(self.label_probs.get(scene_id),))
         kw.setdefault('band', self.initial_value)
-        fresh = self.label_probs.get(scene_id) is None
-        vol = label_probs.new_volume(tsdf.shape, self.n_classes, tsdf.device) if fresh else self.label_probs[scene_id]
-
-        def dev(x):
-            return None if x is None else torch.as_tensor(x).to(tsdf.device)
-        label_probs.integrate_label_probs(vol, self.n_classes, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]),
-                                          depth=dev(depth), intrinsics=intrinsics, extrinsics=extrinsics, mask=dev(mask),
-                                          probs=dev(probs), labels=dev(labels), **kw)
-        self.label_probs[scene_id] = vol  # (a refused call leaves a scene without a volume without one)
+        dev = lambda x: _to_dev(x, tsdf.device)  # noqa: E731
+        with self._side_volume(self.label_probs, scene_id, lambda: label_probs.new_volume(tsdf.shape, self.n_classes, tsdf.device)) as vol:
+            label_probs.integrate_label_probs(vol, self.n_classes, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]),
+                                              depth=dev(depth), intrinsics=intrinsics, extrinsics=extrinsics, mask=dev(mask),
+                                              probs=dev(probs), labels=dev(labels), **kw)
 
     def decide_labels(self, scene_id=None):
         """Write the decision of the class-distribution volumes - of one scene, or of every scene that has one - into ids_est /
@@ -406,8 +415,7 @@ class Database(torch.utils.data.Dataset):
             if vol is None:
                 raise ValueError('Database.decide_labels: scene {!r} has no class-distribution volume (integrate_label_probs)'.format(s))
             ids, scores = self.ids_est[s].volume, self.scores[s].volume
-            if not (_is_dev(vol) and _is_dev(ids) and _is_dev(scores)):
-                raise ValueError('Database.decide_labels: the volumes of {!r} are not resident on the device (to_torch())'.format(s))
+            self._resident(s, 'decide_labels', vol, ids, scores)
             label_probs.decide_labels(vol, self.n_classes, ids, scores)
 
     # ---- the box: re-box, resample, merge (resample.py) ------------------------------------------------------
@@ -420,8 +428,7 @@ class Database(torch.utils.data.Dataset):
             vols['colors'] = self.colors[scene_id]
         if self.label_probs.get(scene_id) is not None:
             vols.update(label_probs=self.label_probs[scene_id], n_classes=self.n_classes)
-        if not all(_is_dev(v) for k, v in vols.items() if k != 'n_classes'):
-            raise ValueError('Database.{}: the volumes of {!r} are not resident on the device (to_torch())'.format(who, scene_id))
+        self._resident(scene_id, who, *(v for k, v in vols.items() if k != 'n_classes'))
         return vols
 
     def _origin64(self, scene_id):
@@ -439,8 +446,7 @@ class Database(torch.utils.data.Dataset):
         est = self._estimated_volumes(scene_id, 'resample')
         gt = self.scenes_gt[scene_id].volume
         ids_gt = self.ids_gt[scene_id].volume if self.semantics and self.semantic_grid else None
-        if not _is_dev(gt) or not (ids_gt is None or _is_dev(ids_gt)):
-            raise ValueError('Database.resample: the volumes of {!r} are not resident on the device (to_torch())'.format(scene_id))
+        self._resident(scene_id, 'resample', gt, optional=(ids_gt,))
         if gt.dtype != torch.float16:
             raise ValueError('Database.resample: the ground-truth volume of {!r} must be fp16, got {}'.format(scene_id, gt.dtype))
         old_origin, old_res = self._origin64(scene_id), float(self.resolution[scene_id])

@@ -9,12 +9,10 @@ counterpart.
 The volume frame is the one extract, integrate, render, projective and color use.  A record is S = 8·ceil((C+1)/8) halves:
 the C class means, the weight W (channel C; 0: nothing fused), and padding that no kernel touches.
 """
-import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, views
 from .ops import _origin_array
-from .projective import _cameras, _images
 
 
 def record_size(n_classes):
@@ -59,31 +57,14 @@ def integrate_label_probs(volume, n_classes, *, origin, resolution, depth, intri
     dev = volume.device
     if (probs is None) == (labels is None):
         raise ValueError('{}: exactly one of probs and labels must be given'.format(who))
-    if not (torch.is_tensor(depth) and depth.device == dev and depth.dim() in (2, 3)):
-        raise ValueError('{}: depth must be a [h,w] or [n,h,w] tensor on the volume\'s device'.format(who))
-    depth = depth.to(torch.float32)
-    if depth.dim() == 2:
-        depth = depth.unsqueeze(0)
-    depth = depth.contiguous()
+    depth = views.depth_frames(who, depth, dev)
     n, h, w = depth.shape
-    if n < 1:
-        raise ValueError('{}: no depth map'.format(who))
-    band, max_weight, near = float(band), float(max_weight), float(near)
-    if not (0.0 < band < float('inf')) or not (1.0 <= max_weight <= 2048.0) or not (0.0 <= near < float('inf')):
-        raise ValueError('{}: band > 0, 1 <= max_weight <= 2048 and near >= 0 expected, got {}, {}, {}'.format(
-            who, band, max_weight, near))
-    try:
-        K, E = _cameras(intrinsics, extrinsics, n)
-        mask = _images(mask, 'mask', torch.uint8, n, h, w, dev)
-        if labels is not None and torch.is_tensor(labels) and labels.dtype != torch.uint8:
-            raise ValueError('{}: labels must be u8, got {}'.format(who, labels.dtype))
-        labels = _images(labels, 'labels', torch.uint8, n, h, w, dev)
-    except ValueError as err:
-        raise ValueError(str(err).replace('integrate_depth', who)) from None
-    if not (np.isfinite(K).all() and np.isfinite(E).all()):
-        raise ValueError('{}: non-finite intrinsics or extrinsics'.format(who))
-    if np.any(K[:, [1, 3, 6, 7]] != 0.0) or np.any(K[:, 8] != 1.0):
-        raise ValueError('{}: pinhole intrinsics [fx 0 cx; 0 fy cy; 0 0 1] expected'.format(who))
+    band, max_weight, near = views.running_mean_options(who, 'band', band, max_weight, near)
+    n, K, E = views.cameras(who, intrinsics, extrinsics, n)
+    mask = views.images(who, mask, 'mask', torch.uint8, n, h, w, dev)
+    if labels is not None and torch.is_tensor(labels) and labels.dtype != torch.uint8:
+        raise ValueError('{}: labels must be u8, got {}'.format(who, labels.dtype))
+    labels = views.images(who, labels, 'labels', torch.uint8, n, h, w, dev)
     stride = 0
     if probs is not None:
         if not (torch.is_tensor(probs) and probs.device == dev and probs.is_floating_point() and probs.dim() in (3, 4)):
@@ -97,14 +78,11 @@ def integrate_label_probs(volume, n_classes, *, origin, resolution, depth, intri
         stride = probs.shape[3]
     org = _origin_array(origin)
     stream = _lib.stream_ptr(dev)
-    step = _lib.LABEL_MAX_VIEWS
-    for v0 in range(0, n, step):
-        v1 = min(n, v0 + step)
-        Kc, Ec = np.ascontiguousarray(K[v0:v1]), np.ascontiguousarray(E[v0:v1])
-        part = lambda t: None if t is None else t[v0:v1]  # noqa: E731  (leading-axis slices of contiguous images are contiguous)
+    for v0, v1, Kc, Ec in views.chunks(n, _lib.LABEL_MAX_VIEWS, K, E):
         rc = lib.ojf_fuse_label_probs(_lib.ptr(volume), C, X, Y, Z, org.ctypes.data, float(resolution), v1 - v0, Kc.ctypes.data,
-                                      Ec.ctypes.data, _lib.ptr(part(depth)), _lib.ptr(part(mask)), _lib.ptr(part(probs)), stride,
-                                      _lib.ptr(part(labels)), h, w, band, max_weight, near, stream)
+                                      Ec.ctypes.data, _lib.ptr(depth[v0:v1]), _lib.ptr(views.part(mask, v0, v1)),
+                                      _lib.ptr(views.part(probs, v0, v1)), stride, _lib.ptr(views.part(labels, v0, v1)), h, w,
+                                      band, max_weight, near, stream)
         _lib.check(rc, 'ojf_fuse_label_probs')
 
 
@@ -115,10 +93,8 @@ def decide_labels(volume, n_classes, ids, scores):
     X, Y, Z = _volume(volume, n_classes, who)
     _lib.require_gpu()
     lib = _lib.load()
-    for vol, dt, name in ((ids, torch.uint8, 'ids'), (scores, torch.float16, 'scores')):
-        if not (torch.is_tensor(vol) and vol.device == volume.device and vol.dtype == dt and tuple(vol.shape) == (X, Y, Z)
-                and vol.is_contiguous()):
-            raise ValueError('{}: {} must be a contiguous {} tensor of the volume\'s [X,Y,Z] and device'.format(who, name, dt))
+    views.volume3(who, ids, 'ids', torch.uint8, (X, Y, Z), volume.device)
+    views.volume3(who, scores, 'scores', torch.float16, (X, Y, Z), volume.device)
     rc = lib.ojf_label_decide(_lib.ptr(volume), int(n_classes), X, Y, Z, _lib.ptr(ids), _lib.ptr(scores),
                               _lib.stream_ptr(volume.device))
     _lib.check(rc, 'ojf_label_decide')

@@ -751,22 +751,18 @@ class Pipeline(torch.nn.Module):
                 return
             scene_id = run_key[0]
             volume = database[scene_id]
+            # (frame, mask, K, E, sem_ids, scores, image) per frame: every stack of the run is made once and serves all three calls
+            depth, mask, K, E = (torch.stack([r[i] for r in run]) for i in range(4))
+            labels, label_scores = (torch.stack([r[i] for r in run]) for i in (4, 5)) if sem else (None, None)
             projective.integrate_depth(
                 volume['current'], volume['weights'], origin=volume['origin'], resolution=float(volume['resolution']),
-                depth=torch.stack([r[0] for r in run]), mask=torch.stack([r[1] for r in run]),
-                intrinsics=torch.stack([r[2] for r in run]), extrinsics=torch.stack([r[3] for r in run]),
-                ids=volume['ids_est'] if sem else None, scores=volume['scores'] if sem else None,
-                labels=torch.stack([r[4] for r in run]) if sem else None,
-                label_scores=torch.stack([r[5] for r in run]) if sem else None, **kw)
+                depth=depth, mask=mask, intrinsics=K, extrinsics=E, ids=volume['ids_est'] if sem else None,
+                scores=volume['scores'] if sem else None, labels=labels, label_scores=label_scores, **kw)
             self._commit_frame(database, scene_id, volume)
             if color_kw is not None:
-                database.integrate_color(scene_id, torch.cat([r[6] for r in run]), torch.stack([r[0] for r in run]),
-                                         torch.stack([r[2] for r in run]), torch.stack([r[3] for r in run]),
-                                         mask=torch.stack([r[1] for r in run]), **color_kw)
+                database.integrate_color(scene_id, torch.cat([r[6] for r in run]), depth, K, E, mask=mask, **color_kw)
             if label_kw is not None:
-                database.integrate_label_probs(scene_id, torch.stack([r[0] for r in run]), torch.stack([r[2] for r in run]),
-                                               torch.stack([r[3] for r in run]), mask=torch.stack([r[1] for r in run]),
-                                               labels=torch.stack([r[4] for r in run]), **label_kw)
+                database.integrate_label_probs(scene_id, depth, K, E, mask=mask, labels=labels, **label_kw)
             del run[:]
 
         for b, s in zip(batches, sems):

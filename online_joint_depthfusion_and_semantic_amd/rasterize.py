@@ -12,9 +12,9 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, views
 from .ops import _origin_array
-from .projective import _cameras, integrate_depth
+from .projective import integrate_depth
 
 
 def _mesh(vertices, faces, who):
@@ -63,18 +63,10 @@ def rasterize(vertices, faces, intrinsics, extrinsics, shape, near=0., face_labe
     h, w = int(shape[0]), int(shape[1])
     if h < 1 or w < 1:
         raise ValueError('{}: shape must be (h, w) with h, w >= 1'.format(who))
-    E = torch.as_tensor(extrinsics)
-    n = 1 if E.dim() == 2 else int(E.shape[0])
-    if n < 1:
-        raise ValueError('{}: no view'.format(who))
     near = float(near)
     if not (0.0 <= near < float('inf')):
         raise ValueError('{}: near >= 0 and finite expected, got {}'.format(who, near))
-    K, E = _cameras(intrinsics, extrinsics, n)
-    if not (np.isfinite(K).all() and np.isfinite(E).all()):
-        raise ValueError('{}: non-finite intrinsics or extrinsics'.format(who))
-    if np.any(K[:, [1, 3, 6, 7]] != 0.0) or np.any(K[:, 8] != 1.0) or np.any(K[:, [0, 4]] == 0.0):
-        raise ValueError('{}: pinhole intrinsics [fx 0 cx; 0 fy cy; 0 0 1] expected'.format(who))
+    n, K, E = views.cameras(who, intrinsics, extrinsics, nonzero_focal=True)
     face_labels = _attribute(face_labels, nf, None, 'face_labels', who, dev)
     vertex_colors = _attribute(vertex_colors, nv, 4, 'vertex_colors', who, dev)
     out = {'depth': torch.empty((n, h, w), dtype=torch.float32, device=dev),
@@ -86,9 +78,7 @@ def rasterize(vertices, faces, intrinsics, extrinsics, shape, near=0., face_labe
     step = _lib.RASTER_MAX_VIEWS
     keys = torch.empty((min(n, step), h, w), dtype=torch.int64, device=dev)
     stream = _lib.stream_ptr(dev)
-    for v0 in range(0, n, step):
-        v1 = min(n, v0 + step)
-        Kc, Ec = np.ascontiguousarray(K[v0:v1]), np.ascontiguousarray(E[v0:v1])
+    for v0, v1, Kc, Ec in views.chunks(n, step, K, E):
         rc = lib.ojf_rasterize(_lib.ptr(vertices), nv, _lib.ptr(faces), nf, v1 - v0, Kc.ctypes.data, Ec.ctypes.data, h, w, near,
                                _lib.ptr(keys), _lib.ptr(out['depth'][v0:v1]), _lib.ptr(out['face'][v0:v1]), stream)
         _lib.check(rc, 'ojf_rasterize')
@@ -128,18 +118,16 @@ class MeshStream:
         self.scene, self.scenes = scene, [scene]
         self.input_key = input_key
         self.near = near
+        self._batches = list(views.chunks(len(P), _lib.RASTER_MAX_VIEWS, self.K, self.poses))  # (v0, v1, K, poses) per batch
         self._cache = {}  # first frame of a batch -> host images of the batch
 
     def __len__(self):
         return len(self.poses)
 
     def _images(self, i):
-        step = _lib.RASTER_MAX_VIEWS
-        v0 = (i // step) * step
+        v0, _, K, poses = self._batches[i // _lib.RASTER_MAX_VIEWS]
         if v0 not in self._cache:
-            v1 = min(len(self), v0 + step)
-            out = rasterize(self.vertices, self.faces, self.K[v0:v1], self.poses[v0:v1], (self.h, self.w), self.near,
-                            self.face_labels, self.vertex_colors)
+            out = rasterize(self.vertices, self.faces, K, poses, (self.h, self.w), self.near, self.face_labels, self.vertex_colors)
             self._cache[v0] = {k: v.cpu().numpy() for k, v in out.items()}
         return {k: v[i - v0] for k, v in self._cache[v0].items()}
 
@@ -194,15 +182,15 @@ def ground_truth_grid(vertices, faces, *, origin, resolution, shape, truncation,
     dev = vertices.device
     truncation = float(truncation)
     X, Y, Z = (int(s) for s in shape)
-    views = rasterize(vertices, faces, intrinsics, extrinsics, image_shape, near, face_labels)
+    frames = rasterize(vertices, faces, intrinsics, extrinsics, image_shape, near, face_labels)
     tsdf = torch.full((X, Y, Z), truncation, dtype=torch.float16, device=dev)
     weights = torch.zeros((X, Y, Z), dtype=torch.float16, device=dev)
     sem = face_labels is not None
     ids = torch.zeros((X, Y, Z), dtype=torch.uint8, device=dev)
     scores = torch.zeros((X, Y, Z), dtype=torch.float16, device=dev) if sem else None
-    integrate_depth(tsdf, weights, origin=_origin_array(origin), resolution=float(resolution), depth=views['depth'],
+    integrate_depth(tsdf, weights, origin=_origin_array(origin), resolution=float(resolution), depth=frames['depth'],
                     intrinsics=intrinsics, extrinsics=extrinsics, ids=ids if sem else None, scores=scores,
-                    labels=views['labels'] if sem else None, truncation=truncation, max_weight=max_weight, near=near, carve=True)
+                    labels=frames['labels'] if sem else None, truncation=truncation, max_weight=max_weight, near=near, carve=True)
     unseen = weights == 0
     tsdf.masked_fill_(unseen, -truncation)
     ids.masked_fill_(unseen, 0)

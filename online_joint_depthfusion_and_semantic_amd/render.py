@@ -6,32 +6,15 @@ The volume frame is the one extract and integrate use (voxel (i,j,k) centred at 
 not the mesh frame of ``Database.get_mesh``.  The returned depth is the camera z-depth, 0 where the ray hits nothing -
 the same convention as the input depth maps.
 """
-import numpy as np
 import torch
 
-from . import _lib
-from .ops import camera_arrays, _origin_array
+from . import _lib, views
+from .ops import _origin_array
 
 
 def _poses(intrinsics, extrinsics):
-    """(n, Kinv f32[n,9], E f32[n,12]) from [3,3] / [n,3,3] intrinsics and [3,4] / [4,4] / [n,3,4] / [n,4,4]
-    extrinsics (numpy or torch, any float type); a single intrinsics matrix serves every pose."""
-    K = torch.as_tensor(intrinsics).detach().cpu()
-    E = torch.as_tensor(extrinsics).detach().cpu()
-    if K.dim() == 2:
-        K = K.unsqueeze(0)
-    if E.dim() == 2:
-        E = E.unsqueeze(0)
-    if K.shape[-2:] != (3, 3) or E.shape[-1] != 4 or E.shape[-2] not in (3, 4):
-        raise ValueError('render: intrinsics [n,]3x3 and extrinsics [n,]3x4 or 4x4 expected, got {} and {}'.format(
-            tuple(K.shape), tuple(E.shape)))
-    n = max(K.shape[0], E.shape[0])
-    if K.shape[0] not in (1, n) or E.shape[0] not in (1, n):
-        raise ValueError('render: {} intrinsics for {} poses'.format(K.shape[0], E.shape[0]))
-    Ki, Ew = np.empty((n, 9), np.float32), np.empty((n, 12), np.float32)
-    for i in range(n):
-        Ki[i], Ew[i] = camera_arrays(K[i if K.shape[0] > 1 else 0], E[i if E.shape[0] > 1 else 0])
-    return n, Ki, Ew
+    """``views.inverse_cameras`` under the name the test helpers of earlier revisions import (their render_ref.cameras)."""
+    return views.inverse_cameras('render', intrinsics, extrinsics)
 
 
 def render_views(tsdf, weights=None, ids=None, *, origin, resolution, intrinsics, extrinsics, shape, near=0.0,
@@ -46,16 +29,13 @@ def render_views(tsdf, weights=None, ids=None, *, origin, resolution, intrinsics
     the leading n kept for a single view too."""
     _lib.require_gpu()
     lib = _lib.load()
-    if not (torch.is_tensor(tsdf) and tsdf.is_cuda and tsdf.dtype == torch.float16 and tsdf.dim() == 3):
-        raise ValueError('render_views: tsdf must be a cuda fp16 [X,Y,Z] tensor')
-    tsdf = tsdf.contiguous()
-    for vol, dt, name in ((weights, torch.float16, 'weights'), (ids, torch.uint8, 'ids')):
-        if vol is not None and not (torch.is_tensor(vol) and vol.device == tsdf.device and vol.dtype == dt
-                                    and vol.shape == tsdf.shape):
-            raise ValueError('render_views: {} must be a {} tensor of the volume\'s shape and device'.format(name, dt))
-    weights = None if weights is None else weights.contiguous()
-    ids = None if ids is None else ids.contiguous()
-    n, Ki, E = _poses(intrinsics, extrinsics)
+    who = 'render_views'
+    tsdf = views.volume3(who, tsdf, 'tsdf', torch.float16, copy=True)
+    if weights is not None:
+        weights = views.volume3(who, weights, 'weights', torch.float16, tsdf.shape, tsdf.device, copy=True)
+    if ids is not None:
+        ids = views.volume3(who, ids, 'ids', torch.uint8, tsdf.shape, tsdf.device, copy=True)
+    n, Ki, E = views.inverse_cameras(who, intrinsics, extrinsics)
     if n > _lib.RENDER_MAX_VIEWS:
         raise ValueError('render_views: at most {} views per call'.format(_lib.RENDER_MAX_VIEWS))
     h, w = int(shape[0]), int(shape[1])

@@ -9,8 +9,8 @@ f32 = np.float32
 def cameras(intrinsics, extrinsics, origin, resolution):
     """(Kinv f32[n,9], E f32[n,12], o f32[n,3]) the way render.py / ojf_render prepare them."""
     import torch
-    from online_joint_depthfusion_and_semantic_amd.render import _poses
-    _, Ki, E = _poses(intrinsics, extrinsics)
+    from online_joint_depthfusion_and_semantic_amd.views import inverse_cameras
+    _, Ki, E = inverse_cameras('render_ref', intrinsics, extrinsics)
     org = np.asarray(origin.numpy() if torch.is_tensor(origin) else origin, dtype=np.float64).reshape(3)
     o = ((E[:, 3::4].astype(np.float64) - org) / float(resolution)).astype(f32)
     return Ki, E, o

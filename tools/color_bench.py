@@ -23,14 +23,14 @@ import torch  # noqa: E402
 from online_joint_depthfusion_and_semantic_amd import synthetic  # noqa: E402
 from online_joint_depthfusion_and_semantic_amd import _lib  # noqa: E402
 from online_joint_depthfusion_and_semantic_amd.color import new_volume, pack_image  # noqa: E402
-from online_joint_depthfusion_and_semantic_amd.projective import _cameras  # noqa: E402
+from online_joint_depthfusion_and_semantic_amd.views import cameras  # noqa: E402
 
 
 def raw_calls(tsdf, wgt, colors, origin, res, K, E, depth, mask, image, band):
     """(ojf_fuse_projective, ojf_fuse_color) closures with the cameras and images prepared once."""
     lib = _lib.load()
     n, h, w = depth.shape
-    Kh, Eh = _cameras(K, E, n)
+    _, Kh, Eh = cameras('color_bench', K, E, n)
     org = np.ascontiguousarray(np.asarray(origin, dtype=np.float64))
     st = _lib.stream_ptr(tsdf.device)
     pargs = (_lib.ptr(tsdf), _lib.ptr(wgt), None, None, *tsdf.shape, org.ctypes.data, float(res), n, Kh.ctypes.data, Eh.ctypes.data,

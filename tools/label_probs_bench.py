@@ -25,7 +25,7 @@ import torch  # noqa: E402
 from online_joint_depthfusion_and_semantic_amd import synthetic  # noqa: E402
 from online_joint_depthfusion_and_semantic_amd import _lib  # noqa: E402
 from online_joint_depthfusion_and_semantic_amd import color, label_probs  # noqa: E402
-from online_joint_depthfusion_and_semantic_amd.projective import _cameras  # noqa: E402
+from online_joint_depthfusion_and_semantic_amd.views import cameras  # noqa: E402
 
 
 def raw_calls(colors, vol_l, vol_p, C, shape, origin, res, K, E, depth, mask, image, labels, probs, band):
@@ -33,7 +33,7 @@ def raw_calls(colors, vol_l, vol_p, C, shape, origin, res, K, E, depth, mask, im
     and images prepared once."""
     lib = _lib.load()
     n, h, w = depth.shape
-    Kh, Eh = _cameras(K, E, n)
+    _, Kh, Eh = cameras('label_probs_bench', K, E, n)
     org = np.ascontiguousarray(np.asarray(origin, dtype=np.float64))
     st = _lib.stream_ptr(colors.device)
     cargs = (_lib.ptr(colors), *shape, org.ctypes.data, float(res), n, Kh.ctypes.data, Eh.ctypes.data, _lib.ptr(depth),

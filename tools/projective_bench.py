@@ -21,14 +21,15 @@ import torch  # noqa: E402
 
 from online_joint_depthfusion_and_semantic_amd import synthetic  # noqa: E402
 from online_joint_depthfusion_and_semantic_amd import _lib  # noqa: E402
-from online_joint_depthfusion_and_semantic_amd.projective import _cameras, integrate_depth  # noqa: E402
+from online_joint_depthfusion_and_semantic_amd.projective import integrate_depth  # noqa: E402
+from online_joint_depthfusion_and_semantic_amd.views import cameras  # noqa: E402
 
 
 def raw_call(tsdf, wgt, origin, res, K, E, depth, mask, trunc, carve):
     """ojf_fuse_projective with the cameras and images prepared once: the kernel without integrate_depth's host work."""
     lib = _lib.load()
     n, h, w = depth.shape
-    Kh, Eh = _cameras(K, E, n)
+    _, Kh, Eh = cameras('projective_bench', K, E, n)
     org = np.ascontiguousarray(np.asarray(origin, dtype=np.float64))
     args = (_lib.ptr(tsdf), _lib.ptr(wgt), None, None, *tsdf.shape, org.ctypes.data, float(res), n, Kh.ctypes.data, Eh.ctypes.data,
             _lib.ptr(depth), _lib.ptr(mask), None, None, h, w, float(trunc), 128.0, 0.0, int(carve), _lib.stream_ptr(tsdf.device))

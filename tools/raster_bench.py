@@ -22,8 +22,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from online_joint_depthfusion_and_semantic_amd import _lib, mesh, synthetic  # noqa: E402
-from online_joint_depthfusion_and_semantic_amd.projective import _cameras  # noqa: E402
-from online_joint_depthfusion_and_semantic_amd.render import _poses  # noqa: E402
+from online_joint_depthfusion_and_semantic_amd.views import cameras, inverse_cameras  # noqa: E402
 
 
 def box_room():
@@ -83,8 +82,8 @@ def main():
             K = synthetic.intrinsics(h, w)
             for n in (1, 8):
                 E = np.stack([synthetic.camera_pose(2.0 * np.pi * i / 8) for i in range(n)])
-                Kh, Eh = _cameras(K, E, n)
-                _, Ki, Ef = _poses(K, E)
+                _, Kh, Eh = cameras('raster_bench', K, E, n)
+                _, Ki, Ef = inverse_cameras('raster_bench', K, E)
                 keys = torch.empty((n, h, w), dtype=torch.int64, device=dev)
                 depth = torch.empty((n, h, w), dtype=torch.float32, device=dev)
                 face = torch.empty((n, h, w), dtype=torch.int32, device=dev)

@@ -22,13 +22,14 @@ import torch  # noqa: E402
 
 from online_joint_depthfusion_and_semantic_amd import synthetic  # noqa: E402
 from online_joint_depthfusion_and_semantic_amd import _lib  # noqa: E402
-from online_joint_depthfusion_and_semantic_amd.render import _poses, render_views  # noqa: E402
+from online_joint_depthfusion_and_semantic_amd.render import render_views  # noqa: E402
+from online_joint_depthfusion_and_semantic_amd.views import inverse_cameras  # noqa: E402
 
 
 def raw_call(tsdf, wgt, ids, origin, res, K, E, h, w):
     """ojf_render with the cameras prepared and the outputs allocated once: the kernel without render_views' host work."""
     lib = _lib.load()
-    n, Ki, Ew = _poses(K, E)
+    n, Ki, Ew = inverse_cameras('render_bench', K, E)
     org = np.ascontiguousarray(np.asarray(origin, dtype=np.float64))
     depth = torch.empty((n, h, w), dtype=torch.float32, device=tsdf.device)
     nrm = torch.empty((n, h, w, 3), dtype=torch.float32, device=tsdf.device)
