@@ -824,6 +824,45 @@ int ojf_resample_records(const uint16_t *src_dev /* fp16 [sX,sY,sZ,S] */, int sX
                          const double *M_host /* f64[9] */, const double *c_host /* f64[3] */, int mode, float max_weight,
                          ojf_stream_t stream);
 
+/* ---- CONNECTED COMPONENTS (floater removal, 3-D instances; no counterpart in the reference) ----------------------------
+ * ojf_volume_components: the connected components of the foreground of an [X,Y,Z] volume (linear index v = (x Y + y) Z + z).
+ *   mask_dev u8 (NULL: every voxel) - foreground where the byte is non-zero; keys_dev u8 (NULL: all equal) - neighbouring
+ *   foreground voxels are joined only when their key bytes are equal; connectivity 6 (faces) or 26 (the 3x3x3 neighbourhood).
+ *   labels_dev i32[X,Y,Z]: -1 on the background, else the smallest linear index of the voxel's component (its root).
+ *   The list, in ascending order of root, n entries: roots_dev i32, sizes_dev i32 (voxels), list_keys_dev u8 (the key byte at
+ *   the root, 0 without keys), boxes_dev i32[6] = (x0, y0, z0, x1, y1, z1), inclusive.  ids_dev i32[X,Y,Z]: -1 on the
+ *   background, else the rank 0..n-1 of the voxel's component in the list.  *count_dev = n.  Everything is a function of the
+ *   input alone - integer atomics only, and the root is a minimum: the same bits on every run.
+ *   phases: OJF_COMPONENTS_ALL, or a subset run in the order brick (union-find per 4 x 4 x 64 brick in LDS), seam (unions
+ *   across brick faces, edges and corners with agent-scope atomics only; no thread waits for another workgroup), flatten
+ *   (labels), rank (ids, *count_dev), list (the list arrays) on the outputs and the workspace that earlier calls with the same
+ *   arguments left.  n is not known in advance: call with capacity = 0 (the list arrays may be NULL; the list phase does
+ *   not run and nothing is written to them) to get labels, ids and n, then with phases = OJF_COMPONENTS_LIST and arrays of
+ *   capacity >= n entries; a single call with enough capacity does both.  Entries beyond capacity are dropped.
+ *   workspace_dev: ojf_volume_components_workspace_bytes(X, Y, Z) bytes, 8-byte aligned (4 bytes per voxel and a little).
+ * ojf_volume_observed_mask: mask_dev[v] = 1 where fp32(weights[v]) > 0 and tsdf[v] is not a NaN (the mesh extractor's
+ *   observed voxel: a NaN, negative or -0 weight is unobserved) and, with use_band != 0, |fp32(tsdf[v])| < band; else 0.
+ * ojf_volume_components_apply: where ids_dev[v] is in [0, n_components) and keep_dev[ids_dev[v]] == 0: tsdf = init_value,
+ *   weights = 0 - what ojf_volume_filter writes.  Every other voxel is not written at all.
+ * All launches go on the caller's stream and never wait.  Bad arguments (null required pointers, non-positive sizes,
+ *   X*Y*Z >= 2^31, a connectivity other than 6 and 26, unknown phases, a workspace that is too small, alignment, a band that
+ *   is not > 0) are refused before any HIP call.  The kernels are described in csrc/ojf_components.hip. */
+#define OJF_COMPONENTS_BRICK 1
+#define OJF_COMPONENTS_SEAM 2
+#define OJF_COMPONENTS_FLATTEN 4
+#define OJF_COMPONENTS_RANK 8
+#define OJF_COMPONENTS_LIST 16
+#define OJF_COMPONENTS_ALL 31
+size_t ojf_volume_components_workspace_bytes(int X, int Y, int Z);
+int ojf_volume_components(const uint8_t *mask_dev /* or NULL */, const uint8_t *keys_dev /* or NULL */, int X, int Y, int Z,
+                          int connectivity, int phases, void *workspace_dev, size_t workspace_bytes, int32_t *labels_dev,
+                          int32_t *ids_dev, int32_t *roots_dev, int32_t *sizes_dev, uint8_t *list_keys_dev,
+                          int32_t *boxes_dev /* i32[capacity][6] */, uint32_t capacity, uint32_t *count_dev, ojf_stream_t stream);
+int ojf_volume_observed_mask(const uint16_t *tsdf_dev, const uint16_t *weights_dev, size_t n, int use_band, float band,
+                             uint8_t *mask_dev, ojf_stream_t stream);
+int ojf_volume_components_apply(const int32_t *ids_dev, const uint8_t *keep_dev, uint32_t n_components, uint16_t *tsdf_dev,
+                                uint16_t *weights_dev, size_t n, float init_value, ojf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

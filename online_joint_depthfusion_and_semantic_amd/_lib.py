@@ -52,6 +52,7 @@ RASTER_MAX_VIEWS = 32  # include/ojf.h OJF_RASTER_MAX_VIEWS
 LABEL_MAX_VIEWS = 32  # include/ojf.h OJF_LABEL_MAX_VIEWS
 RESAMPLE_REPLACE, RESAMPLE_MERGE = 0, 1  # include/ojf.h OJF_RESAMPLE_REPLACE / OJF_RESAMPLE_MERGE
 MESH_DISTANCE_BIN, MESH_DISTANCE_SCAN, MESH_DISTANCE_FILL, MESH_DISTANCE_GATHER, MESH_DISTANCE_ALL = 1, 2, 4, 8, 15  # OJF_MESH_DISTANCE_*
+COMPONENTS_BRICK, COMPONENTS_SEAM, COMPONENTS_FLATTEN, COMPONENTS_RANK, COMPONENTS_LIST, COMPONENTS_ALL = 1, 2, 4, 8, 16, 31  # OJF_COMPONENTS_*
 
 
 class ExtractJob(ctypes.Structure):
@@ -197,6 +198,14 @@ SIGNATURES = {
     'ojf_resample_volumes': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _f, _i, _f, _vp]),
     # source records, sX, sY, sZ, destination records, dX, dY, dZ, S, Cw, M, c, mode, max_weight, stream
     'ojf_resample_records': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _f, _vp]),
+    'ojf_volume_components_workspace_bytes': (_sz, [_i, _i, _i]),
+    # mask, keys, X, Y, Z, connectivity, phases, workspace, workspace_bytes, labels, ids, roots, sizes, list keys, boxes, capacity,
+    # count, stream
+    'ojf_volume_components': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_uint32, _vp, _vp]),
+    # tsdf, weights, n, use_band, band, mask, stream
+    'ojf_volume_observed_mask': (_i, [_vp, _vp, _sz, _i, _f, _vp, _vp]),
+    # ids, keep, n_components, tsdf, weights, n, init_value, stream
+    'ojf_volume_components_apply': (_i, [_vp, _vp, _c.c_uint32, _vp, _vp, _sz, _f, _vp]),
 }
 
 _LIB = None

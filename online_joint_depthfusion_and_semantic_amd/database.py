@@ -222,6 +222,30 @@ class Database(torch.utils.data.Dataset):
                 res = median_filter(host, size=value)
                 self.ids_est[s].volume = torch.from_numpy(res).to(v.device) if torch.is_tensor(v) else res
 
+    def filter_components(self, min_voxels=None, keep_largest=None, connectivity=26, band=None):
+        """Floater filter (components.remove_small_components; no counterpart in the reference): in every scene, the connected
+        components of the observed voxels (within ``band`` of the surface, if given) that are smaller than ``min_voxels`` - or
+        all but the ``keep_largest`` largest - go back to the initial value and weight 0, as ``filter`` leaves a voxel.  Touches
+        the same two volumes as ``filter``; host state is refused.  Returns {scene: the component list with the keep flags}."""
+        from . import components
+        components.keep_flags([], [], min_voxels, keep_largest, 'Database.filter_components')
+        for s in self.scenes:
+            self._resident(s, 'filter_components', self.scenes_est[s].volume, self.fusion_weights[s])
+        return {s: components.remove_small_components(self.scenes_est[s].volume, self.fusion_weights[s], init_value=self.initial_value,
+                                                      min_voxels=min_voxels, keep_largest=keep_largest, connectivity=connectivity, band=band)
+                for s in self.scenes}
+
+    def instances(self, scene_id, connectivity=6, min_voxels=1):
+        """3-D instances of a scene (components.instances): the connected components of equal labels of ids_est among the
+        observed voxels.  Returns {'ids' i32 [X,Y,Z] on the device (-1: no instance), 'n', 'roots', 'sizes', 'classes',
+        'boxes'}; components of fewer than ``min_voxels`` voxels are dropped and the rest renumbered densely in root order."""
+        from . import components
+        if not self.semantics:
+            raise ValueError('Database.instances: the database has no semantics (ids_est)')
+        tsdf, w, ids = self.scenes_est[scene_id].volume, self.fusion_weights[scene_id], self.ids_est[scene_id].volume
+        self._resident(scene_id, 'instances', tsdf, w, ids)
+        return components.instances(ids, tsdf, w, connectivity=connectivity, min_voxels=min_voxels)
+
     def evaluate(self, mode='train', workspace=None):
         """database.py:265-309 (note: averages over ALL scenes, untouched ones included, :304)."""
         results, per_scene = {}, {}
