@@ -863,6 +863,37 @@ int ojf_volume_observed_mask(const uint16_t *tsdf_dev, const uint16_t *weights_d
 int ojf_volume_components_apply(const int32_t *ids_dev, const uint8_t *keep_dev, uint32_t n_components, uint16_t *tsdf_dev,
                                 uint16_t *weights_dev, size_t n, float init_value, ojf_stream_t stream);
 
+/* ---- DISTANCE TRANSFORM (exact Euclidean distance and nearest seed of every voxel; surface voxels and ESDF of a fused TSDF) ----
+ * Volumes are [X,Y,Z], linear index v = (x Y + y) Z + z, 1 <= X, Y, Z <= 2048 and X*Y*Z < 2^31.
+ * ojf_volume_edt: seeds_dev u8 - a voxel is a seed where the byte is non-zero.  dist2_dev i32[X,Y,Z]: the minimum over the
+ *   seeds q of |p - q|^2 in voxel units; nearest_dev i32[X,Y,Z]: the smallest linear index among the seeds that attain it -
+ *   the pair is the minimum of the 64-bit key (d^2 << 32) | index(q), a function of the input alone.  With no seed in reach
+ *   dist2 = OJF_EDT_NONE and nearest = -1.  max_dist2 (negative: unlimited): a voxel with d^2 > max_dist2 gets NONE / -1, every
+ *   other voxel is unchanged from the unlimited result; no pass then looks further than sqrt(max_dist2) along its axis.
+ *   phases: OJF_EDT_ALL, or a subset run in the order z, y, x on the outputs and the workspace that earlier calls with the
+ *   same arguments left (each is a 1-D pass along its axis; ties go to the smaller coordinate).
+ *   workspace_dev: ojf_volume_edt_workspace_bytes(X, Y, Z) bytes, 8-byte aligned (4 bytes per voxel).
+ * ojf_volume_surface_mask: mask_dev[v] = 1 where v is observed as ojf_volume_observed_mask defines it without a band and has
+ *   an observed face neighbour on the other side of the surface (inside: fp32(tsdf) < 0; -0.0 and +0.0 are outside); else 0.
+ * ojf_volume_esdf: esdf_dev[v] = s (fp32(resolution) sqrtf((float)dist2[v])), each operation correctly rounded, s = -1 where
+ *   v is observed and inside, else +1; where dist2[v] is OJF_EDT_NONE, s far (far >= 0, +inf allowed).
+ * All launches go on the caller's stream and never wait.  Bad arguments (null pointers, a dimension out of range, unknown
+ *   phases, a workspace that is too small, alignment, a resolution that is not > 0 and finite, a far that is not >= 0) are
+ *   refused before any kernel is launched and leave every output untouched.  The kernels are described in
+ *   csrc/ojf_distance.hip. */
+#define OJF_EDT_Z 1
+#define OJF_EDT_Y 2
+#define OJF_EDT_X 4
+#define OJF_EDT_ALL 7
+#define OJF_EDT_NONE 0x7fffffff
+size_t ojf_volume_edt_workspace_bytes(int X, int Y, int Z);
+int ojf_volume_edt(const uint8_t *seeds_dev, int X, int Y, int Z, int max_dist2, int phases, void *workspace_dev,
+                   size_t workspace_bytes, int32_t *dist2_dev, int32_t *nearest_dev, ojf_stream_t stream);
+int ojf_volume_surface_mask(const uint16_t *tsdf_dev, const uint16_t *weights_dev, int X, int Y, int Z, uint8_t *mask_dev,
+                            ojf_stream_t stream);
+int ojf_volume_esdf(const int32_t *dist2_dev, const uint16_t *tsdf_dev, const uint16_t *weights_dev, size_t n, float resolution,
+                    float far, float *esdf_dev, ojf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,7 @@ LABEL_MAX_VIEWS = 32  # include/ojf.h OJF_LABEL_MAX_VIEWS
 RESAMPLE_REPLACE, RESAMPLE_MERGE = 0, 1  # include/ojf.h OJF_RESAMPLE_REPLACE / OJF_RESAMPLE_MERGE
 MESH_DISTANCE_BIN, MESH_DISTANCE_SCAN, MESH_DISTANCE_FILL, MESH_DISTANCE_GATHER, MESH_DISTANCE_ALL = 1, 2, 4, 8, 15  # OJF_MESH_DISTANCE_*
 COMPONENTS_BRICK, COMPONENTS_SEAM, COMPONENTS_FLATTEN, COMPONENTS_RANK, COMPONENTS_LIST, COMPONENTS_ALL = 1, 2, 4, 8, 16, 31  # OJF_COMPONENTS_*
+EDT_Z, EDT_Y, EDT_X, EDT_ALL, EDT_NONE = 1, 2, 4, 7, 2 ** 31 - 1  # OJF_EDT_*
 
 
 class ExtractJob(ctypes.Structure):
@@ -206,6 +207,13 @@ SIGNATURES = {
     'ojf_volume_observed_mask': (_i, [_vp, _vp, _sz, _i, _f, _vp, _vp]),
     # ids, keep, n_components, tsdf, weights, n, init_value, stream
     'ojf_volume_components_apply': (_i, [_vp, _vp, _c.c_uint32, _vp, _vp, _sz, _f, _vp]),
+    'ojf_volume_edt_workspace_bytes': (_sz, [_i, _i, _i]),
+    # seeds, X, Y, Z, max_dist2, phases, workspace, workspace_bytes, dist2, nearest, stream
+    'ojf_volume_edt': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
+    # tsdf, weights, X, Y, Z, mask, stream
+    'ojf_volume_surface_mask': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    # dist2, tsdf, weights, n, resolution, far, esdf, stream
+    'ojf_volume_esdf': (_i, [_vp, _vp, _vp, _sz, _f, _f, _vp, _vp]),
 }
 
 _LIB = None

@@ -246,6 +246,15 @@ class Database(torch.utils.data.Dataset):
         self._resident(scene_id, 'instances', tsdf, w, ids)
         return components.instances(ids, tsdf, w, connectivity=connectivity, min_voxels=min_voxels)
 
+    def esdf(self, scene_id, max_distance=None):
+        """Euclidean signed distance field of a scene (distance.esdf; f32 [X,Y,Z] on the device, metres): the distance of every
+        voxel to the nearest surface voxel of the estimated volume, negative inside, capped at ``max_distance``.  Reads the
+        TSDF and the weights and writes no volume of the scene; host state is refused."""
+        from . import distance
+        tsdf, w = self.scenes_est[scene_id].volume, self.fusion_weights[scene_id]
+        self._resident(scene_id, 'esdf', tsdf, w)
+        return distance.esdf(tsdf, w, float(self.resolution[scene_id]), max_distance)
+
     def evaluate(self, mode='train', workspace=None):
         """database.py:265-309 (note: averages over ALL scenes, untouched ones included, :304)."""
         results, per_scene = {}, {}
