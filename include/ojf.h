@@ -894,6 +894,43 @@ int ojf_volume_surface_mask(const uint16_t *tsdf_dev, const uint16_t *weights_de
 int ojf_volume_esdf(const int32_t *dist2_dev, const uint16_t *tsdf_dev, const uint16_t *weights_dev, size_t n, float resolution,
                     float far, float *esdf_dev, ojf_stream_t stream);
 
+/* ---- MESH SIMPLIFICATION (vertex clustering with quadric error metrics; definition: DESIGN.md §19, tests/simplify_ref.py) ----
+ * vertices_dev f32[nv][3], faces_dev i32[nf][3]; 1 <= nv < 2^31, 0 <= nf <= 2^24 (the exact integer sums are proved for that
+ * many faces).  The grid: lo_host f32[3] finite, cell > 0 and finite, GX, GY, GZ >= 1 with GX*GY*GZ < 2^31.  A vertex is valid
+ * when t = (v - lo) / cell is finite and 0 <= floorf(t) < G on every axis; all valid vertices of one cell become ONE output
+ * vertex (a cluster), the clusters are numbered by ascending cell index (gx GY + gy) GZ + gz.  The output vertex lies where the
+ * summed plane quadric of the incident faces, plus a small pull towards the vertex mean, is smallest; source_dev[c] is the input
+ * vertex of cluster c nearest to it (the lower index at a tie), to carry labels and colours.  Face f becomes
+ * (cluster[v0], cluster[v1], cluster[v2]) and is kept when its indices are in range, its vertices valid, its fp32 area neither
+ * 0 nor non-finite and its three clusters differ; kept faces stay in input order, face_source_dev[j] is the input face.
+ * The same bits on every run and for every order of the faces (all sums are exact integers).
+ * Two calls, like ojf_mesh_extract: phases MARK|SCAN|COUNT write counts_dev[0] = clusters and counts_dev[1] = kept faces and
+ *   touch no output; the host reads them, allocates out_vertices_dev f32[vertex_capacity][3], source_dev i32[vertex_capacity],
+ *   out_faces_dev i32[face_capacity][3], face_source_dev i32[face_capacity] and clusters_dev of
+ *   ojf_mesh_simplify_cluster_bytes(counts[0]) bytes (128 per cluster, 128-byte aligned), and calls again with
+ *   ACCUMULATE|SOLVE|NEAREST|FACES and the same other arguments.  Any subset of the phase bits runs, in that order, on what
+ *   earlier calls left in workspace_dev, clusters_dev and counts_dev.  Nothing is written past a capacity, and no cluster past
+ *   clusters_bytes / 128 is touched.
+ * workspace_dev: ojf_mesh_simplify_workspace_bytes(nv, nf, GX, GY, GZ) bytes, 8-byte aligned; 0 for sizes out of range.
+ * All launches go on the caller's stream and never wait.  Bad arguments (sizes out of range, nf > 2^24, unknown phases, null
+ *   required pointers, a short workspace, alignment, a cell that is not > 0 and finite, a non-finite lo) are refused before any
+ *   HIP call and leave every output untouched.  The kernels are described in csrc/ojf_simplify.hip. */
+#define OJF_SIMPLIFY_MARK 1
+#define OJF_SIMPLIFY_SCAN 2
+#define OJF_SIMPLIFY_COUNT 4
+#define OJF_SIMPLIFY_ACCUMULATE 8
+#define OJF_SIMPLIFY_SOLVE 16
+#define OJF_SIMPLIFY_NEAREST 32
+#define OJF_SIMPLIFY_FACES 64
+#define OJF_SIMPLIFY_ALL 127
+size_t ojf_mesh_simplify_workspace_bytes(int nv, int nf, int GX, int GY, int GZ);
+size_t ojf_mesh_simplify_cluster_bytes(uint32_t nc);
+int ojf_mesh_simplify(const float *vertices_dev, int nv, const int32_t *faces_dev, int nf, const float *lo_host, float cell, int GX,
+                      int GY, int GZ, int phases, void *workspace_dev, size_t workspace_bytes, void *clusters_dev,
+                      size_t clusters_bytes, float *out_vertices_dev, int32_t *source_dev, uint32_t vertex_capacity,
+                      int32_t *out_faces_dev, int32_t *face_source_dev, uint32_t face_capacity, uint32_t *counts_dev,
+                      ojf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,8 @@ RESAMPLE_REPLACE, RESAMPLE_MERGE = 0, 1  # include/ojf.h OJF_RESAMPLE_REPLACE / 
 MESH_DISTANCE_BIN, MESH_DISTANCE_SCAN, MESH_DISTANCE_FILL, MESH_DISTANCE_GATHER, MESH_DISTANCE_ALL = 1, 2, 4, 8, 15  # OJF_MESH_DISTANCE_*
 COMPONENTS_BRICK, COMPONENTS_SEAM, COMPONENTS_FLATTEN, COMPONENTS_RANK, COMPONENTS_LIST, COMPONENTS_ALL = 1, 2, 4, 8, 16, 31  # OJF_COMPONENTS_*
 EDT_Z, EDT_Y, EDT_X, EDT_ALL, EDT_NONE = 1, 2, 4, 7, 2 ** 31 - 1  # OJF_EDT_*
+(SIMPLIFY_MARK, SIMPLIFY_SCAN, SIMPLIFY_COUNT, SIMPLIFY_ACCUMULATE, SIMPLIFY_SOLVE, SIMPLIFY_NEAREST, SIMPLIFY_FACES,
+ SIMPLIFY_ALL) = 1, 2, 4, 8, 16, 32, 64, 127  # OJF_SIMPLIFY_*
 
 
 class ExtractJob(ctypes.Structure):
@@ -214,6 +216,12 @@ SIGNATURES = {
     'ojf_volume_surface_mask': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     # dist2, tsdf, weights, n, resolution, far, esdf, stream
     'ojf_volume_esdf': (_i, [_vp, _vp, _vp, _sz, _f, _f, _vp, _vp]),
+    'ojf_mesh_simplify_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
+    'ojf_mesh_simplify_cluster_bytes': (_sz, [_c.c_uint32]),
+    # vertices, nv, faces, nf, lo, cell, GX, GY, GZ, phases, workspace, workspace_bytes, clusters, clusters_bytes, out vertices,
+    # source, vertex capacity, out faces, face source, face capacity, counts, stream
+    'ojf_mesh_simplify': (_i, [_vp, _i, _vp, _i, _vp, _f, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _vp, _c.c_uint32, _vp, _vp,
+                               _c.c_uint32, _vp, _vp]),
 }
 
 _LIB = None

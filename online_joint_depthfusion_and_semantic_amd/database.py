@@ -342,16 +342,17 @@ class Database(torch.utils.data.Dataset):
         g = np.asarray(vertices, dtype=np.float32) / np.float32(self.resolution[scene_id])  # (one fp32 division per coordinate)
         return color.sample_color(self._color_volume(scene_id, who), g).cpu().numpy()
 
-    def get_mesh(self, scene_id, semantics=False, palette=None, color=False):
+    def get_mesh(self, scene_id, semantics=False, palette=None, color=False, simplify=None):
         """database.py:118-139: (vertices, faces, normals, rgb) of the zero level set of the estimated volume in
         the reference's mesh frame (voxel index * voxel size, no origin).  Marching tetrahedra instead of skimage's
         marching cubes: same surface, different triangulation (mesh.py).  color=True: rgb is what the scene's colour
         volume holds at the vertices (color.sample_color), in [0,1] and the images' channel order, 0 where nothing is
-        coloured."""
+        coloured.  simplify: None, or the cell size in voxels of the quadric vertex clustering (mesh_simplify.py) the mesh
+        goes through before it leaves the device."""
         from . import mesh
         ids = self._device_volume(self.ids_est[scene_id].volume, torch.uint8) if semantics else None
         m = mesh.extract_mesh(self._device_volume(self.scenes_est[scene_id].volume, torch.float16), ids=ids,
-                              resolution=float(self.resolution[scene_id]), palette=palette)
+                              resolution=float(self.resolution[scene_id]), palette=palette, simplify=simplify)
         if color:
             return m['vertices'], m['faces'], m['normals'], self._vertex_colors(scene_id, m['vertices'], 'get_mesh')[:, :3] / 255.0
         return m['vertices'], m['faces'], m['normals'], m['rgb']
@@ -558,11 +559,12 @@ class Database(torch.utils.data.Dataset):
             self.label_probs[dst_scene] = fresh['label_probs']
         self.state[dst_scene] = self.state[dst_scene] or self.state[src_scene]
 
-    def save_to_workspace(self, workspace, mode, save_mode='ply'):
+    def save_to_workspace(self, workspace, mode, save_mode='ply', simplify=None):
         """database.py:141-177: every scene that holds integrated frames goes to the workspace's output directory as
         ``<scene>.tsdf_<mode>.hf5`` / ``.weights_<mode>.hf5`` / ``.semantic_<mode>.hf5`` ('tsdf'), ``<scene>_<mode>.ply``
         ('ply'), or all of them ('test').  ``workspace`` offers save_tsdf_data / save_weights_data /
-        save_semantic_data / save_ply_data(file, volume) (utils/setup.py:253-267; drivers.Workspace)."""
+        save_semantic_data / save_ply_data(file, volume) (utils/setup.py:253-267; drivers.Workspace).  simplify (cell size in
+        voxels, SETTINGS.simplify; default off) goes to save_ply_data as a keyword when it is set."""
         if save_mode not in ('tsdf', 'ply', 'test'):
             return  # the reference's if / elif chain falls through silently
         for s in self.scenes:
@@ -575,13 +577,15 @@ class Database(torch.utils.data.Dataset):
                 if self.semantics:
                     workspace.save_semantic_data('{}.semantic_{}.hf5'.format(base, mode), self.ids_est[s].volume)
             if save_mode in ('ply', 'test'):
-                workspace.save_ply_data('{}_{}.ply'.format(base, mode), self.scenes_est[s].volume)
+                workspace.save_ply_data('{}_{}.ply'.format(base, mode), self.scenes_est[s].volume,
+                                        **({} if simplify is None else {'simplify': simplify}))
 
-    def save(self, path, save_mode='ply', scene_id=None, palette=None):
+    def save(self, path, save_mode='ply', scene_id=None, palette=None, simplify=None):
         """database.py:172-261: 'tsdf' (volumes), 'ply' (mesh), 'test' (volumes + mesh + label-coloured mesh whose
         alpha channel carries the label id).  A scene with a colour volume also gets ``<scene>_color.ply`` (the mesh with
         its sampled vertex colours, alpha 255 where coloured) beside every mesh and ``<scene>.color.hf5`` beside the volumes; a scene
-        with a class-distribution volume gets ``<scene>.label_probs.hf5`` there."""
+        with a class-distribution volume gets ``<scene>.label_probs.hf5`` there.  simplify (cell size in voxels; default off):
+        the meshes go through the quadric vertex clustering of mesh_simplify.py first."""
         if scene_id is None:
             raise NotImplementedError
         if save_mode not in ('tsdf', 'ply', 'test'):
@@ -592,7 +596,7 @@ class Database(torch.utils.data.Dataset):
             sem = self.semantics and save_mode == 'test'
             ids = self._device_volume(self.ids_est[scene_id].volume, torch.uint8) if sem else None
             m = mesh.extract_mesh(self._device_volume(self.scenes_est[scene_id].volume, torch.float16), ids=ids,
-                                  resolution=float(self.resolution[scene_id]), palette=palette)
+                                  resolution=float(self.resolution[scene_id]), palette=palette, simplify=simplify)
             mesh.save_ply(os.path.join(path, base + '.ply'), m['vertices'], m['faces'], m['normals'])
             if sem:
                 table = np.array(mesh.default_palette() if palette is None else palette, dtype=np.uint8)

@@ -103,11 +103,12 @@ class Workspace:
     def save_semantic_data(self, file, data):
         self._save_volume(file, 'semantics', data)
 
-    def save_ply_data(self, file, data, resolution=0.01):
-        """utils/saving.py:42-48 (hard-coded 1 cm spacing there); the mesh comes from the HIP kernel (mesh.py)."""
+    def save_ply_data(self, file, data, resolution=0.01, simplify=None):
+        """utils/saving.py:42-48 (hard-coded 1 cm spacing there); the mesh comes from the HIP kernel (mesh.py).  simplify: the
+        cell size in voxels of mesh.extract_mesh's simplification, default off."""
         from . import mesh
         vol = data if torch.is_tensor(data) else torch.from_numpy(np.ascontiguousarray(data))
-        m = mesh.extract_mesh(vol.to(device='cuda', dtype=torch.float16).contiguous(), resolution=float(resolution))
+        m = mesh.extract_mesh(vol.to(device='cuda', dtype=torch.float16).contiguous(), resolution=float(resolution), simplify=simplify)
         mesh.save_ply(os.path.join(self.output_path, file), m['vertices'], m['faces'], m['normals'])
 
 
@@ -196,7 +197,8 @@ def test_fusion(config, dataset, device, rank=0, world=1, state_dict=None, log=p
         with open(os.path.join(test_dir, 'test.logs' if world == 1 else 'test.rank%d.logs' % rank), 'a') as f:
             f.write('\n'.join(lines) + '\n')
         for scene_id in database.scenes_est.keys():
-            database.save(path=test_dir, save_mode=config.SETTINGS.get('save_mode', 'test'), scene_id=scene_id)
+            database.save(path=test_dir, save_mode=config.SETTINGS.get('save_mode', 'test'), scene_id=scene_id,
+                          simplify=config.SETTINGS.get('simplify', None))
     return results, per_scene, database
 
 
@@ -353,6 +355,7 @@ def train_fusion(config, dataset, device, rank=0, world=1, max_steps=None, log=p
     log_freq = int(config.SETTINGS.get('log_freq', 0) or 0)
     hybrid = config.DATA.get('data_load_strategy', None) == 'hybrid'
     save_mode = config.SETTINGS.get('save_mode', 'tsdf')
+    simplify = config.SETTINGS.get('simplify', None)  # cell size in voxels of the exported meshes' simplification; default off
     best_score = 0.
     losses, step, window = [], 0, 0.
     done = False
@@ -438,13 +441,13 @@ def train_fusion(config, dataset, device, rank=0, world=1, max_steps=None, log=p
                     if score >= best_score:  # train_fusion.py:226-240
                         best_score = score
                         if workspace is not None:
-                            val_database.save_to_workspace(workspace, mode='best_val', save_mode=save_mode)
+                            val_database.save_to_workspace(workspace, mode='best_val', save_mode=save_mode, simplify=simplify)
                         if chief:
                             workspace.log('Found new best model with score {} at epoch {}'.format(best_score, epoch), mode='val')
                             workspace.save_model_state({'epoch': epoch + 1, 'model_state': net.state_dict(),
                                                         'best_iou': best_score}, is_best=True, name='best.pth.tar')
                     if workspace is not None:
-                        val_database.save_to_workspace(workspace, mode='latest_val', save_mode=save_mode)
+                        val_database.save_to_workspace(workspace, mode='latest_val', save_mode=save_mode, simplify=simplify)
                 if chief:  # train_fusion.py:245-251
                     workspace.save_model_state({'epoch': epoch + 1, 'model_state': net.state_dict(),
                                                 'optimizer_state': optimizer.state_dict(),

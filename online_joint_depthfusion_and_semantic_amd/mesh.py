@@ -107,11 +107,19 @@ def default_palette():
     return table
 
 
-def extract_mesh(tsdf, weights=None, ids=None, iso=0., origin=(0., 0., 0.), resolution=1., palette=None):
+def extract_mesh(tsdf, weights=None, ids=None, iso=0., origin=(0., 0., 0.), resolution=1., palette=None, simplify=None):
     """Database.get_mesh equivalent: dict(vertices, faces, normals, labels, rgb) of numpy arrays.  rgb in [0,1] with
-    id 0 shown grey as database.py:132-135 does; None without ids."""
+    id 0 shown grey as database.py:132-135 does; None without ids.  simplify: None, or the cell size in voxels (e.g. 2) of
+    the quadric vertex clustering the mesh goes through on the device (mesh_simplify.py); labels are those of the input
+    vertex nearest to each output vertex."""
+    if simplify is not None:
+        from . import mesh_simplify
+        cell = mesh_simplify.voxel_cell(simplify, resolution)
     tri, labels, keys = extract_triangles(tsdf, weights, ids, iso, origin, resolution, keys=True)
     verts, faces, vlab = weld(tri, labels, keys, n_voxels=tsdf.numel())
+    if simplify is not None:
+        verts, faces, vlab = mesh_simplify.simplify_tensors(verts, faces, cell, vlab)[:3]
+        faces = faces.to(torch.int64)
     normals = vertex_normals(verts, faces) if faces.shape[0] else torch.zeros_like(verts)
     out = {'vertices': verts.cpu().numpy(), 'faces': faces.to(torch.int32).cpu().numpy(), 'normals': normals.cpu().numpy(),
            'labels': None, 'rgb': None}
