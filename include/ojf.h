@@ -226,6 +226,21 @@ int ojf_pool_pyramid(const float *z_dev, const float *z2_dev, float *q1_dev, flo
                      const float *wfg_t_dev, const float *bf_dev, int cphys, int c_out, float *bias_out_dev, int bias_len,
                      ojf_stream_t stream);
 
+/* Test entry point: the stand-alone branch-entry GEMM of a VortexPooling in the net's forward pass (entry1x1_kernel, the 8-input-tile
+ * form in split-fp16 arithmetic), on caller-supplied device buffers.  weight_host [4*cs][c_in_phys] and bias_host [4*cs] are the raw fp32
+ * layer (c_in_phys <= 128, cs <= 20, multiples of 4); the call packs them as the net does, runs one launch and synchronises `stream`.
+ * Planes: [group][npix] float4, 16-byte aligned; the float4 in front of in_dev must be readable and zero (what lanes outside the frame
+ * read).  in_dev: c4_in groups (in_split: split planes, {4 fp16 high halves | 4 low halves} per float4).  out_dev: 5 * 4 groups are
+ * computed, groups < og_store (<= cs) are written; ReLU on channels < act_n; groups < split_groups are written as split planes.
+ * colsums_dev: int64 fix[16][256] (2^-20 fixed point), then uint32 bad[256] - the launch ADDS the channel sums of its input (which
+ * shard a strip adds into is unspecified; the shards' integer sum is not) and sets bad[c] where a 64-pixel strip's sum is not finite.
+ * form: 0 = one 64-pixel strip per block, 1 = the persistent form the net launches (a block walks several strips, the next strip's
+ * planes in flight while one computes); both give the same bits.  max_blocks: 0 = the net's grid rule, > 0 caps the persistent grid.
+ * A stored pre-activation beyond the fp16 range raises the process-wide range guard (ojf_net_check). */
+int ojf_entry_gemm(const float *weight_host, const float *bias_host, int c_in_phys, int cs, const float *in_dev, int in_split,
+                   int c4_in, int npix, float *out_dev, int og_store, int split_groups, int act_n, void *colsums_dev, int form,
+                   int max_blocks, ojf_stream_t stream);
+
 /* ---- SEGCONV: convolutions of the 2-D semantic front-end (AdapNet++) ---------------------------
  * One prepacked layer = nn.Conv2d (groups 1, square kernel <= 7, any stride / dilation / zero padding) with what
  * follows it in modules/adapnet.py folded in: eval-mode BatchNorm as scale_host[c_out] (multiplied into the weights)

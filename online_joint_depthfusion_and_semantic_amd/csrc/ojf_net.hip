@@ -904,7 +904,30 @@ struct ChainArgs {
     struct ColSums *colsum;       // channel sums of the entry layer's INPUT (global-average branch), see block_colsum
     int in_split = 0;             // entry1x1_kernel: the input planes are split planes (the dense-growth buffer of dense_chain_kernel)
     int split_groups = 0;         // kChainEntry: channel groups < split_groups (branch 0, read by its 3x3 convolution only) are stored as split planes
+#ifdef OJF_ENTRY_STAMPS
+    int stamp = 0;                // the stand-alone entry GEMM's launches set it: the fused tail's entry layer leaves the stamps alone
+#endif
 };
+
+#ifdef OJF_ENTRY_STAMPS  // profiling build only (tools/entry_stamps.py): phase stamps of the stand-alone entry GEMM's blocks, thread 0
+// [block][strip of the block's walk < 4][slot]: clock64 at 0 strip start (block start for the first), 1 inputs landed, 2 channel sums
+// done, 3 weight part 0 landed (persistent form: the whole layer, first strip only), 4 weight part 1 landed (one-strip form only),
+// 5 MFMAs issued, 6 stores issued; 100-MHz wall clock at 7 strip start, 8 strip end; 9 = strip index + 1.  In the persistent form a
+// strip's planes land while the strip before it computes: its slot 1 then precedes its slot 0.  The stamps of the LAST stamped launch remain.
+constexpr int kEntryStampBlocks = 8192, kEntryStampStrips = 4, kEntryStampSlots = 10;
+__device__ unsigned long long g_entry_stamps[kEntryStampBlocks][kEntryStampStrips][kEntryStampSlots];
+#define ENTRY_STAMP(on, k, i, v)                                                                                              \
+    do {                                                                                                                       \
+        if ((on) && threadIdx.x == 0 && blockIdx.x < (unsigned)kEntryStampBlocks && (k) < kEntryStampStrips)                   \
+            g_entry_stamps[blockIdx.x][k][i] = (i) == 9 ? (unsigned long long)(v) : ((i) >= 7 ? wall_clock64() : clock64());   \
+    } while (0)
+#define ENTRY_STAMP_ON(a) ((a).stamp)
+#define ENTRY_STAMP_LANDED() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")  // "inputs landed" has to wait for them (the one-strip form)
+#else
+#define ENTRY_STAMP(on, k, i, v) do { } while (0)
+#define ENTRY_STAMP_ON(a) 0
+#define ENTRY_STAMP_LANDED() do { } while (0)
+#endif
 
 // Weight fragments of one (output tile, K block) pair.  fp32: K block = one 16-channel input tile, 64 float4
 // (lane (oc i16, g) holds W[oc][16S+4g .. +3]).  split-fp16: K block = two input tiles (32 channels), 128 float4 =
@@ -1041,6 +1064,7 @@ __device__ __forceinline__ void chain_layer(const f32x4 (&in)[MT][NA], f32x4 (&o
         if constexpr (chain_dma(ARITH)) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's chunks of the current part have landed
             __syncthreads();  // ... everybody's have, and the readers of the other buffer are done with it
+            if constexpr (MODE == kChainEntry) ENTRY_STAMP(ENTRY_STAMP_ON(a) && part < 2, 0, 3 + (part < 2 ? part : 0), 0);
             wpart = wlds + buf * chain_cap(ARITH);
             buf ^= 1;
             dma_part(nsrc, wlds + buf * chain_cap(ARITH), nsize, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane);
@@ -1109,6 +1133,7 @@ __device__ __forceinline__ void chain_layer(const f32x4 (&in)[MT][NA], f32x4 (&o
             }
         }
     }
+    if constexpr (MODE == kChainEntry) ENTRY_STAMP(ENTRY_STAMP_ON(a), 0, 5, 0);
     if constexpr (MODE != kChainAccumulate) {
         const int g = lane >> 4;
         float gmax = 0.0f;
@@ -1146,6 +1171,10 @@ __device__ __forceinline__ void chain_layer(const f32x4 (&in)[MT][NA], f32x4 (&o
         }
         if constexpr (ARITH == OJF_ARITH_F16X3)
             if (gmax > 65504.0f && a.ovf) guard_raise(a.ovf, 1);
+        if constexpr (MODE == kChainEntry) {
+            ENTRY_STAMP(ENTRY_STAMP_ON(a), 0, 6, 0);
+            ENTRY_STAMP(ENTRY_STAMP_ON(a), 0, 8, 0);
+        }
     }
 }
 
@@ -1192,7 +1221,18 @@ struct ColSums {
 static_assert(sizeof(ColSums) == kColShards * kColMax * 8 + kColMax * 4, "the layout include/ojf.h gives for ojf_pool_pyramid");
 constexpr int colsum_row(int nt) { return nt > 8 ? 256 : 128; }  // floats per wave row of block_colsum's LDS scratch
 
-template <int MT, int NT, int NA>
+// v of the lane CTRL names within this lane's row of 16 (a DPP move: VALU, where __shfl_xor goes through the LDS crossbar)
+template <int CTRL>
+__device__ __forceinline__ float row_dpp(float v)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+
+// DPP: the butterfly's partners come by DPP moves instead of __shfl_xor - the same sums in the same order.  Lane i adds the value of lane
+// i ^ 8 (row_ror:8), then of lane (i + 4) & 15 (row_ror:4: that is lane i ^ 4 or lane i ^ 4 ^ 8, which hold the same bits after the first
+// step, fp32 addition being commutative), then of lanes i ^ 2 and i ^ 1 (quad_perm).  Only the payload of a NaN can differ, and a
+// non-finite sum sets the channel's flag whatever its bits.
+template <int MT, int NT, bool DPP = false, int NA = 0>
 __device__ __forceinline__ void block_colsum(const f32x4 (&x)[MT][NA], const int (&p)[MT], int npix, float *red /* LDS [waves][colsum_row(NT)] */,
                                              ColSums *out, int lane, int wave, int off = 0)
 {
@@ -1207,10 +1247,17 @@ __device__ __forceinline__ void block_colsum(const f32x4 (&x)[MT][NA], const int
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float v = s[j];
-            v += __shfl_xor(v, 8, 64);
-            v += __shfl_xor(v, 4, 64);
-            v += __shfl_xor(v, 2, 64);
-            v += __shfl_xor(v, 1, 64);
+            if constexpr (DPP) {
+                v += row_dpp<0x128>(v);  // row_ror:8
+                v += row_dpp<0x124>(v);  // row_ror:4
+                v += row_dpp<0x4e>(v);   // quad_perm:[2,3,0,1]
+                v += row_dpp<0xb1>(v);   // quad_perm:[1,0,3,2]
+            } else {
+                v += __shfl_xor(v, 8, 64);
+                v += __shfl_xor(v, 4, 64);
+                v += __shfl_xor(v, 2, 64);
+                v += __shfl_xor(v, 1, 64);
+            }
             s[j] = v;
         }
         if ((lane & 15) == 0) *reinterpret_cast<f32x4 *>(red + wave * RS + S * 16 + 4 * g) = s;
@@ -1246,6 +1293,9 @@ __global__ __launch_bounds__(kChainThreads, kChainBlocks) void entry1x1_kernel(c
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i16 = lane & 15, g = lane >> 4;
     const int strip = (banded_block_x() * kChainWaves + wave) * (MT * 16);
+    ENTRY_STAMP(ENTRY_STAMP_ON(a), 0, 7, 0);
+    ENTRY_STAMP(ENTRY_STAMP_ON(a), 0, 0, 0);
+    ENTRY_STAMP(ENTRY_STAMP_ON(a), 0, 9, banded_block_x() + 1);
     f32x4 pre[kChainPre];
     int buf = 0;
     VecStage vs;
@@ -1278,8 +1328,182 @@ __global__ __launch_bounds__(kChainThreads, kChainBlocks) void entry1x1_kernel(c
             if (a.in_split) x[m][S] = unsplit4(x[m][S]);  // hi + lo: exact in fp32, the value every consumer of the halves means
         }
     }
+    ENTRY_STAMP_LANDED();
+    ENTRY_STAMP(ENTRY_STAMP_ON(a), 0, 1, 0);
     if (a.colsum) block_colsum<MT, NTIN>(x, p, a.npix, red, a.colsum, lane, wave);
+    ENTRY_STAMP(ENTRY_STAMP_ON(a), 0, 2, 0);
     chain_layer<ARITH, MT, NTIN, NTOUT, kChainEntry, 0>(x, y, wlds, a.w, a, p, lane, pre, buf, vs);
+}
+
+// Persistent form of the stand-alone entry GEMM for the case the headline net runs (split-fp16, 8 input tiles -> 5, one pixel
+// tile per wave).  The one-strip kernel above runs its phases in series - planes in (cold: ~3.9 us of a block's 10), channel
+// sums, weight part 0, MFMAs, part 1, MFMAs, stores - and every block streams the layer's 40 KB of weights for its 64 pixels.
+// Here a grid of at most kChainBlocks blocks per CU keeps the whole layer and its epilogue vectors in LDS and walks its strips
+// (entry_walk_strip: a static assignment - no inter-block wait, flag or ticket, nothing depends on residency); while strip k
+// computes, the eight plane loads of strip k + 1 are in flight into a second register set.  The arithmetic of a strip is the
+// one-strip kernel's, operation for operation: unsplit4, block_colsum over the same 64 pixels, split_f16 once, each
+// accumulator's K blocks ascending in mfma_f16x3's term order, the kChainEntry epilogue - the same bits in the output planes
+// and the same integers in ColSums (which fix[] shard a strip adds into differs; the fold sums the shards as integers).
+//
+// Strip k of block b's walk, -1 past its end.  strips and grid both multiples of 8: block b stays inside XCD band b & 7 (the
+// eighth of the strips the one-strip grid gives that XCD) and walks (b >> 3) + k * grid / 8 within it; otherwise b + k * grid.
+// (tests/test_entry_gemm_host.py restates it.)
+__host__ __device__ __forceinline__ int entry_walk_strip(int b, int grid, int strips, int k)
+{
+    if (((strips | grid) & 7) == 0) {
+        const int per = strips >> 3, j = (b >> 3) + k * (grid >> 3);
+        return j < per ? (b & 7) * per + j : -1;
+    }
+    const int s = b + k * grid;
+    return s < strips ? s : -1;
+}
+
+// the eight plane loads of one wave's 16 pixels of strip s (s < 0: no such strip - every lane reads the zero float4 in front of the planes)
+__device__ __forceinline__ void entry_load_planes(f32x4 (&x)[8], const ChainArgs &a, int s, int wave, int i16, int g)
+{
+    const int p = (s * kChainWaves + wave) * 16 + i16;
+#pragma unroll
+    for (int S = 0; S < 8; ++S) {
+        const int G = 4 * S + g;
+        const bool ok = s >= 0 && p < a.npix && G < a.c4_in;
+        x[S] = a.in[ok ? (a.in_g0 + G) * a.npix + p : -1];
+    }
+}
+
+// dma_part of a compile-time size that gives every wave the same number of 1 KB chunks: no branch around the instructions, so the
+// compiler's own waits can count them
+template <int SIZE>
+__device__ __forceinline__ void entry_dma(const f32x4 *src, f32x4 *dst, int wave, int lane)
+{
+    static_assert(SIZE % (64 * kChainWaves) == 0, "whole rounds of the block's waves");
+#pragma unroll
+    for (int c0 = 0; c0 < SIZE / 64; c0 += kChainWaves)
+        __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)(src + (c0 + wave) * 64 + lane),
+                                         (void __attribute__((address_space(3))) *)(dst + (c0 + wave) * 64), 16, 0, 0);
+}
+
+// MFMAs of CNT output tiles (accumulators y[NB ..]) over the KB K blocks, weights at wpart [tile][K block][hi 64 | lo 64]: K block
+// outer, tile inner, fragments requested kChainAhead steps ahead of their MFMAs (chain_layer's pipeline)
+template <int KB, int NB, int CNT, int NY>
+__device__ __forceinline__ void entry_mfma_tiles(const f32x4 *wpart, int lane, const f16x8 (&xh)[KB], const f16x8 (&xl)[KB], f32x4 (&y)[NY])
+{
+    constexpr int steps = KB * CNT;
+    f32x4 rh[kChainAhead], rl[kChainAhead];
+    auto frag = [&](int t) { return ((t % CNT) * KB + t / CNT) * 128; };  // step t = (S = t / CNT, tile NB + t % CNT)
+#pragma unroll
+    for (int t = 0; t < kChainAhead; ++t) {
+        rh[t] = wpart[frag(t) + lane];
+        rl[t] = wpart[frag(t) + 64 + lane];
+    }
+#pragma unroll
+    for (int t = 0; t < steps; ++t) {
+        const f32x4 wh = rh[t % kChainAhead], wl = rl[t % kChainAhead];
+        if (t + kChainAhead < steps) {
+            rh[t % kChainAhead] = wpart[frag(t + kChainAhead) + lane];
+            rl[t % kChainAhead] = wpart[frag(t + kChainAhead) + 64 + lane];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        y[NB + t % CNT] = mfma_f16x3(wh, wl, xh[t / CNT], xl[t / CNT], y[NB + t % CNT]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+template <bool IN_SPLIT>  // the input planes are split planes (the dense-growth buffer of dense_chain_kernel: the headline) | plain fp32
+__global__ __launch_bounds__(kChainThreads, kChainBlocks) void entry1x1_persistent_kernel(const ChainArgs a, const int strips)
+{
+    constexpr int ARITH = OJF_ARITH_F16X3, NTIN = 8, NTOUT = 5, KB = chain_kblocks(ARITH, NTIN);
+    constexpr int kSize = chain_layer_size(ARITH, NTIN, NTOUT);  // 2560 float4
+    constexpr int kVec = chain_bias_stride(ARITH, NTOUT) / 4;
+    static_assert(kVec <= kVecF4 && kVec <= kChainThreads, "one float4 of the epilogue vectors per thread");
+    __shared__ f32x4 wlds[kSize];
+    __shared__ f32x4 vec[kVecF4];
+    // two rows: the readers of strip k's partial sums and the writers of strip k + 1's are separated by no barrier, those of strip k + 2's
+    // by the barrier inside strip k + 1's block_colsum
+    __shared__ float red[2][kChainWaves * colsum_row(NTIN)];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i16 = lane & 15, g = lane >> 4;
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    int s = entry_walk_strip(blockIdx.x, gridDim.x, strips, 0);
+    ENTRY_STAMP(ENTRY_STAMP_ON(a), 0, 7, 0);
+    ENTRY_STAMP(ENTRY_STAMP_ON(a), 0, 0, 0);
+    // Vector-memory order of a wave: epilogue vectors | the layer's weights (10 DMA instructions) | planes of the first strip || planes
+    // of the second strip.  Loads complete in order, and the first strip's planes - cold, written by dense_chain_kernel on other XCDs -
+    // are the last to land: one wait covers all three, and the weights cost a block nothing beyond the plane latency it pays anyway.
+    // (Two DMA groups with waits of their own, as in the one-strip kernel, do not survive the compiler here: while a DMA instruction
+    // is in flight in its model it puts a full vmcnt wait in front of the next LDS read, LDS write and __syncthreads - with tiles 3..4
+    // requested behind the first barrier the first MFMAs waited for them all the same, and with them requested behind the first strip's
+    // planes the channel sums' barrier waited for the second strip's planes.)
+    f32x4 vreg = f32x4{0.f, 0.f, 0.f, 0.f};
+    if ((int)threadIdx.x < kVec) vreg = reinterpret_cast<const f32x4 *>(a.bias)[threadIdx.x];
+    entry_dma<kSize>(a.w, wlds, wave_u, lane);
+    f32x4 xn[NTIN], x[1][NTIN];
+    entry_load_planes(xn, a, s, wave, i16, g);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's chunks of the weights and its planes have landed
+    ENTRY_STAMP(ENTRY_STAMP_ON(a), 0, 1, 0);
+    if ((int)threadIdx.x < kVec) vec[threadIdx.x] = vreg;  // published by the first barrier of the loop
+#pragma unroll
+    for (int S = 0; S < NTIN; ++S) x[0][S] = IN_SPLIT ? unsplit4(xn[S]) : xn[S];  // hi + lo: exact in fp32, the value every consumer of the halves means
+    int sn = entry_walk_strip(blockIdx.x, gridDim.x, strips, 1);
+    entry_load_planes(xn, a, sn, wave, i16, g);  // in flight while the first strip computes
+    asm volatile("" ::: "memory");
+    float gmax = 0.0f;
+    for (int k = 0; s >= 0; ++k) {
+        ENTRY_STAMP(ENTRY_STAMP_ON(a), k, 9, s + 1);
+        // (opaque copy of the lane's channel-group index: left alone, the compiler hoists every mask and address part derived from it out of the
+        // loop - 38 lane masks and 13 address pairs held across the strips, which spilled both register files)
+        int gk = g;
+        asm volatile("" : "+v"(gk));
+        const int p[1] = {(s * kChainWaves + wave) * 16 + i16};  // waves past the image still take part in the barriers
+        // (the butterfly by DPP moves: 128 ds_bpermute per wave and strip through the LDS crossbar were 1.8 us of a strip's 5.4)
+        if (a.colsum) block_colsum<1, NTIN, true>(x, p, a.npix, red[k & 1], a.colsum, lane, wave);
+        ENTRY_STAMP(ENTRY_STAMP_ON(a), k, 2, 0);
+        f16x8 xh[KB], xl[KB];
+#pragma unroll
+        for (int S = 0; S < KB; ++S) split_f16(x[0][2 * S], x[0][2 * S + 1], xh[S], xl[S]);
+        f32x4 y[NTOUT];
+#pragma unroll
+        for (int n2 = 0; n2 < NTOUT; ++n2) y[n2] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (k == 0) {  // the weights: every wave waited for its chunks above
+            __syncthreads();
+            ENTRY_STAMP(ENTRY_STAMP_ON(a), k, 3, 0);
+        }
+        // one round over the five tiles where the one-strip kernel runs tiles 0..2, then 3..4: each accumulator still takes its K blocks in
+        // ascending order, and nothing else decides its bits
+        entry_mfma_tiles<KB, 0, NTOUT>(wlds, lane, xh, xl, y);
+        ENTRY_STAMP(ENTRY_STAMP_ON(a), k, 5, 0);
+        // The next strip's planes, requested one strip ago, leave their registers BEFORE this strip's stores are issued: stores count in
+        // vmcnt like loads, so a wait for the planes at the top of the next strip would also wait for the stores' acknowledgements.
+        const int s_next = sn;
+        if (s_next >= 0) {
+#pragma unroll
+            for (int S = 0; S < NTIN; ++S) x[0][S] = IN_SPLIT ? unsplit4(xn[S]) : xn[S];
+#ifdef OJF_ENTRY_STAMPS
+            __builtin_amdgcn_sched_barrier(0);  // (the stamp stays behind the wait the conversions needed)
+            ENTRY_STAMP(ENTRY_STAMP_ON(a), k + 1, 1, 0);
+#endif
+            sn = entry_walk_strip(blockIdx.x, gridDim.x, strips, k + 2);
+            entry_load_planes(xn, a, sn, wave, i16, gk);
+            asm volatile("" ::: "memory");
+        }
+#pragma unroll
+        for (int n2 = 0; n2 < NTOUT; ++n2) {  // chain_layer's kChainEntry epilogue
+            const int og = n2 * 4 + gk;
+            const f32x4 lin4 = fma4(y[n2], vec[(NTOUT + n2) * 4 + g], vec[n2 * 4 + g]);
+            f32x4 v = lin4;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = (og * 4 + j < a.act_n && !(v[j] > 0.0f)) ? (v[j] != v[j] ? v[j] : 0.0f) : v[j];
+            if (p[0] < a.npix && og < a.og_store) {
+                a.out_planes[(size_t)(a.out_g0 + og) * a.npix + p[0]] = og < a.split_groups ? split_pack4(v) : v;
+                gmax = guard_max(gmax, lin4);  // over stored elements only
+            }
+        }
+        ENTRY_STAMP(ENTRY_STAMP_ON(a), k, 6, 0);
+        ENTRY_STAMP(ENTRY_STAMP_ON(a), k, 8, 0);
+        s = s_next;
+        ENTRY_STAMP(ENTRY_STAMP_ON(a) && s >= 0, k + 1, 7, 0);
+        ENTRY_STAMP(ENTRY_STAMP_ON(a) && s >= 0, k + 1, 0, 0);
+    }
+    if (gmax > 65504.0f && a.ovf) guard_raise(a.ovf, 1);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3004,6 +3228,17 @@ static dim3 launch_pyramid(PyramidArgs &pa, hipStream_t st)
 
 static int chain_blocks(const ojf_net *net) { return ((net->npix + 15) / 16 + ojf::kChainWaves - 1) / ojf::kChainWaves; }  // blocks of the MT = 1 chain kernels
 
+// The persistent entry GEMM over `strips` 64-pixel strips: min(strips, kChainBlocks x CUs) blocks - what the device holds at once,
+// though nothing depends on it - or at most max_blocks of them (> 0: tests, so that a tiny frame walks several strips per block).
+static void launch_entry_persistent(const ChainArgs &ea, int strips, int max_blocks, hipStream_t st)
+{
+    const int cus = device_cu_count();
+    int blocks = cus > 0 && ojf::kChainBlocks * cus < strips ? ojf::kChainBlocks * cus : strips;
+    if (max_blocks > 0 && max_blocks < blocks) blocks = max_blocks;
+    if (ea.in_split) hipLaunchKernelGGL(entry1x1_persistent_kernel<true>, dim3(blocks), dim3(ojf::kChainThreads), 0, st, ea, strips);
+    else hipLaunchKernelGGL(entry1x1_persistent_kernel<false>, dim3(blocks), dim3(ojf::kChainThreads), 0, st, ea, strips);
+}
+
 // one launch of a chain-layer kernel template in the net's arithmetic: KERNEL<arithmetic, further template arguments>(ARGS)
 #define OJF_LAUNCH_BY_ARITH(KERNEL, ARGS, ...)                                                                              \
     do {                                                                                                                     \
@@ -3052,9 +3287,13 @@ static int run_vortex(ojf_net *net, const VortexStep &s, hipStream_t st, const C
         ea.out_planes = planes(sc.Z); ea.out_g0 = 0; ea.og_store = 4 * c4; ea.act_n = net->cs; ea.colsum = sc.colsum;
         ea.split_groups = s.split ? c4 : 0;
         ea.in_split = s.in_split ? 1 : 0;
+#ifdef OJF_ENTRY_STAMPS
+        ea.stamp = 1;
+#endif
         // (two pixel tiles per wave - half the blocks, half the weight stream per pixel - measured 22.2 against 23.7 us and changes the
         // rounding of the channel sums: not kept, profiles/r06_fusion_net_experiments.txt)
         if (s.entry_ntin == 16) OJF_LAUNCH_BY_ARITH(entry1x1_kernel, ea, 1, 16, 5);
+        else if (h16) launch_entry_persistent(ea, (int)grid.x, 0, st);  // (profiles/entry_gemm_persistent.txt)
         else OJF_LAUNCH_BY_ARITH(entry1x1_kernel, ea, 1, 8, 5);
         if (net_trace_on())
             fprintf(stderr, "ojf_net %s | ntin %d blocks %u banded %d\n", kLaunchNames[L_ENTRY1X1], s.entry_ntin, grid.x, banded);
@@ -3798,10 +4037,56 @@ OJF_API int ojf_pool_pyramid(const float *z, const float *z2, float *q1, float *
     return check_hip(hipGetLastError(), "ojf_pool_pyramid launch");
 }
 
+OJF_API int ojf_entry_gemm(const float *weight, const float *bias, int c_in_phys, int cs, const float *in, int in_split, int c4_in,
+                           int npix, float *out, int og_store, int split_groups, int act_n, void *colsums, int form,
+                           int max_blocks, ojf_stream_t stream)
+{
+    using namespace ojf;
+    if (!weight || !bias || !in || !out || !colsums) return fail("ojf_entry_gemm: null pointer argument");
+    if (c_in_phys < 4 || c_in_phys > 128 || c_in_phys % 4 || cs < 4 || cs > 20 || cs % 4)
+        return fail("ojf_entry_gemm: the 8-tile form takes up to 128 input channels and 4 slots of up to 20, both multiples of 4");
+    if (c4_in < 1 || c4_in * 4 > c_in_phys || npix < 1 || npix > (1 << 24) || og_store < 0 || og_store > cs || split_groups < 0 || split_groups > cs || act_n < 0 ||
+        (form != 0 && form != 1) || max_blocks < 0)
+        return fail("ojf_entry_gemm: bad sizes");
+    hipStream_t st = as_stream(stream);
+    auto we = [&](int oc, int k) { return oc < 4 * cs && k < c_in_phys ? weight[(size_t)oc * c_in_phys + k] : 0.0f; };
+    const std::vector<float> re = chain_row_scales(OJF_ARITH_F16X3, 5, c_in_phys, we);
+    std::vector<float> ew, eb;
+    pack_chain_layer(ew, OJF_ARITH_F16X3, 5, 8, re, we);
+    append_chain_bias(eb, OJF_ARITH_F16X3, 5, 4 * cs, bias, re);
+    float *dw = nullptr, *db = nullptr;
+    int rc = upload(ew, &dw);
+    if (!rc) rc = upload(eb, &db);
+    if (!rc) {
+        ChainArgs ea;
+        ea.in = planes(in); ea.w = planes(dw); ea.bias = db; ea.out_rows = nullptr;
+        ea.in_g0 = 0; ea.c4_in = c4_in; ea.npix = npix; ea.rows_stride = 0; ea.rows_n = 0; ea.scale = 1.0f;
+        ea.ovf = overflow_flag();
+        ea.out_planes = planes(out); ea.out_g0 = 0; ea.og_store = og_store; ea.act_n = act_n; ea.colsum = static_cast<ColSums *>(colsums);
+        ea.split_groups = split_groups;
+        ea.in_split = in_split ? 1 : 0;
+        const int strips = ((npix + 15) / 16 + kChainWaves - 1) / kChainWaves;
+        if (form == 1) launch_entry_persistent(ea, strips, max_blocks, st);
+        else hipLaunchKernelGGL((entry1x1_kernel<OJF_ARITH_F16X3, 1, 8, 5>), dim3(strips), dim3(kChainThreads), 0, st, ea);
+        rc = check_hip(hipGetLastError(), "ojf_entry_gemm launch");
+        if (!rc) rc = check_hip(hipStreamSynchronize(st), "ojf_entry_gemm sync");  // test-only API: packs per call
+    }
+    if (dw) (void)hipFree(dw);
+    if (db) (void)hipFree(db);
+    return rc;
+}
+
 #ifdef OJF_POOL_STAMPS
 extern "C" __attribute__((visibility("default"))) int ojf_debug_pool_stamps(void *host_dst, size_t bytes)
 {
     return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(ojf::g_pool_stamps), bytes < sizeof(ojf::g_pool_stamps) ? bytes : sizeof(ojf::g_pool_stamps));
+}
+#endif
+
+#ifdef OJF_ENTRY_STAMPS
+extern "C" __attribute__((visibility("default"))) int ojf_debug_entry_stamps(void *host_dst, size_t bytes)
+{
+    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(ojf::g_entry_stamps), bytes < sizeof(ojf::g_entry_stamps) ? bytes : sizeof(ojf::g_entry_stamps));
 }
 #endif
 
