@@ -60,7 +60,8 @@ def _models(room, E_ref, levels):
 
 
 def _associate(cuda, depth, mask, level, K, Ki, mdepth, mnormal, E_ref, E_pose, **kw):
-    """One ojf_track_associate call: (pyramid levels 0..level, J, r, reason, sums, pose, status) on the host."""
+    """One ojf_track_associate call: (pyramid levels 0..level, J, r, reason, sums, pose, status) on the host.  Keywords:
+    dist (0.1), angle (20), delta (0.03), frac (the minimum inlier fraction, 0.05)."""
     lib = _lib.load()
     h, w = depth.shape
     hl, wl = h >> level, w >> level
@@ -77,7 +78,8 @@ def _associate(cuda, depth, mask, level, K, Ki, mdepth, mnormal, E_ref, E_pose, 
     Er, Ep = track_ref_pose(E_ref), track_ref_pose(E_pose)
     rc = lib.ojf_track_associate(_lib.ptr(d), _lib.ptr(m), h, w, level, Kd.ctypes.data, Ki.ctypes.data, _lib.ptr(mdepth),
                                  _lib.ptr(mnormal), Er.ctypes.data, Ep.ctypes.data, kw.get('dist', 0.1), kw.get('angle', 20.0),
-                                 0.03, 0.05, _lib.ptr(ws), ws.numel(), _lib.ptr(pose), _lib.ptr(sums), _lib.ptr(jr),
+                                 kw.get('delta', 0.03), kw.get('frac', 0.05), _lib.ptr(ws), ws.numel(), _lib.ptr(pose),
+                                 _lib.ptr(sums), _lib.ptr(jr),
                                  _lib.ptr(reason), _lib.ptr(status), _lib.stream_ptr(cuda))
     _lib.check(rc, 'ojf_track_associate')
     wsf = ws.cpu().numpy()[:4 * sum((h >> l) * (w >> l) for l in range(level + 1))].view(np.float32)

@@ -54,9 +54,10 @@ def _dot3(a, b):
     return ((a[0] * b[0]).astype(f32) + (a[1] * b[1]).astype(f32) + (a[2] * b[2]).astype(f32)).astype(f32)
 
 
-def associate(D, Ki, K, level, mdepth, mnormal, E_ref, pose, dist_thresh=0.1, angle_thresh=20.0):
+def associate(D, Ki, K, level, mdepth, mnormal, E_ref, pose, dist_thresh=0.1, angle_thresh=20.0, pixels=False):
     """(J f32[h,w,6], r f32[h,w], reason u8[h,w]) of level ``level`` (D its pyramid level, Ki f32[9] the level's Kinv,
-    K the level-0 intrinsics, mdepth [h,w] / mnormal [h,w,3] the model images at E_ref, pose the current f64 pose)."""
+    K the level-0 intrinsics, mdepth [h,w] / mnormal [h,w,3] the model images at E_ref, pose the current f64 pose).
+    ``pixels``: also the model pixel (row i64[h,w], col i64[h,w]) each live pixel projects to (0 for reasons 1..4)."""
     D = np.asarray(D, f32)
     h, w = D.shape
     Ki = np.asarray(Ki, f32).reshape(9)
@@ -131,6 +132,8 @@ def associate(D, Ki, K, level, mdepth, mnormal, E_ref, pose, dist_thresh=0.1, an
     for i in range(6):
         J[..., i] = np.where(ok, Jv[i], f32(0))
     res[:] = np.where(ok, rv, f32(0))
+    if pixels:
+        return J, res, reason, mr, mc
     return J, res, reason
 
 
@@ -208,25 +211,75 @@ def system(sums):
     return A, -np.asarray(sums[21:27], dtype=np.float64)
 
 
-def step(sums, pose, min_count):
-    """(status code, new pose f64[3,4]) of one solve: the kernel's checks, Cholesky and left update."""
+def step(sums, pose, min_count, moves=False):
+    """(status code, new pose f64[3,4]) of one solve: the kernel's checks, Cholesky and left update.  ``moves``: also
+    th = |omega| and |tau| as the stats row holds them (0 after a failed step)."""
+    code, out, th, tau = _step(sums, pose, min_count)
+    return (code, out, th, tau) if moves else (code, out)
+
+
+def _step(sums, pose, min_count):
     sums = np.asarray(sums, dtype=np.float64)
     P = np.asarray(pose, dtype=np.float64).reshape(-1, 4)[:3]
     if sums[28] < min_count:
-        return 1, P.copy()
+        return 1, P.copy(), 0.0, 0.0
     A, b = system(sums)
     x = cholesky_solve(A, b)
     if x is None:
-        return 2, P.copy()
+        return 2, P.copy(), 0.0, 0.0
     if not np.isfinite(x).all():
-        return 3, P.copy()
+        return 3, P.copy(), 0.0, 0.0
     Ri = rodrigues(x[:3])
     out = np.empty((3, 4))
     for i in range(3):
         for j in range(3):
             out[i, j] = Ri[i, 0] * P[0, j] + Ri[i, 1] * P[1, j] + Ri[i, 2] * P[2, j]
         out[i, 3] = (Ri[i, 0] * P[0, 3] + Ri[i, 1] * P[1, 3] + Ri[i, 2] * P[2, 3]) + x[3 + i]
-    return 0, out
+    th = math.sqrt(float(x[0]) * float(x[0]) + float(x[1]) * float(x[1]) + float(x[2]) * float(x[2]))
+    tau = math.sqrt(float(x[3]) * float(x[3]) + float(x[4]) * float(x[4]) + float(x[5]) * float(x[5]))
+    return 0, out, th, tau
+
+
+def schedule(iterations, levels):
+    """The level of every step of a call, in launch order: levels - 1 down to 0, iterations[l] times each."""
+    return [l for l in range(levels - 1, -1, -1) for _ in range(int(iterations[l]))]
+
+
+def prefix_iterations(iterations, levels, k):
+    """iterations_host of the call that runs only the first k steps of ``schedule(iterations, levels)``."""
+    steps = schedule(iterations, levels)[:k]
+    return [steps.count(l) for l in range(levels)]
+
+
+def run(depth, mask, K, Kinv, mdepth, mnormal, E_ref, E_init, iterations, dist_thresh=0.1, angle_thresh=20.0, delta=0.03,
+        min_inlier_fraction=0.05, trace=None):
+    """The whole call (ojf_track): (pose f64[3,4], (code, iteration), stats f64[n,4]).  Kinv[l], mdepth[l], mnormal[l] per
+    level, len(mdepth) levels; the pyramid once, then levels L-1 down to 0 and iterations[l] times associate -> sums ->
+    step with min_count = min_inlier_fraction * h_l * w_l.  A failed step writes (s28, s27/s28 or 0, 0, 0), sets the
+    status and puts the pose back to E_init; every later step is skipped and its stats row is 0.  The sums are numpy's
+    (not the kernels' summation order).  ``trace``: a list that receives, per step that ran, dict(level, pose (before the
+    step), reason, sums, code)."""
+    levels = len(mdepth)
+    E0 = np.asarray(E_init, np.float64).reshape(-1, 4)[:3].copy()
+    pyr = pyramid(depth, mask, levels, delta)
+    steps = schedule(iterations, levels)
+    stats = np.zeros((len(steps), 4))
+    P, status = E0.copy(), (0, -1)
+    for it, l in enumerate(steps):
+        if status[0]:
+            continue
+        J, r, reason = associate(pyr[l], Kinv[l], K, l, mdepth[l], mnormal[l], E_ref, P, dist_thresh, angle_thresh)
+        with np.errstate(invalid='ignore'):
+            sums = term_matrix(J, r, reason).sum(axis=0)
+        code, Q, th, tau = _step(sums, P, float(min_inlier_fraction) * float(pyr[l].size))
+        if trace is not None:
+            trace.append(dict(level=l, pose=P.copy(), reason=reason, sums=sums, code=code))
+        stats[it] = (sums[28], sums[27] / sums[28] if sums[28] > 0 else 0.0, th, tau)
+        if code:
+            status, P = (code, it), E0.copy()
+        else:
+            P = Q
+    return P, status, stats
 
 
 def pose_error(E, E_gt):
