@@ -17,24 +17,6 @@ def _connectivity(who, connectivity):
     return int(connectivity)
 
 
-def _volume(who, vol, name, dtype, like=None):
-    """``vol`` as views.volume3 takes it: beside ``like`` (its shape and device) when that is given."""
-    if not torch.is_tensor(vol):
-        raise ValueError('{}: {} must be a {} [X,Y,Z] tensor'.format(who, name, dtype))
-    if dtype == torch.uint8 and vol.dtype == torch.bool and vol.is_contiguous():
-        vol = vol.view(torch.uint8)  # reinterpreted, not converted
-    return views.volume3(who, vol, name, dtype, shape=None if like is None else like.shape, dev=vol.device if like is None else like.device)
-
-
-def _on_device(who, vol):
-    if not vol.is_cuda:
-        raise ValueError('{}: the volumes must be cuda tensors'.format(who))
-    if vol.numel() < 1 or vol.numel() >= 2 ** 31:
-        raise ValueError('{}: 1 <= X·Y·Z < 2^31 expected, got shape {}'.format(who, tuple(vol.shape)))
-    _lib.require_gpu()
-    return _lib.load()
-
-
 def label_components(mask=None, keys=None, *, connectivity=6):
     """The connected components of the foreground of a volume, on the current stream of its device.
 
@@ -49,12 +31,12 @@ def label_components(mask=None, keys=None, *, connectivity=6):
     connectivity = _connectivity(who, connectivity)
     if mask is None and keys is None:
         raise ValueError('{}: a mask or a key volume is needed'.format(who))
-    first = _volume(who, mask if mask is not None else keys, 'mask' if mask is not None else 'keys', torch.uint8)
+    first = views.mask_volume(who, mask if mask is not None else keys, 'mask' if mask is not None else 'keys', torch.uint8)
     if mask is not None:
-        mask, keys = first, (None if keys is None else _volume(who, keys, 'keys', torch.uint8, like=first))
+        mask, keys = first, (None if keys is None else views.mask_volume(who, keys, 'keys', torch.uint8, like=first))
     else:
         keys = first
-    lib = _on_device(who, first)
+    lib = views.on_device(who, first)
     dev, (X, Y, Z) = first.device, first.shape
     stream = _lib.stream_ptr(dev)
     ws_bytes = lib.ojf_volume_components_workspace_bytes(X, Y, Z)
@@ -89,11 +71,6 @@ def _band(who, band):
     return 1, band
 
 
-def _tsdf_pair(who, tsdf, weights):
-    tsdf = _volume(who, tsdf, 'tsdf', torch.float16)
-    return tsdf, _volume(who, weights, 'weights', torch.float16, like=tsdf)
-
-
 def observed_mask(tsdf, weights, band=None):
     """u8 [X,Y,Z] on the device: 1 where a voxel is observed - fp32(weight) > 0 and a TSDF value that is no NaN, the mesh
     extractor's rule (a NaN, negative or -0 weight is unobserved, the smallest subnormal observed) - and, with ``band``,
@@ -101,8 +78,8 @@ def observed_mask(tsdf, weights, band=None):
     carving projective fusion observes free space as well and needs one (its truncation)."""
     who = 'observed_mask'
     use_band, band = _band(who, band)
-    tsdf, weights = _tsdf_pair(who, tsdf, weights)
-    lib = _on_device(who, tsdf)
+    tsdf, weights = views.tsdf_pair(who, tsdf, weights)
+    lib = views.on_device(who, tsdf)
     mask = torch.empty(tsdf.shape, dtype=torch.uint8, device=tsdf.device)
     rc = lib.ojf_volume_observed_mask(_lib.ptr(tsdf.view(torch.int16)), _lib.ptr(weights.view(torch.int16)), tsdf.numel(), use_band, band,
                                       _lib.ptr(mask), _lib.stream_ptr(tsdf.device))
@@ -136,8 +113,8 @@ def remove_small_components(tsdf, weights, *, init_value, min_voxels=None, keep_
     keep_flags([], [], min_voxels, keep_largest, who)  # (the criteria, before anything is computed)
     connectivity = _connectivity(who, connectivity)
     _band(who, band)
-    tsdf, weights = _tsdf_pair(who, tsdf, weights)
-    lib = _on_device(who, tsdf)
+    tsdf, weights = views.tsdf_pair(who, tsdf, weights)
+    lib = views.on_device(who, tsdf)
     out = label_components(observed_mask(tsdf, weights, band), connectivity=connectivity)
     keep = keep_flags(out['sizes'], out['roots'], min_voxels, keep_largest, who)
     out['keep'] = keep
@@ -158,8 +135,8 @@ def instances(ids_volume, tsdf, weights, *, connectivity=6, min_voxels=1, band=N
     connectivity = _connectivity(who, connectivity)
     if isinstance(min_voxels, bool) or int(min_voxels) != min_voxels or min_voxels < 1:
         raise ValueError('{}: min_voxels must be an integer >= 1, got {!r}'.format(who, min_voxels))
-    tsdf, weights = _tsdf_pair(who, tsdf, weights)
-    ids_volume = _volume(who, ids_volume, 'ids', torch.uint8, like=tsdf)
+    tsdf, weights = views.tsdf_pair(who, tsdf, weights)
+    ids_volume = views.mask_volume(who, ids_volume, 'ids', torch.uint8, like=tsdf)
     c = label_components(observed_mask(tsdf, weights, band), ids_volume, connectivity=connectivity)
     keep = c['sizes'] >= int(min_voxels)
     ids = c['ids']

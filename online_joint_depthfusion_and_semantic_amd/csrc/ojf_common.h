@@ -35,7 +35,6 @@ struct Camera {
 
 Camera make_camera(const float *Ki, const float *E, const double *origin, double res);
 
-// fp16 bit pattern <-> fp32 (round-to-nearest-even on the way down, like torch .half())
 // Block b of a launch is observed to run on XCD b % 8 (8 XCDs with a private 4 MB L2 each).  For a 1-D grid that is a
 // multiple of 8 this renumbers the blocks so that every XCD works on ONE contiguous eighth of the range - for pixel
 // tiles: one band of the image, the same band in every kernel of the frame, so that what neighbouring tiles share and
@@ -81,6 +80,7 @@ __device__ __forceinline__ float4 split_planes4(const float4 &v)
                   __uint_as_float(split_lo_pair(h[1], v.z, v.w))};
 }
 
+// fp16 bit pattern <-> fp32 (round-to-nearest-even on the way down, like torch .half())
 __device__ __forceinline__ float h2f(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
 __device__ __forceinline__ uint16_t f2h(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
 

@@ -43,7 +43,7 @@
 //   flatten (comp_flatten_kernel), after the kernel boundary: labels[v] = find(v); a reader that meets a voxel already
 //     flattened meets an ancestor all the same.
 //   rank   : comp_count_kernel counts the roots (labels[v] == v) of every run of 1024 voxels, comp_scan_kernel makes the
-//     counts exclusive offsets (one block, the way of ojf_mesh.hip), comp_rank_kernel writes each root's rank at ids[root]
+//     counts exclusive offsets (one block: ojf_blocks.h), comp_rank_kernel writes each root's rank at ids[root]
 //     and comp_gather_kernel ids[v] = ids[labels[v]].
 //   list   : comp_list_kernel writes roots and keys and adds the brick-local figures to the entry of their component: at
 //     most one integer atomicAdd, three atomicMin and three atomicMax per brick-local component, never one per voxel (the
@@ -53,7 +53,7 @@
 //     extrema do not depend on their order or on who added what up.  The list phase reads only labels, ids, the keys
 //     and the workspace: it may run in a later call, with a list sized by the n the first call returned (capacity /
 //     count as in ojf_mesh_extract).
-#include "ojf_projview.h"
+#include "ojf_blocks.h"
 
 namespace ojf {
 
@@ -61,7 +61,6 @@ constexpr int kCBx = 4, kCBy = 4, kCBz = 64;       // the brick
 constexpr int kCBrick = kCBx * kCBy * kCBz;        // 1024 voxels
 constexpr int kCBlock = 256;                       // lanes per block, everywhere in this file
 constexpr int kCRun = 1024;                        // voxels per block of the root count / rank kernels
-constexpr int kCScan = 1024;
 
 #define OJF_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
@@ -250,31 +249,13 @@ __global__ __launch_bounds__(kCBlock) void comp_count_kernel(const int *labels, 
     if (threadIdx.x == 0) counts[blockIdx.x] = (uint32_t)n;
 }
 
-// exclusive prefix sum of counts[0..n) in place, the total to *total_ws and *count_out (ojf_mesh.hip's mesh_scan_kernel)
-__global__ __launch_bounds__(kCScan) void comp_scan_kernel(uint32_t *counts, uint32_t n, uint32_t *total_ws, uint32_t *count_out)
+// exclusive prefix sum of counts[0..n) in place, the total to *total_ws and *count_out
+__global__ __launch_bounds__(kScanBlock) void comp_scan_kernel(uint32_t *counts, uint32_t n, uint32_t *total_ws, uint32_t *count_out)
 {
-    __shared__ uint32_t part[kCScan];
-    const uint32_t chunk = (n + kCScan - 1) / kCScan;
-    const uint64_t lo = (uint64_t)threadIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
-    uint32_t sum = 0;
-    for (uint64_t i = lo; i < hi; ++i) sum += counts[i];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    for (int d = 1; d < kCScan; d <<= 1) {
-        const uint32_t add = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += add;
-        __syncthreads();
-    }
-    uint32_t run = part[threadIdx.x] - sum;
-    for (uint64_t i = lo; i < hi; ++i) {
-        const uint32_t c = counts[i];
-        counts[i] = run;
-        run += c;
-    }
-    if (threadIdx.x == kCScan - 1) {
-        *total_ws = part[kCScan - 1];
-        *count_out = part[kCScan - 1];
+    const uint32_t total = block_exclusive_scan<uint32_t>(counts, counts, n);
+    if (threadIdx.x == kScanBlock - 1) {
+        *total_ws = total;
+        *count_out = total;
     }
 }
 
@@ -428,8 +409,7 @@ __global__ __launch_bounds__(kCBlock) void comp_list_kernel(ListArgs a, uint32_t
 // ---- observed mask, removal --------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t observed(uint16_t t, uint16_t w, bool use_band, float band)
 {
-    const float tv = h2f(t);
-    return (h2f(w) > 0.0f && tv == tv && (!use_band || fabsf(tv) < band)) ? 1u : 0u;
+    return (voxel_observed(t, w) && (!use_band || fabsf(h2f(t)) < band)) ? 1u : 0u;
 }
 
 __global__ __launch_bounds__(kCBlock) void observed_mask_kernel(const uint16_t *tsdf, const uint16_t *wgt, size_t n, int use_band, float band,
@@ -440,14 +420,11 @@ __global__ __launch_bounds__(kCBlock) void observed_mask_kernel(const uint16_t *
     const bool aligned = (((uintptr_t)tsdf | (uintptr_t)wgt) & 15) == 0 && ((uintptr_t)mask & 7) == 0;
     const size_t nvec = aligned ? n / 8 : 0;
     for (size_t i = tid; i < nvec; i += step) {
-        const uint4 t8 = reinterpret_cast<const uint4 *>(tsdf)[i];
-        const uint4 w8 = reinterpret_cast<const uint4 *>(wgt)[i];
-        const uint32_t tw[4] = {t8.x, t8.y, t8.z, t8.w}, ww[4] = {w8.x, w8.y, w8.z, w8.w};
-        uint32_t out[2] = {0u, 0u};
+        uint32_t tq[4], wq[4], out[2] = {0u, 0u};
+        load8(tsdf, i, tq);
+        load8(wgt, i, wq);
 #pragma unroll
-        for (int k = 0; k < 8; ++k)
-            out[k >> 2] |= observed((uint16_t)(tw[k >> 1] >> (16 * (k & 1))), (uint16_t)(ww[k >> 1] >> (16 * (k & 1))), use_band != 0, band)
-                           << (8 * (k & 3));
+        for (int e = 0; e < 8; ++e) set8(out, e, observed((uint16_t)get16(tq, e), (uint16_t)get16(wq, e), use_band != 0, band));
         reinterpret_cast<uint2 *>(mask)[i] = make_uint2(out[0], out[1]);
     }
     for (size_t i = nvec * 8 + tid; i < n; i += step) mask[i] = (uint8_t)observed(tsdf[i], wgt[i], use_band != 0, band);
@@ -469,18 +446,11 @@ __global__ __launch_bounds__(kCBlock) void components_apply_kernel(const int *id
 
 static inline uint32_t comp_runs(uint32_t total) { return (total + kCRun - 1) / kCRun; }
 
-static inline int comp_stream_grid(size_t work_items)
-{
-    size_t blocks = (work_items + kCBlock - 1) / kCBlock;
-    if (blocks > 2048) blocks = 2048;  // 256 CUs x 8 resident blocks, grid-stride the rest (ojf_volume.hip)
-    return blocks ? (int)blocks : 1;
-}
-
 }  // namespace ojf
 
 OJF_API size_t ojf_volume_components_workspace_bytes(int X, int Y, int Z)
 {
-    if (X <= 0 || Y <= 0 || Z <= 0 || (int64_t)X * Y * Z > 0x7fffffffLL) return 0;
+    if (!ojf::volume_size_ok(X, Y, Z)) return 0;
     const uint32_t total = (uint32_t)((int64_t)X * Y * Z);
     // the brick-local figures (i32 per voxel), the root counts / offsets (u32 per run of 1024 voxels), n (u32), to 8 bytes
     return (((size_t)total + ojf::comp_runs(total) + 1) * sizeof(uint32_t) + 7) & ~(size_t)7;
@@ -532,7 +502,7 @@ OJF_API int ojf_volume_components(const uint8_t *mask, const uint8_t *keys, int 
     }
     if (phases & OJF_COMPONENTS_RANK) {
         hipLaunchKernelGGL(comp_count_kernel, dim3(runs), block, 0, s, labels, total, counts);
-        hipLaunchKernelGGL(comp_scan_kernel, dim3(1), dim3(kCScan), 0, s, counts, runs, n_ws, count);
+        hipLaunchKernelGGL(comp_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, counts, runs, n_ws, count);
         hipLaunchKernelGGL(comp_rank_kernel, dim3(runs), block, 0, s, labels, total, counts, ids);
         hipLaunchKernelGGL(comp_gather_kernel, per_voxel, block, 0, s, labels, total, ids);
         OJF_HIP(hipGetLastError());
@@ -544,7 +514,7 @@ OJF_API int ojf_volume_components(const uint8_t *mask, const uint8_t *keys, int 
         l.roots = roots; l.sizes = sizes; l.boxes = boxes; l.keys_out = list_keys; l.cap = capacity;
         const uint32_t cap_blocks = (uint32_t)(((uint64_t)(capacity < total ? capacity : total) + kCBlock - 1) / kCBlock);
         hipLaunchKernelGGL(comp_list_init_kernel, dim3(cap_blocks), block, 0, s, l);
-        hipLaunchKernelGGL(comp_list_kernel, dim3(comp_stream_grid(total)), block, 0, s, l, total);
+        hipLaunchKernelGGL(comp_list_kernel, dim3(stream_grid(total, kCBlock)), block, 0, s, l, total);
         OJF_HIP(hipGetLastError());
     }
     return 0;
@@ -559,7 +529,7 @@ OJF_API int ojf_volume_observed_mask(const uint16_t *tsdf, const uint16_t *wgt, 
     if (n == 0 || n > 0x7fffffffULL) return refuse(who, "the voxel count must be in 1..2^31-1");
     if (use_band && !(band > 0.0f)) return refuse(who, "band must be > 0 (a NaN is refused)");
     if (((uintptr_t)tsdf & 1) || ((uintptr_t)wgt & 1)) return refuse(who, "tsdf_dev and weights_dev must be 2-byte aligned");
-    hipLaunchKernelGGL(observed_mask_kernel, dim3(comp_stream_grid(n / 8 + 1)), dim3(kCBlock), 0, as_stream(stream), tsdf, wgt, n, use_band, band,
+    hipLaunchKernelGGL(observed_mask_kernel, dim3(stream_grid(n / 8 + 1, kCBlock)), dim3(kCBlock), 0, as_stream(stream), tsdf, wgt, n, use_band, band,
                        mask);
     OJF_HIP(hipGetLastError());
     return 0;
@@ -577,7 +547,7 @@ OJF_API int ojf_volume_components_apply(const int32_t *ids, const uint8_t *keep,
     const _Float16 hv = (_Float16)init_value;
     uint16_t bits;
     __builtin_memcpy(&bits, &hv, 2);
-    hipLaunchKernelGGL(components_apply_kernel, dim3(comp_stream_grid(n)), dim3(kCBlock), 0, as_stream(stream), ids, keep, n_components, tsdf, wgt,
+    hipLaunchKernelGGL(components_apply_kernel, dim3(stream_grid(n, kCBlock)), dim3(kCBlock), 0, as_stream(stream), ids, keep, n_components, tsdf, wgt,
                        n, bits);
     OJF_HIP(hipGetLastError());
     return 0;

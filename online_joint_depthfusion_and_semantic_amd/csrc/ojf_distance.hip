@@ -43,7 +43,7 @@
 //     y pass nearest -> workspace, the x pass workspace -> nearest - since a gather may read a voxel another lane rewrites.
 //   finish (surface_mask_kernel, esdf_kernel): streaming, one lane per 8 consecutive voxels with 16-byte loads of the fp16
 //     volumes where the pointers (and for the mask, the z rows) allow it, one voxel per lane otherwise.
-#include "ojf_projview.h"
+#include "ojf_blocks.h"
 
 namespace ojf {
 
@@ -158,18 +158,7 @@ __global__ __launch_bounds__(kDLineBlock) void edt_line_kernel(LineArgs a)
 // ---- surface mask, ESDF --------------------------------------------------------------------------------------------------
 // 0: unobserved, 1: observed and outside, 2: observed and inside; two voxels face each other across the surface when the
 // exclusive or of their states is 3
-__device__ __forceinline__ uint32_t surf_state(uint16_t t, uint16_t w)
-{
-    const float tv = h2f(t);
-    if (!(h2f(w) > 0.0f && tv == tv)) return 0u;
-    return tv < 0.0f ? 2u : 1u;
-}
-
-__device__ __forceinline__ void load8(const uint16_t *p, size_t group, uint32_t q[4])
-{
-    const uint4 v = reinterpret_cast<const uint4 *>(p)[group];
-    q[0] = v.x; q[1] = v.y; q[2] = v.z; q[3] = v.w;
-}
+__device__ __forceinline__ uint32_t surf_state(uint16_t t, uint16_t w) { return voxel_observed(t, w) ? (h2f(t) < 0.0f ? 2u : 1u) : 0u; }
 
 __global__ __launch_bounds__(kDBlock) void surface_mask_kernel(const uint16_t *tsdf, const uint16_t *wgt, int X, int Y, int Z, uint8_t *mask)
 {
@@ -257,18 +246,12 @@ __global__ __launch_bounds__(kDBlock) void esdf_kernel(const int *dist2, const u
     for (size_t i = nvec * 8 + tid; i < n; i += step) esdf[i] = esdf_value(dist2[i], tsdf[i], wgt[i], res, far);
 }
 
-static inline int dist_stream_grid(size_t work_items)
-{
-    size_t blocks = (work_items + kDBlock - 1) / kDBlock;
-    if (blocks > 2048) blocks = 2048;  // 256 CUs x 8 resident blocks, grid-stride the rest (ojf_volume.hip)
-    return blocks ? (int)blocks : 1;
-}
+static inline bool edt_dims_ok(int X, int Y, int Z) { return X >= 1 && Y >= 1 && Z >= 1 && X <= kDMaxDim && Y <= kDMaxDim && Z <= kDMaxDim; }
 
 static inline int check_edt_size(const char *who, int X, int Y, int Z)
 {
-    if (X < 1 || Y < 1 || Z < 1 || X > kDMaxDim || Y > kDMaxDim || Z > kDMaxDim) return refuse(who, "X, Y and Z must be in 1..2048");
-    if ((int64_t)X * Y * Z > 0x7fffffffLL) return refuse(who, "volume too large");
-    return 0;
+    if (!edt_dims_ok(X, Y, Z)) return refuse(who, "X, Y and Z must be in 1..2048");
+    return check_volume_size(who, X, Y, Z);
 }
 
 static int launch_line_pass(int L, int outer, uint32_t stride, uint32_t outer_stride, int Z, uint32_t lim, int *dist2, const int *near_in,
@@ -300,7 +283,7 @@ static int launch_line_pass(int L, int outer, uint32_t stride, uint32_t outer_st
 
 OJF_API size_t ojf_volume_edt_workspace_bytes(int X, int Y, int Z)
 {
-    if (X < 1 || Y < 1 || Z < 1 || X > ojf::kDMaxDim || Y > ojf::kDMaxDim || Z > ojf::kDMaxDim || (int64_t)X * Y * Z > 0x7fffffffLL) return 0;
+    if (!ojf::edt_dims_ok(X, Y, Z) || !ojf::volume_size_ok(X, Y, Z)) return 0;
     return ((size_t)X * Y * Z * sizeof(int32_t) + 7) & ~(size_t)7;  // the index array the y pass writes and the x pass reads
 }
 
@@ -339,7 +322,7 @@ OJF_API int ojf_volume_surface_mask(const uint16_t *tsdf, const uint16_t *wgt, i
     if (int rc = check_edt_size(who, X, Y, Z)) return rc;
     if (((uintptr_t)tsdf & 1) || ((uintptr_t)wgt & 1)) return refuse(who, "tsdf_dev and weights_dev must be 2-byte aligned");
     const size_t n = (size_t)X * Y * Z;
-    hipLaunchKernelGGL(surface_mask_kernel, dim3(dist_stream_grid((Z & 7) ? n : n / 8)), dim3(kDBlock), 0, as_stream(stream), tsdf, wgt, X, Y, Z,
+    hipLaunchKernelGGL(surface_mask_kernel, dim3(stream_grid((Z & 7) ? n : n / 8, kDBlock)), dim3(kDBlock), 0, as_stream(stream), tsdf, wgt, X, Y, Z,
                        mask);
     OJF_HIP(hipGetLastError());
     return 0;
@@ -356,7 +339,7 @@ OJF_API int ojf_volume_esdf(const int32_t *dist2, const uint16_t *tsdf, const ui
     if (!(far >= 0.0f)) return refuse(who, "far must be >= 0 (a NaN is refused)");
     if (((uintptr_t)dist2 & 3) || ((uintptr_t)esdf & 3) || ((uintptr_t)tsdf & 1) || ((uintptr_t)wgt & 1))
         return refuse(who, "dist2_dev and esdf_dev must be 4-byte, the volumes 2-byte aligned");
-    hipLaunchKernelGGL(esdf_kernel, dim3(dist_stream_grid(n / 8 + 1)), dim3(kDBlock), 0, as_stream(stream), dist2, tsdf, wgt, n, resolution, far,
+    hipLaunchKernelGGL(esdf_kernel, dim3(stream_grid(n / 8 + 1, kDBlock)), dim3(kDBlock), 0, as_stream(stream), dist2, tsdf, wgt, n, resolution, far,
                        esdf);
     OJF_HIP(hipGetLastError());
     return 0;

@@ -14,7 +14,7 @@
 // Vertices are origin + voxel_index * resolution; with origin = 0 that is the frame of the reference's meshes
 // (marching_cubes(..., spacing=voxel_size), modules/database.py:120-122).  Triangles are oriented so that the
 // normal points from the negative (inside) to the positive (free space) side.
-#include "ojf_common.h"
+#include "ojf_blocks.h"
 
 namespace ojf {
 
@@ -210,27 +210,10 @@ __global__ __launch_bounds__(kTileZ * kTileY) void mesh_kernel(MeshArgs a)
 
 // exclusive prefix sum of blocks[0..n) in place, total to *count.  One workgroup: the list is (cells / 256) long,
 // 65 K entries for a 256^3 volume.
-__global__ __launch_bounds__(1024) void mesh_scan_kernel(unsigned int *blocks, unsigned int n, unsigned int *count)
+__global__ __launch_bounds__(kScanBlock) void mesh_scan_kernel(unsigned int *blocks, unsigned int n, unsigned int *count)
 {
-    __shared__ unsigned int part[1024];
-    const unsigned int chunk = (n + 1023) / 1024, lo = threadIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
-    unsigned int sum = 0;
-    for (unsigned int i = lo; i < hi; ++i) sum += blocks[i];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const unsigned int add = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += add;
-        __syncthreads();
-    }
-    unsigned int run = part[threadIdx.x] - sum;
-    for (unsigned int i = lo; i < hi; ++i) {
-        const unsigned int c = blocks[i];
-        blocks[i] = run;
-        run += c;
-    }
-    if (threadIdx.x == 1023) *count = part[1023];
+    const uint32_t total = block_exclusive_scan<uint32_t>(blocks, blocks, n);
+    if (threadIdx.x == kScanBlock - 1) *count = total;
 }
 
 // F-score support: hit[i] = 1 when some point of a cell-sorted set lies within tau of query i.  The set is binned on
@@ -324,7 +307,7 @@ OJF_API int ojf_mesh_extract(const uint16_t *tsdf, const uint16_t *wgt, const ui
     hipStream_t st = as_stream(stream);
     const dim3 block(kTileZ, kTileY);
     hipLaunchKernelGGL(mesh_kernel<false>, grid, block, 0, st, a);
-    hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(1024), 0, st, a.blocks, (unsigned int)n_blocks, count);
+    hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(kScanBlock), 0, st, a.blocks, (unsigned int)n_blocks, count);
     if (capacity) hipLaunchKernelGGL(mesh_kernel<true>, grid, block, 0, st, a);
     return check_hip(hipGetLastError(), "mesh_kernel launch");
 }

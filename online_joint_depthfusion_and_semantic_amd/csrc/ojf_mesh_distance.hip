@@ -40,7 +40,7 @@
 //     bricks.  Up to 8 bricks the lane visits them itself; more (a wall that spans thousands of bricks) are taken one
 //     triangle at a time by the whole wave (a loop over __ballot, the triangle re-read from its lane), which also drops the
 //     bricks whose centre is farther from the triangle's plane than R + the brick's half diagonal (f64).  Counting adds 1
-//     to the brick's u32 counter (integer atomicAdd); mesh_scan_kernel turns counts into exclusive offsets and the total
+//     to the brick's u32 counter (integer atomicAdd); mesh_pairs_scan_kernel turns counts into exclusive offsets and the total
 //     number of (triangle, brick) pairs; filling writes the face index at an atomic cursor.  The order inside a brick's
 //     list is whatever the atomics give; it shows in no output, because the minimum of the keys does not depend on it.
 //   distance (mesh_distance_kernel): one workgroup of 256 lanes per brick, each lane owns two voxels (x and x + 4) and keeps
@@ -71,7 +71,7 @@
 // that d² > L: the triangle neither reaches the voxel nor wins or ties its key.  This is reasoning about magnitudes,
 // not a proof; the GPU tests compare with the bin-free, bound-free reference on meshes with zero-area, sliver, far-away
 // and box-spanning triangles, at bands from a fraction of a voxel to more than the box.
-#include "ojf_projview.h"
+#include "ojf_blocks.h"
 
 namespace ojf {
 
@@ -81,7 +81,6 @@ constexpr int kChunk = 128;         // triangles staged through LDS at a time
 constexpr int kTriWords = 32;       // words of one staged triangle (TriPrep, the face index, the widened bounding box)
 constexpr int kBinBlock = 256;
 constexpr int kLaneBricks = 8;      // brick boxes up to this many bricks are visited by the triangle's own lane
-constexpr int kScanBlock = 1024;
 constexpr double kSlack = 1.0 / 262144.0;  // 2^-18 (the header's c·eps)
 constexpr float kVoxelSlack = 1.0f / 65536.0f;  // 2^-16: the header's sv over (G + D + band)
 constexpr double kBrickRadius = 6.07;      // > 3.5·sqrt(3): from a brick's centre to its farthest voxel centre, in voxels
@@ -108,17 +107,6 @@ struct TriPrep {  // what the distance needs of one triangle (the header's names
     float ee[3];
 };
 
-__device__ __forceinline__ float dot3(const float u[3], const float v[3]) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
-
-__device__ __forceinline__ void mcross3(const float u[3], const float v[3], float o[3])
-{
-    o[0] = u[1] * v[2] - u[2] * v[1];
-    o[1] = u[2] * v[0] - u[0] * v[2];
-    o[2] = u[0] * v[1] - u[1] * v[0];
-}
-
-__device__ __forceinline__ bool mfinite3(const float p[3]) { return fabsf(p[0]) < INFINITY && fabsf(p[1]) < INFINITY && fabsf(p[2]) < INFINITY; }
-
 // Face f of the mesh: false for a skipped face, else its vertices and their indices.
 __device__ __forceinline__ bool load_face(const MeshRef &M, int f, float P[3][3], int idx[3])
 {
@@ -128,7 +116,7 @@ __device__ __forceinline__ bool load_face(const MeshRef &M, int f, float P[3][3]
     for (int i = 0; i < 3; ++i) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) P[i][k] = M.vertices[3 * (size_t)idx[i] + k];
-        if (!mfinite3(P[i])) return false;
+        if (!finite3(P[i])) return false;
     }
     return true;
 }
@@ -144,7 +132,7 @@ __device__ __forceinline__ void prepare_triangle(const float P[3][3], TriPrep &T
         T.e2[m] = P[0][m] - P[2][m];
         ac[m] = P[2][m] - P[0][m];
     }
-    mcross3(T.e0, ac, T.n);
+    cross3(T.e0, ac, T.n);
     T.nn = dot3(T.n, T.n);
     T.ee[0] = dot3(T.e0, T.e0);
     T.ee[1] = dot3(T.e1, T.e1);
@@ -190,11 +178,11 @@ __device__ __forceinline__ void closest_feature(const float p[3], const TriPrep 
     C.h = dot3(w0, T.n);
     if (T.nn > 0.0f) {
         float x[3];
-        mcross3(T.e0, w0, x);
+        cross3(T.e0, w0, x);
         const float f0 = dot3(x, T.n);
-        mcross3(T.e1, w1, x);
+        cross3(T.e1, w1, x);
         const float f1 = dot3(x, T.n);
-        mcross3(T.e2, w2, x);
+        cross3(T.e2, w2, x);
         const float f2 = dot3(x, T.n);
         if (f0 >= 0.0f && f1 >= 0.0f && f2 >= 0.0f) {
             const float s3 = (C.h * C.h) / T.nn;
@@ -335,35 +323,15 @@ __global__ __launch_bounds__(kBinBlock) void mesh_bin_kernel(BinLaunch L)
     }
 }
 
-// counts -> exclusive offsets (and the fill's cursors), the total to total_ws and *count_out.  One block: lane t sums its
-// run of the counters, the runs' sums are scanned in LDS, lane t writes its run's offsets.  Offsets are u32: a total
-// of 2^32 pairs or more wraps them (the entry point's callers see the total and refuse; the lists stay inside cap).
-__global__ __launch_bounds__(kScanBlock) void mesh_scan_kernel(const uint32_t *counts, uint32_t nb, uint32_t *offsets,
-                                                               unsigned long long *total_ws, unsigned long long *count_out)
+// counts -> exclusive offsets (and the fill's cursors), the total to total_ws and *count_out.  Sums are u64, offsets u32: a
+// total of 2^32 pairs or more wraps them (the entry point's callers see the total and refuse; the lists stay inside cap).
+__global__ __launch_bounds__(kScanBlock) void mesh_pairs_scan_kernel(const uint32_t *counts, uint32_t nb, uint32_t *offsets,
+                                                                     unsigned long long *total_ws, unsigned long long *count_out)
 {
-    __shared__ unsigned long long sums[kScanBlock];
-    const uint32_t t = threadIdx.x;
-    const uint32_t per = (nb + kScanBlock - 1) / kScanBlock;
-    const uint64_t first = (uint64_t)t * per;
-    const uint64_t last = first + per < nb ? first + per : nb;
-    unsigned long long s = 0;
-    for (uint64_t i = first; i < last; ++i) s += counts[i];
-    sums[t] = s;
-    __syncthreads();
-    for (uint32_t step = 1; step < kScanBlock; step <<= 1) {
-        const unsigned long long v = t >= step ? sums[t - step] : 0;
-        __syncthreads();
-        sums[t] += v;
-        __syncthreads();
-    }
-    unsigned long long run = sums[t] - s;  // exclusive
-    for (uint64_t i = first; i < last; ++i) {
-        offsets[i] = (uint32_t)run;
-        run += counts[i];
-    }
-    if (t == kScanBlock - 1) {
-        *total_ws = sums[t];
-        if (count_out) *count_out = sums[t];
+    const unsigned long long total = block_exclusive_scan<unsigned long long>(counts, offsets, nb);
+    if (threadIdx.x == kScanBlock - 1) {
+        *total_ws = total;
+        if (count_out) *count_out = total;
     }
 }
 
@@ -573,7 +541,7 @@ static size_t mesh_bricks(int X, int Y, int Z)
 
 OJF_API size_t ojf_mesh_distance_workspace_bytes(int X, int Y, int Z)
 {
-    if (X <= 0 || Y <= 0 || Z <= 0 || (int64_t)X * Y * Z > 0x7fffffffLL) return 0;
+    if (!ojf::volume_size_ok(X, Y, Z)) return 0;
     // counts, offsets, cursors (u32 per brick), rounded up to 8 bytes; the total (u64)
     return ((3 * ojf::mesh_bricks(X, Y, Z) * sizeof(uint32_t) + 7) & ~(size_t)7) + sizeof(uint64_t);
 }
@@ -616,7 +584,7 @@ OJF_API int ojf_mesh_distance(const float *vertices, int nv, const int *faces, i
         OJF_HIP(hipGetLastError());
     }
     if (phases & OJF_MESH_DISTANCE_SCAN) {
-        hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, counts, (uint32_t)nb, offsets, total,
+        hipLaunchKernelGGL(mesh_pairs_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, counts, (uint32_t)nb, offsets, total,
                            reinterpret_cast<unsigned long long *>(count));
         OJF_HIP(hipGetLastError());
     }

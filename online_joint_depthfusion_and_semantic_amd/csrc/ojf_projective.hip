@@ -62,19 +62,10 @@ struct ProjLaunch {
     ProjView v[OJF_PROJECTIVE_MAX_VIEWS];
 };
 
-// element e of 8-bit values packed into 32-bit registers (16-bit: ojf_projview.h); e is a constant after unrolling
-__device__ __forceinline__ uint32_t get8(const uint32_t *q, int e) { return (q[e >> 2] >> ((e & 3) * 8)) & 0xffu; }
-__device__ __forceinline__ void set8(uint32_t *q, int e, uint32_t v)
-{
-    const int sh = (e & 3) * 8;
-    q[e >> 2] = (q[e >> 2] & ~(0xffu << sh)) | (v << sh);
-}
-
 __device__ __forceinline__ void load16x8(const uint16_t *p, bool vec, int cnt, uint32_t q[4])
 {
     if (vec) {
-        const uint4 r = *reinterpret_cast<const uint4 *>(p);
-        q[0] = r.x; q[1] = r.y; q[2] = r.z; q[3] = r.w;
+        load8(p, 0, q);
     } else {
 #pragma unroll
         for (int e = 0; e < kProjGroup; ++e)

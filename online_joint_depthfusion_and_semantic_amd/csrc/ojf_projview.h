@@ -2,12 +2,9 @@
 // host prepares in f64 and steps 1-3 of the definition in ojf_projective.hip's header - voxel -> camera point -> nearest
 // pixel -> depth and mask tests.  One text for all kernels, so that colour and label votes land in exactly the voxels the
 // depth of the same frame reaches.  The operation order is normative (see there); nothing here may be re-associated.
-// The host checks at the end are also what the other volume operators ask of a box (check_volume_size, all_finite).
+// The packed lanes and the host checks of a box that the sweeps use are in ojf_blocks.h, shared with the other operators.
 #pragma once
-#include "ojf_common.h"
-
-#include <math.h>
-#include <cmath>
+#include "ojf_blocks.h"
 
 namespace ojf {
 
@@ -23,14 +20,6 @@ struct ProjImages {  // the depth images of a call and what bounds a projection 
     int h, w;
     float near, cmax, rmax;  // cmax = w - 1, rmax = h - 1
 };
-
-// element e of 16-bit values packed into 32-bit registers; e is a constant after unrolling
-__device__ __forceinline__ uint32_t get16(const uint32_t *q, int e) { return (q[e >> 1] >> ((e & 1) * 16)) & 0xffffu; }
-__device__ __forceinline__ void set16(uint32_t *q, int e, uint32_t v)
-{
-    const int sh = (e & 1) * 16;
-    q[e >> 1] = (q[e >> 1] & ~(0xffffu << sh)) | (v << sh);
-}
 
 // voxel indices, as floats, of `count` consecutive elements of the flattened [X,Y,Z] volume from `first` on (a group may
 // run over the end of a z row)
@@ -72,21 +61,6 @@ __device__ __forceinline__ bool project_depth(const ProjView &V, const ProjImage
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
-static inline bool all_finite(const double *p, int n)
-{
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(p[i])) return false;
-    return true;
-}
-
-// What every entry point asks of an [X,Y,Z] box: positive sizes and a voxel count a 31-bit index reaches; 0 or refuse(who, ...).
-static inline int check_volume_size(const char *who, int X, int Y, int Z)
-{
-    if (X <= 0 || Y <= 0 || Z <= 0) return refuse(who, "non-positive volume size");
-    if ((int64_t)X * Y * Z > 0x7fffffffLL) return refuse(who, "volume too large");
-    return 0;
-}
-
 // What the sweeps' entry points ask of their volume, images and cameras; 0 or refuse(who, ...).
 static inline int check_projective_views(const char *who, int X, int Y, int Z, const double *origin, double res, int n,
                                          int max_views, const double *K, const double *E, int h, int w, float max_weight,

@@ -55,7 +55,7 @@
 // edge i.  `est` is four times that with eps = 2^-24; up to est = 0.5 the one-pixel widening covers it, beyond it the box
 // grows by ceil(est) pixels (a degenerate triangle ends at the whole image).  This is reasoning about magnitudes, not a
 // proof; the GPU tests compare with the box-free reference on meshes with sub-pixel, zero-area and edge-on triangles.
-#include "ojf_projview.h"
+#include "ojf_blocks.h"
 
 namespace ojf {
 
@@ -92,15 +92,6 @@ struct RasterTri {  // what the pixel test needs of one triangle
     float n0[3], n1[3], n2[3];
     float det;
 };
-
-__device__ __forceinline__ void cross3(const float u[3], const float v[3], float o[3])
-{
-    o[0] = u[1] * v[2] - u[2] * v[1];
-    o[1] = u[2] * v[0] - u[0] * v[2];
-    o[2] = u[0] * v[1] - u[1] * v[0];
-}
-
-__device__ __forceinline__ bool finite3(const float p[3]) { return fabsf(p[0]) < INFINITY && fabsf(p[1]) < INFINITY && fabsf(p[2]) < INFINITY; }
 
 __device__ __forceinline__ void camera_point(const RasterView &V, const float P[3], float a[3])
 {

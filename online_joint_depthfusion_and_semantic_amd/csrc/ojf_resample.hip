@@ -60,7 +60,7 @@
 // one lane; a wave is 16 or 64 voxels of a 4 x 16 tile.  The chunk that holds Cw and padding behind it goes element by
 // element, which keeps the padding unread and unwritten; so does everything of a colour volume off the 8-byte grid.
 // Record indexing is 64-bit.
-#include "ojf_projview.h"
+#include "ojf_blocks.h"
 
 #include <cmath>
 
@@ -229,8 +229,7 @@ struct ResampleRecords {
 __device__ __forceinline__ void load_chunk(const uint16_t *p, int n, int CH, bool vec, uint32_t q[4])
 {
     if (vec && CH == 8) {
-        const uint4 r = *reinterpret_cast<const uint4 *>(p);
-        q[0] = r.x; q[1] = r.y; q[2] = r.z; q[3] = r.w;
+        load8(p, 0, q);
     } else if (vec) {
         const uint2 r = *reinterpret_cast<const uint2 *>(p);
         q[0] = r.x; q[1] = r.y; q[2] = 0; q[3] = 0;
@@ -371,7 +370,7 @@ static bool is_whole_voxel_map(const ResampleMap &P)
 static int resample_tiles(const char *who, ResampleMap &P, int XL, int YL, int ZL, uint32_t &blocks)
 {
     const int64_t nx = (P.dX + XL - 1) / XL, ny = (P.dY + YL - 1) / YL, nz = (P.dZ + ZL - 1) / ZL;
-    if (nx * ny * nz > 0x7fffffffLL) return refuse(who, "volume too large");
+    if (!volume_size_ok(nx, ny, nz)) return refuse(who, "volume too large");
     P.ny = (uint32_t)ny; P.nz = (uint32_t)nz;
     blocks = (uint32_t)(nx * ny * nz);
     return 0;

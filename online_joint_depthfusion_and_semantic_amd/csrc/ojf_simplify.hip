@@ -9,7 +9,7 @@
 // kernel boundary, no thread waits for another workgroup:
 //   MARK        per vertex: cell index and local position (1/256 cell around the cell centre, packed 3 x 9 bits), and the
 //               cell's bit in a bitmap (atomicOr; one BIT per cell: 256^3 cells are 2 MB).
-//   SCAN        exclusive prefix of the per-word popcounts (one workgroup, the form of ojf_mesh.hip's scan), counts[0] = the
+//   SCAN        exclusive prefix of the per-word popcounts (one workgroup: ojf_blocks.h's block_exclusive_scan), counts[0] = the
 //               number of occupied cells = output vertices; then per vertex cluster = prefix[word] + popcount(bits below).
 //   COUNT       per block of 256 faces the number of kept faces, the same scan over the blocks, counts[1] = kept faces.
 //   ACCUMULATE  128-byte accumulator row per cluster, zeroed; per occupied cell its index into the row; per vertex S += p,
@@ -26,7 +26,7 @@
 // Overflow: |p| <= 2^7, |n| <= 2^9, 1 <= w <= 2^10, so |d| = |n.p| <= 3 2^16, one term of b is at most
 // 2^10 3 2^16 2^9 = 3 2^35 and one of A at most 2^10 2^18 = 2^28.  A face is added once per corner: at most 3 2^24 incidences
 // in all, hence |b| <= 9 2^59 < 2^63 and |A| <= 3 2^52; |S| <= 2^7 nv < 2^38.  The static_asserts below repeat this.
-#include "ojf_common.h"
+#include "ojf_blocks.h"
 
 #include <math.h>
 
@@ -110,30 +110,17 @@ __global__ __launch_bounds__(kSBlock) void simplify_mark_kernel(SimplifyArgs a)
     if (word >= 0 && (lane == 63 || next != word)) atomicOr(&a.bitmap[word], bits);
 }
 
-// exclusive prefix sum of n values into out (in == out allowed), total to *total.  One workgroup, every thread a contiguous
-// chunk: ojf_mesh.hip's mesh_scan_kernel.  BITS: the values are the popcounts of the words of in.
-template <bool BITS>
-__global__ __launch_bounds__(1024) void simplify_scan_kernel(const uint32_t *in, uint32_t *out, uint32_t n, uint32_t *total)
+struct ScanPopcount {
+    __device__ __forceinline__ uint32_t operator()(uint32_t v) const { return (uint32_t)__popc(v); }
+};
+
+// exclusive prefix sum of n values into out (in == out allowed), total to *total.  Value = ScanPopcount: the values are the
+// popcounts of the words of in.
+template <typename Value>
+__global__ __launch_bounds__(kScanBlock) void simplify_scan_kernel(const uint32_t *in, uint32_t *out, uint32_t n, uint32_t *total)
 {
-    __shared__ uint32_t part[1024];
-    const uint32_t chunk = (n + 1023) / 1024, lo = threadIdx.x * chunk < n ? threadIdx.x * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
-    uint32_t sum = 0;
-    for (uint32_t i = lo; i < hi; ++i) sum += BITS ? (uint32_t)__popc(in[i]) : in[i];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const uint32_t add = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += add;
-        __syncthreads();
-    }
-    uint32_t run = part[threadIdx.x] - sum;
-    for (uint32_t i = lo; i < hi; ++i) {
-        const uint32_t c = BITS ? (uint32_t)__popc(in[i]) : in[i];
-        out[i] = run;
-        run += c;
-    }
-    if (threadIdx.x == 1023) *total = part[1023];
+    const uint32_t sum = block_exclusive_scan<uint32_t, Value>(in, out, n);
+    if (threadIdx.x == kScanBlock - 1) *total = sum;
 }
 
 __global__ __launch_bounds__(kSBlock) void simplify_rank_kernel(SimplifyArgs a)
@@ -461,13 +448,13 @@ OJF_API int ojf_mesh_simplify(const float *vertices, int nv, const int32_t *face
         OJF_HIP(hipGetLastError());
     }
     if (phases & OJF_SIMPLIFY_SCAN) {
-        hipLaunchKernelGGL(simplify_scan_kernel<true>, dim3(1), dim3(1024), 0, s, a.bitmap, a.prefix, a.words, counts);
+        hipLaunchKernelGGL(simplify_scan_kernel<ScanPopcount>, dim3(1), dim3(kScanBlock), 0, s, a.bitmap, a.prefix, a.words, counts);
         hipLaunchKernelGGL(simplify_rank_kernel, vgrid, block, 0, s, a);
         OJF_HIP(hipGetLastError());
     }
     if (phases & OJF_SIMPLIFY_COUNT) {
         if (nf) hipLaunchKernelGGL(simplify_faces_kernel<false>, fgrid, block, 0, s, a);
-        hipLaunchKernelGGL(simplify_scan_kernel<false>, dim3(1), dim3(1024), 0, s, a.fblocks, a.fblocks, a.fblocks_n, counts + 1);
+        hipLaunchKernelGGL(simplify_scan_kernel<ScanIdentity>, dim3(1), dim3(kScanBlock), 0, s, a.fblocks, a.fblocks, a.fblocks_n, counts + 1);
         OJF_HIP(hipGetLastError());
     }
     if (phases & OJF_SIMPLIFY_ACCUMULATE) {

@@ -1,16 +1,8 @@
 // Full-grid passes of the Database (modules/database.py:108-112, 351-370; utils/metrics.py:111-127).
 // Pure streaming kernels: 16-byte accesses per lane, grid-stride, bandwidth roofline.
-#include "ojf_common.h"
+#include "ojf_blocks.h"
 
 namespace ojf {
-
-static inline int stream_grid(size_t work_items)
-{
-    size_t blocks = (work_items + 255) / 256;
-    if (blocks > 2048) blocks = 2048;  // 256 CUs x 8 resident blocks, grid-stride the rest
-    if (blocks == 0) blocks = 1;
-    return (int)blocks;
-}
 
 __global__ __launch_bounds__(256) void fill_u16_kernel(uint16_t *v, size_t n, uint16_t bits)
 {

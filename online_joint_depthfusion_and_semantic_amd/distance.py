@@ -10,8 +10,7 @@ import math
 
 import torch
 
-from . import _lib
-from .components import _tsdf_pair, _volume
+from . import _lib, views
 
 MAX_DIM = 2048  # csrc/ojf_distance.hip: kDMaxDim
 NONE = _lib.EDT_NONE
@@ -27,18 +26,9 @@ def _radius2(who, name, radius, unit=1.0):
     return int(min(math.floor(r * r), 2 ** 24))  # (d² < 2^24 in every volume: 2^24 is as good as unlimited)
 
 
-def _on_device(who, vol):
-    if not vol.is_cuda:
-        raise ValueError('{}: the volumes must be cuda tensors'.format(who))
-    if min(vol.shape) < 1 or max(vol.shape) > MAX_DIM or vol.numel() >= 2 ** 31:
-        raise ValueError('{}: 1 <= X, Y, Z <= {} and X·Y·Z < 2^31 expected, got shape {}'.format(who, MAX_DIM, tuple(vol.shape)))
-    _lib.require_gpu()
-    return _lib.load()
-
-
 def _edt(who, seeds, max_dist2):
-    seeds = _volume(who, seeds, 'seeds', torch.uint8)
-    lib = _on_device(who, seeds)
+    seeds = views.mask_volume(who, seeds, 'seeds', torch.uint8)
+    lib = views.on_device(who, seeds, MAX_DIM)
     dev, (X, Y, Z) = seeds.device, seeds.shape
     ws_bytes = lib.ojf_volume_edt_workspace_bytes(X, Y, Z)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
@@ -75,8 +65,8 @@ def surface_mask(tsdf, weights):
     face neighbour on the other side of the surface - inside is fp32(tsdf) < 0, so both zeros are outside.  The voxels on
     either side of every observed zero crossing: the seeds of the ESDF."""
     who = 'surface_mask'
-    tsdf, weights = _tsdf_pair(who, tsdf, weights)
-    lib = _on_device(who, tsdf)
+    tsdf, weights = views.tsdf_pair(who, tsdf, weights)
+    lib = views.on_device(who, tsdf, MAX_DIM)
     X, Y, Z = tsdf.shape
     mask = torch.empty(tsdf.shape, dtype=torch.uint8, device=tsdf.device)
     rc = lib.ojf_volume_surface_mask(_lib.ptr(tsdf.view(torch.int16)), _lib.ptr(weights.view(torch.int16)), X, Y, Z, _lib.ptr(mask),
@@ -96,8 +86,8 @@ def esdf(tsdf, weights, resolution, max_distance=None):
     if isinstance(resolution, bool) or not isinstance(resolution, (int, float)) or not (resolution > 0) or math.isinf(resolution):
         raise ValueError('{}: resolution must be a finite number > 0, got {!r}'.format(who, resolution))
     limit = _radius2(who, 'max_distance', max_distance, float(resolution))
-    tsdf, weights = _tsdf_pair(who, tsdf, weights)
-    lib = _on_device(who, tsdf)
+    tsdf, weights = views.tsdf_pair(who, tsdf, weights)
+    lib = views.on_device(who, tsdf, MAX_DIM)
     dist2, _ = _edt(who, surface_mask(tsdf, weights), limit)
     out = torch.empty(tsdf.shape, dtype=torch.float32, device=tsdf.device)
     rc = lib.ojf_volume_esdf(_lib.ptr(dist2), _lib.ptr(tsdf.view(torch.int16)), _lib.ptr(weights.view(torch.int16)), tsdf.numel(),
@@ -125,9 +115,8 @@ def erode(mask, radius):
     if radius is None:
         raise ValueError('{}: a radius is needed'.format(who))
     limit = _radius2(who, 'radius', radius)
-    mask = _volume(who, mask, 'mask', torch.uint8)
-    if not mask.is_cuda:
-        raise ValueError('{}: the volumes must be cuda tensors'.format(who))
+    mask = views.mask_volume(who, mask, 'mask', torch.uint8)
+    views.on_device(who, mask, MAX_DIM)
     dist2, _ = _edt(who, (mask == 0).view(torch.uint8), limit)
     return (dist2 == NONE).to(torch.uint8)
 

@@ -1,8 +1,10 @@
 """The host front end the view operators share (render, projective, color, label_probs, rasterize): ``n`` pinhole cameras,
 their [n,h,w] frames, the running-mean options and the [X,Y,Z] volumes, checked and brought into the form the kernels take,
-and the one loop that cuts ``n`` views into kernel calls.  Nothing here loads the library or needs a device: every helper
-works on CPU tensors (tests/test_views_host.py).  ``who`` is the public function's name; every refusal is a ValueError
-that starts with it.  ``dev`` is the torch.device the tensors of a call must live on.
+and the one loop that cuts ``n`` views into kernel calls - and the volume half, which the volume operators share (components,
+distance): ``mask_volume``, ``tsdf_pair``, ``on_device``.  Nothing here loads the library or needs a device before a device
+check is due: every helper but the last, ``on_device``, works on CPU tensors (tests/test_views_host.py).  ``who`` is the
+public function's name; every refusal is a ValueError that starts with it.  ``dev`` is the torch.device the tensors of a call
+must live on.
 """
 import numpy as np
 import torch
@@ -115,3 +117,35 @@ def chunks(n, step, K, E):
 def part(x, v0, v1):
     """The views v0..v1 of an [n,...] image stack or None (leading-axis slices of contiguous images are contiguous)."""
     return None if x is None else x[v0:v1]
+
+
+def mask_volume(who, vol, name, dtype, like=None):
+    """``vol`` as ``volume3`` takes it, on whatever device it lives: beside ``like`` (its shape and device) when that is given.
+    A contiguous bool volume asked for as u8 is reinterpreted, not converted."""
+    if not torch.is_tensor(vol):
+        raise ValueError('{}: {} must be a {} [X,Y,Z] tensor'.format(who, name, dtype))
+    if dtype == torch.uint8 and vol.dtype == torch.bool and vol.is_contiguous():
+        vol = vol.view(torch.uint8)
+    return volume3(who, vol, name, dtype, shape=None if like is None else like.shape, dev=vol.device if like is None else like.device)
+
+
+def tsdf_pair(who, tsdf, weights):
+    """The f16 [X,Y,Z] TSDF and, beside it, its weights."""
+    tsdf = mask_volume(who, tsdf, 'tsdf', torch.float16)
+    return tsdf, mask_volume(who, weights, 'weights', torch.float16, like=tsdf)
+
+
+def on_device(who, vol, max_dim=None):
+    """The loaded library, for a checked volume that is on a cuda device and of a size the kernels index: 1 <= X·Y·Z < 2^31,
+    and with ``max_dim`` no side above it.  The one helper here that needs a GPU and loads the library - the device check is
+    due where an operator calls it - hence last, with its import inside."""
+    from . import _lib
+    if not vol.is_cuda:
+        raise ValueError('{}: the volumes must be cuda tensors'.format(who))
+    if max_dim is None:
+        if vol.numel() < 1 or vol.numel() >= 2 ** 31:
+            raise ValueError('{}: 1 <= X·Y·Z < 2^31 expected, got shape {}'.format(who, tuple(vol.shape)))
+    elif min(vol.shape) < 1 or max(vol.shape) > max_dim or vol.numel() >= 2 ** 31:
+        raise ValueError('{}: 1 <= X, Y, Z <= {} and X·Y·Z < 2^31 expected, got shape {}'.format(who, max_dim, tuple(vol.shape)))
+    _lib.require_gpu()
+    return _lib.load()

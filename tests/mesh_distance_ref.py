@@ -224,6 +224,64 @@ def fan(n=300, seed=5):
                 face_labels=rng.integers(1, 255, n).astype(np.uint8))
 
 
+BRICK = 8  # csrc/ojf_mesh_distance.hip: kBrick
+
+
+def brick_counts(vertices, faces, origin, res, shape, band):
+    """u32 [bricks] in the kernel's brick order: the (triangle, brick) pairs mesh_bin_kernel counts per brick - every brick of
+    the box of voxels whose centres lie in the triangle's bounding box dilated by R (the header's f64 arithmetic).  Only for
+    meshes whose brick boxes hold at most 8 bricks each: the larger ones go through a plane test that is not restated here."""
+    origin, res, band = np.asarray(origin, np.float64).reshape(3), float(res), float(F(band))
+    nb = [(s + BRICK - 1) // BRICK for s in shape]
+    counts = np.zeros(nb, np.uint32)
+    gmax = max(max(abs(origin[m]), abs(origin[m] + float(shape[m]) * res)) for m in range(3))
+    T, faces = prepare(vertices, faces)
+    for f in np.flatnonzero(T['ok']):
+        P = np.asarray(vertices, F).reshape(-1, 3)[faces[f]].astype(np.float64)
+        lo, hi = P.min(axis=0), P.max(axis=0)
+        D, G = 0.0, gmax
+        for m in range(3):
+            D += hi[m] - lo[m]
+            G = max(G, abs(lo[m]), abs(hi[m]))
+        R = band + (1.0 / 262144.0) * ((G + D) + band)
+        b = []
+        for m in range(3):
+            i0 = max(np.ceil(((lo[m] - R) - origin[m]) / res - 0.5), 0.0)
+            i1 = min(np.floor(((hi[m] + R) - origin[m]) / res - 0.5), float(shape[m] - 1))
+            if not i0 <= i1:
+                break
+            b.append(slice(int(i0) // BRICK, int(i1) // BRICK + 1))
+        else:
+            assert counts[tuple(b)].size <= 8, 'face {}: a brick box of the wave-wide tier'.format(f)
+            counts[tuple(b)] += 1
+    return counts.ravel()
+
+
+SCAN_BRICKS = (1, 1023, 1024, 1025, 2049)  # chunks of 1, 1, 1, 2 and 3 counters per lane of the one-block scan (1024 lanes)
+SCAN_BOX = dict(origin=np.zeros(3), res=0.1, band=0.15)
+
+
+def scan_bricks(B):
+    """The bricks of a (8·B, 8, 8) box that hold triangles in ``scan_mesh``: the first and the last, and the last counter of a
+    scan lane's chunk with the first of the next lane's - behind lane 0, in the middle, and in front of the last lane with work."""
+    chunk = (B + 1023) // 1024
+    mid, last = (B // chunk // 2) * chunk, (B - 1) // chunk * chunk
+    return sorted({b for b in (0, chunk - 1, chunk, mid - 1, mid, last - 1, last, B - 1) if 0 <= b < B})
+
+
+def scan_mesh(B):
+    """Small triangles about the centres of ``scan_bricks(B)`` of a box of (8·B, 8, 8) voxels of 0.1 m at the origin, 2, 3, 4, 2,
+    ... to a brick, each within 0.1 m of the centre: with SCAN_BOX's band every one of them is binned to its own brick alone."""
+    verts = []
+    for i, b in enumerate(scan_bricks(B)):
+        for j in range(2 + i % 3):
+            c = np.array([0.8 * b + 0.4, 0.4, 0.4 + 0.06 * (j - 1.5)])  # (0.06 apart: each is the nearest of some voxel)
+            verts += [c + (-0.05, -0.04, 0.0), c + (0.05, -0.03, 0.01), c + (0.0, 0.05, -0.01)]
+    n = len(verts) // 3
+    return dict(vertices=np.array(verts).astype(F), faces=np.arange(3 * n, dtype=np.int32).reshape(n, 3),
+                face_labels=(1 + np.arange(n) % 200).astype(np.uint8))
+
+
 ROOM32 = dict(shape=(32, 32, 32), band=0.24)
 
 

@@ -117,6 +117,60 @@ def test_statistics_of_a_component_over_many_bricks(cuda):
     _same(got, ref.label_components(mask, None, 6), 'frame')
 
 
+RUN_Y, RUN_Z = 16, 64  # one x slice = one run of 1024 voxels of the root count (csrc/ojf_components.hip: kCRun)
+
+
+def _isolated_voxels(R):
+    """u8 (R, 16, 64): foreground voxels of which no two are 26-adjacent, for the scan of the R root counts (one block of 1024
+    lanes, lane t owns the counts [chunk·t, chunk·t + chunk)).  Run x holds 7x mod 5 voxels in its middle - 0 to 4, rows y that
+    alternate with the parity of x.  Around a seam r between two lanes' chunks (behind lane 0, in the middle, in front of the
+    last lane with work) the runs r - 2 and r hold their first voxel as well and the runs r - 1 and r + 1 their last.  The
+    first and the last run are empty, but for R = 1, which holds its first, its last and 3 voxels between."""
+    mask = np.zeros((R, RUN_Y, RUN_Z), np.uint8)
+    if R == 1:
+        mask[0, 0, 0] = mask[0, RUN_Y - 1, RUN_Z - 1] = 1
+        mask[0, 4:9:2, 10] = 1
+        return mask, []
+    for x in range(1, R - 1):
+        for k in range(7 * x % 5):
+            mask[x, 4 + 2 * (x % 2) + 4 * (k % 2), 10 + 20 * (k // 2)] = 1
+    chunk = (R + 1023) // 1024
+    seams = sorted({chunk, (R // chunk // 2) * chunk, (R - 1) // chunk * chunk})
+    for r in seams:
+        for x, y, z in ((r - 2, 0, 0), (r, 0, 0), (r - 1, RUN_Y - 1, RUN_Z - 1), (r + 1, RUN_Y - 1, RUN_Z - 1)):
+            if 0 < x < R - 1:
+                mask[x, y, z] = 1
+    return mask, seams
+
+
+@pytest.mark.parametrize('R', [1, 1023, 1024, 1025, 2049])  # chunks of 1, 1, 1, 2 and 3 counts per lane of the scan
+def test_rank_scan_at_its_chunk_edges(cuda, R):
+    """Every foreground voxel is a component of its own, so the result is closed form: labels[v] = v, ids = the rank of v among
+    the foreground voxels - the exclusive scan of the runs' root counts plus the rank inside the run -, sizes 1, boxes the
+    voxel.  A wrong offset of one run shifts the ids of every voxel of the run."""
+    mask, seams = _isolated_voxels(R)
+    P = np.argwhere(mask)  # index order
+    taken = set(map(tuple, P.tolist()))
+    offsets = [d for d in np.ndindex(3, 3, 3) if d != (1, 1, 1)]
+    assert not any((x + dx - 1, y + dy - 1, z + dz - 1) in taken for x, y, z in taken for dx, dy, dz in offsets)  # no two 26-adjacent
+    per_run = mask.reshape(R, -1).sum(axis=1)
+    if R > 1:
+        assert per_run[0] == 0 and per_run[-1] == 0 and set(per_run[1:-1].tolist()) >= {0, 1, 2, 3, 4} and len(seams) == 3
+        chunk = (R + 1023) // 1024
+        for r in seams:  # the last voxel of a chunk's last run, the first voxel of the next chunk's first run
+            assert r % chunk == 0 and 0 < r < R and (mask[r - 1, -1, -1] or r == 1) and (mask[r, 0, 0] or r == R - 1), r
+        r = seams[1]  # the one in the middle has all four
+        assert mask[r - 2, 0, 0] and mask[r - 1, -1, -1] and mask[r, 0, 0] and mask[r + 1, -1, -1]
+    roots = np.flatnonzero(mask.ravel()).astype(np.int32)
+    n = len(roots)
+    want = {'labels': np.where(mask.ravel() > 0, np.arange(mask.size), -1).astype(np.int32).reshape(mask.shape),
+            'ids': np.full(mask.size, -1, np.int32), 'n': n, 'roots': roots, 'sizes': np.ones(n, np.int32),
+            'keys': np.zeros(n, np.uint8), 'boxes': np.concatenate([P, P], axis=1).astype(np.int32)}
+    want['ids'][roots] = np.arange(n, dtype=np.int32)
+    want['ids'] = want['ids'].reshape(mask.shape)
+    _same(_run(mask, None, 26, cuda), want, ('isolated voxels', R))
+
+
 def test_capacity_contract(cuda):
     """Capacity 0 returns n and writes nothing to the list; a list phase of its own fills it from what the first call left; one
     call with enough capacity does both; a smaller capacity drops the entries beyond it."""

@@ -117,6 +117,19 @@ def test_triangles_that_span_every_brick(cuda, band):
         assert 25 <= got['pairs'] < 150 and set(np.unique(got['face'])) == {-1, 0, 1}
 
 
+@pytest.mark.parametrize('B', ref.SCAN_BRICKS)
+def test_the_scan_of_the_brick_counters_at_its_chunk_edges(cuda, B):
+    """(8·B, 8, 8) voxels = B bricks in a row; triangles in the first and the last brick and in the bricks on either side of
+    the scan lanes' chunk boundaries, 2, 3 or 4 to a brick (test_mesh_distance_host.py checks where they fall and that the
+    counters are what brick_counts says).  A wrong offset hands a brick another brick's list.  The restatement takes
+    two to three seconds for the largest box (23 triangles, a million voxels), so the whole volume is compared."""
+    mesh, shape = ref.scan_mesh(B), (8 * B, 8, 8)
+    got, want = _check(mesh, ref.SCAN_BOX['origin'], ref.SCAN_BOX['res'], shape, ref.SCAN_BOX['band'], cuda, 'scan, {} bricks'.format(B))
+    counts = ref.brick_counts(mesh['vertices'], mesh['faces'], ref.SCAN_BOX['origin'], ref.SCAN_BOX['res'], shape, ref.SCAN_BOX['band'])
+    assert got['pairs'] == int(counts.sum()) == len(mesh['faces'])
+    assert set(np.unique(want[1])) == set(range(-1, len(mesh['faces'])))  # every triangle is the nearest of some voxel
+
+
 # ---- 2. determinism and order independence ---------------------------------------------------------------------------------
 def _d2_of(mesh, origin, res, shape, face):
     """bits of d² from every voxel to the face the grid names (the restatement's candidates)."""

@@ -156,3 +156,23 @@ def test_degenerate_input():
     bad = m['faces'][list(cases['out_of_range'] + cases['nan_vertex'])]
     d2, f2 = ref.distance_field(m['vertices'], bad, origin, res, shape, 100.0)
     assert np.isinf(d2).all() and (f2 == -1).all()
+
+
+def test_scan_cases_reach_their_chunks():
+    """The cases of the GPU test of the brick counters' scan (one block of 1024 lanes, lane t owns the counters
+    [chunk·t, chunk·t + chunk)): every triangle is binned to the brick it was made for and to no other, the counts of the
+    occupied bricks are unequal, the first and the last brick are occupied, and occupied bricks lie on either side of a
+    boundary between two lanes' chunks, with empty bricks elsewhere."""
+    for B, chunk in zip(ref.SCAN_BRICKS, (1, 1, 1, 2, 3)):
+        assert (B + 1023) // 1024 == chunk
+        mesh, bricks = ref.scan_mesh(B), ref.scan_bricks(B)
+        counts = ref.brick_counts(mesh['vertices'], mesh['faces'], ref.SCAN_BOX['origin'], ref.SCAN_BOX['res'], (8 * B, 8, 8), ref.SCAN_BOX['band'])
+        assert counts.shape == (B,) and np.flatnonzero(counts).tolist() == bricks
+        assert counts[bricks].tolist() == [2 + i % 3 for i in range(len(bricks))] and counts.sum() == len(mesh['faces'])
+        assert counts[0] > 0 and counts[B - 1] > 0
+        if B > 1:
+            assert len(set(counts[bricks].tolist())) > 1 and (counts == 0).any()
+            seams = [b for b in bricks if b % chunk == 0 and b > 0 and counts[b - 1] > 0]  # b opens a chunk, b - 1 closes one
+            assert len(seams) >= 3 and counts[chunk - 1] > 0 and counts[chunk] > 0, (B, seams)
+    # chunk 3 over 2049 counters: lane 682 is the last with work, lane 683 starts exactly at n; chunk 2 over 1025: lane 512 owns one
+    assert 683 * 3 == 2049 and ref.scan_bricks(2049)[-3:] == [2045, 2046, 2048] and ref.scan_bricks(1025)[-2:] == [1023, 1024]

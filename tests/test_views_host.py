@@ -161,6 +161,27 @@ def test_volume3():
     assert got.is_contiguous() and got.shape == (3, 4, 5)
 
 
+# ---- the volume operators' half ------------------------------------------------------------------------------------------
+def test_mask_volume_tsdf_pair_and_on_device():
+    mask = torch.zeros(3, 4, 5, dtype=torch.bool)
+    as_u8 = views.mask_volume(WHO, mask, 'mask', torch.uint8)  # a volume on its own: wherever it lives; bool is reinterpreted
+    assert as_u8.dtype == torch.uint8 and as_u8.data_ptr() == mask.data_ptr()
+    keys = torch.zeros(3, 4, 5, dtype=torch.uint8)
+    assert views.mask_volume(WHO, keys, 'keys', torch.uint8, like=as_u8) is keys
+    _refused(views.mask_volume, keys[:2], 'keys', torch.uint8, like=as_u8)
+    _refused(views.mask_volume, keys.numpy(), 'keys', torch.uint8)
+    _refused(views.mask_volume, keys.float(), 'keys', torch.uint8)
+    tsdf, wgt = torch.zeros(3, 4, 5, dtype=torch.float16), torch.ones(3, 4, 5, dtype=torch.float16)
+    got = views.tsdf_pair(WHO, tsdf, wgt)
+    assert got[0] is tsdf and got[1] is wgt
+    _refused(views.tsdf_pair, tsdf, wgt[:, :, :4])
+    _refused(views.tsdf_pair, tsdf, wgt.float())
+    with pytest.raises(ValueError, match=WHO + ': the volumes must be cuda tensors'):  # the device check comes first
+        views.on_device(WHO, tsdf)
+    with pytest.raises(ValueError, match=WHO + ': the volumes must be cuda tensors'):
+        views.on_device(WHO, tsdf, 2048)
+
+
 # ---- chunks -----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('n, spans', [(1, [(0, 1)]), (32, [(0, 32)]), (33, [(0, 32), (32, 33)]), (64, [(0, 32), (32, 64)]),
                                       (65, [(0, 32), (32, 64), (64, 65)])])
