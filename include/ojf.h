@@ -314,7 +314,7 @@ int ojf_segconv_forward_group_batch(int n, int batch, const ojf_segconv *const *
                                     float *const *outs_dev, int out_stride, const float *const *ress_dev, int res_stride,
                                     const float *const *muls_dev, int mul_stride, int act, int h, int w, ojf_stream_t stream);
 
-/* ---- FUSION NET, TRAINING (modules/pipeline.py:301-363 with the net in train() mode; csrc/ojf_net_train.h) -------
+/* ---- FUSION NET, TRAINING (modules/pipeline.py:301-363 with the net in train() mode; csrc/ojf_train.hip) ---------
  * One layer unit of the reference's Sequentials (modules/model.py:4-52,115-141) - conv -> BatchNorm2d (batch
  * statistics) -> activation -> Dropout2d - as device operations on "C4 planes": a tensor with C channels padded to
  * c_phys (multiple of 4) is c_phys/4 planes of float4, element (group cg, pixel p) at [(g0 + cg) * h*w + p]; g0 selects
@@ -358,7 +358,7 @@ int ojf_train_wgrad(const float *x_dev, int x_g0, int c_in_phys, const float *dy
                     int ksize, int dilation, int group, int slot, int h, int w, float *partial_dev, float *dw_dev, int accumulate,
                     ojf_stream_t stream);
 
-/* ---- whole-net TRAINING executor (csrc/ojf_train_net.h) ---------------------------------------------------------
+/* ---- whole-net TRAINING executor (csrc/ojf_train.hip) -----------------------------------------------------------
  * The net of modules/pipeline.py:322 inside fuse_training and the loss.backward() of train_fusion.py:171 as two calls:
  * forward and backward pass of FusionNet_v3 / _v2 (modules/model.py:164-283) in train() or eval() mode on the layer-unit
  * kernels above, with every activation / gradient buffer owned by the trainer and the four branches of a VortexPooling

@@ -42,7 +42,7 @@ Camera make_camera(const float *Ki, const float *E, const double *origin, double
 __device__ __forceinline__ int xcd_band_block(int b, int n8) { return (b & 7) * (n8 >> 3) + (b >> 3); }
 __device__ __forceinline__ int banded_block_x() { return (gridDim.x & 7) == 0 ? xcd_band_block(blockIdx.x, gridDim.x) : (int)blockIdx.x; }
 
-// Range guard of the split-fp16 arithmetic (ojf_net.hip: overflow_flag): a DEVICE-resident block {flag, integrate calls
+// Range guard of the split-fp16 arithmetic (ojf_guard.hip): a DEVICE-resident block {flag, integrate calls
 // skipped, pointer to the host-mapped mirror of the flag}.  A kernel that meets a value a later split could not
 // represent raises the flag here - the device word is what the integrate kernels test before they touch a volume (a
 // frame whose net tripped the guard must not be fused), the host-mapped mirror is what the host polls without
@@ -53,6 +53,15 @@ __device__ __forceinline__ void guard_raise(int *g, int v)
     int *host = *reinterpret_cast<int *const *>(g + 2);
     *host = v;
 }
+// Host side of the guard (ojf_guard.hip holds the one block of the process):
+int *overflow_flag();             // the device block, created on first use - what a split-fp16 launch passes as its `ovf`
+int *range_flag_device();         // the same, under the name ojf_seg.hip uses
+const int *range_guard_if_any();  // ojf_integrate*.hip: NULL while no split-fp16 kernel ever got the flag
+// a fired guard, after the stream was synchronised: the value (0 none, 1 range, 2 dense chain stuck), how many integrate
+// calls were skipped because of it; `clear` re-arms both copies
+int guard_take(int *skipped, bool clear);
+int guard_fail(int what);         // fail() with the message of guard value `what`
+int guard_refusal();              // 0, or guard_fail of the mirror's value while the guard is raised (no synchronisation)
 
 // Low halves of the split-fp16 operands: fp16(x0 - hi.lo), fp16(x1 - hi.hi) packed like `hpair` (the two fp16 high
 // halves of x0, x1).  v_fma_mix{lo,hi}_f16 forms x - hi exactly in fp32 and rounds once to fp16: the same bits as

@@ -65,7 +65,6 @@ __device__ __forceinline__ float frame_depth(const IntegrateArgs &a, int n)
     return (a.mask && !a.mask[n]) ? 0.0f : z;  // torch.where(mask == 0, 0, frame)
 }
 
-const int *range_guard_if_any();  // ojf_net.hip
 __device__ __forceinline__ bool guard_set(const IntegrateArgs &a) { return a.guard && *static_cast<volatile const int *>(a.guard) != 0; }
 
 size_t fast_workspace_bytes(int X, int Y, int Z, int h, int w, int n_tail);

@@ -54,8 +54,13 @@
 // head's tail computing its half of the last entry GEMM.  Other inputs take the general paths: dense_pair_kernel per Block
 // (w % 8 != 0), generic convolutions (fp32 arithmetic, other growth rates), the general VortexPooling flow with the
 // global-average branch on a side stream and an unfused tail / head (topologies without chain-layer forms).
-// Environment switches: OJF_NET_GRAPH=1 (opt-in hipGraph replay); test-only, set by tests/test_net_gpu.py:
-// OJF_NO_DENSE_CHAIN=1 (pair kernels instead of the chain kernel).
+// Environment switches: OJF_NET_GRAPH=1 (opt-in hipGraph replay); OJF_NET_TRACE=1 (one stderr line per launch: net_trace_on);
+// test-only, set by tests/test_net_gpu.py: OJF_NO_DENSE_CHAIN=1 (pair kernels instead of the chain kernel).
+// Files: this unit is the inference net (kernels, packing, the forward plan, the executor, ojf_net_*) with ojf_net_pair.h
+// (dense_pair_kernel) and ojf_net_chain.h (dense_chain_kernel) as its parts.  ojf_net_conv.h is what it shares with the training
+// path, a unit of its own (ojf_train.hip): ConvArgs and the helpers around it, and the declarations of launch_conv_args,
+// div_magic and event_flags, defined here.  The range guard's state and its entry points
+// (ojf_net_check, ojf_guard_*) are ojf_guard.hip; this file only passes overflow_flag() to its kernels.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -63,26 +68,11 @@
 #include <cstring>
 #include <vector>
 
-#include "ojf_common.h"
+#include "ojf_net_conv.h"
 
 namespace ojf {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-// x (8 fp32 values) -> fp16 halves xh + xl, both rounded to nearest; x - xh is exact in fp32
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void split_f16(const f32x4 &a, const f32x4 &b, f16x8 &hi, f16x8 &lo)
-{
-    const f32x8 x = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    hi = __builtin_convertvector(x, f16x8);  // 4 x v_cvt_pk_f16_f32
-    const u32x4 h = __builtin_bit_cast(u32x4, hi);
-    u32x4 l;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) l[i] = split_lo_pair(h[i], x[2 * i], x[2 * i + 1]);
-    lo = __builtin_bit_cast(f16x8, l);
-}
+// (vector typedefs, split_f16, ConvArgs, fast_div, guard_max, round_up, planes(), the packing constants: ojf_net_conv.h)
 
 // One float4 -> its split-fp16 form in the same 16 bytes: halfs {h0 h1 h2 h3 | l0 l1 l2 l3}, the very halves split_f16
 // makes of these values (same pairs, same instructions).  A producer that stores its planes this way ("split planes")
@@ -123,41 +113,9 @@ __device__ __forceinline__ f32x4 mfma_f16x3(const f32x4 &wh, const f32x4 &wl, co
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(h, xh, acc, 0, 0, 0);
 }
 
-static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
-
 // ------------------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------------------
-struct ConvArgs {
-    const f32x4 *in;   // input planes (in[-1] is a zero float4); group cg of the window = plane in_g0 + cg
-    f32x4 *out;        // output planes (NULL when out_rows is used)
-    float *out_rows;   // last layer only: row-major [npix, rows_stride] scalars, channels < rows_n
-    const f32x4 *wp;   // packed weights [oc tile][superstep][lane] float4
-    const float *bias; // [n_ot*16]
-    const float *rinv; // split-fp16: [n_ot*16] inverse of the per-output-channel power-of-two weight scale
-    int in_g0, out_g0, rows_stride, rows_n;
-    int h, w, npix;
-    int taps, dil;
-    int c4;          // input channel groups per tap
-    int nsteps;      // supersteps = ceil(taps * c4 / 4)
-    int og_store;    // output channel groups written (planar mode)
-    int act, act_n;  // activation applied to output channels < act_n
-    float scale;
-    int *ovf;        // split-fp16 only: set to 1 when an activation leaves the fp16 range (host-mapped flag)
-    int accum;       // planar stores only: out += result (fan-out gradients of the training path); 0 = plain store
-    const float *dscale;  // training backward-data: the input carries a power-of-two factor *dscale - the result is divided by it; NULL = off
-    unsigned w_magic, c4_magic;  // ceil(2^32 / w), ceil(2^32 / c4): x / d == umulhi(x, magic) while x * d < 2^32 (0: divide)
-    int in_split = 0, out_split = 0;  // split-fp16 launches: the input / output planes are split planes (split_pack4)
-    // Banded split-fp16 3x3 launches with dilation r > 1 (round 6): the rows of the image are handed to the blocks in the order
-    // (y mod r, y div r) instead of y.  An XCD's band of 30 rows of a 240-row frame then holds rows that are r apart - the
-    // very rows its taps read - instead of 30 neighbours whose taps reach 27 rows into both neighbouring bands: with plain
-    // bands every private L2 pulled (30 + 2 r) / 30 of its share through the fabric (2.8x for r = 27, 1.6x for r = 9: the
-    // grouped launch fetched 40 MB for a 24.6-MB input, profiles/r05_final_traffic_pmc.txt); in class order the halo is one
-    // row on either side of the band.  Which block computes which pixels changes, nothing else: the same bits.
-    int row_perm = 0, perm_q = 0, perm_rem = 0;  // r (0: off), h / r, h % r
-    const f32x4 *wp_rows = nullptr;  // the layer's weights in tap-row order (conv_f16x3_rows_kernel), NULL: not packed for it
-};
-
 // position `pr` of the row order (y mod r, y div r) -> row y; classes c < h % r have h / r + 1 rows, the others h / r
 __device__ __forceinline__ int perm_row(int pr, int r, int q, int rem)
 {
@@ -170,19 +128,7 @@ __device__ __forceinline__ int perm_row(int pr, int r, int q, int rem)
     return rem + c + (p2 - c * q) * r;
 }
 
-__device__ __forceinline__ int fast_div(int x, int d, unsigned magic) { return magic ? (int)__umulhi((unsigned)x, magic) : x / d; }
-
-// Split-fp16 range guard.  Kernels keep a running maximum of the magnitudes of every value a later layer will
-// split (2 VALU per float4: v_max3_f32 with |.| modifiers) and raise the flag if it exceeds the fp16 range.
-// v_max ignores NaN operands, deliberately: a NaN input (the reference writes NaN TSDF into voxels it touches with
-// zero total weight, and later frames gather them) propagates to NaN outputs in both arithmetics exactly as in the
-// fp32 reference, so it is not an error here either.  With finite weights (checked at creation) an out-of-range
-// event is always a finite value beyond 65504 or an infinity at a guarded point first.
-__device__ __forceinline__ float guard_max(float mx, const f32x4 &v)
-{
-    return fmaxf(fmaxf(fmaxf(mx, fabsf(v[0])), fmaxf(fabsf(v[1]), fabsf(v[2]))), fabsf(v[3]));
-}
-__device__ __forceinline__ bool beyond_f16(const f32x4 &v)  // raw inputs; NaN is not a range violation (see above)
+__device__ __forceinline__ bool beyond_f16(const f32x4 &v)  // raw inputs; NaN is not a range violation (see guard_max)
 {
     return guard_max(0.0f, v) > 65504.0f;
 }
@@ -220,8 +166,6 @@ __device__ __forceinline__ f32x4 leaky_max4(const f32x4 &x, float slope)
     return r;
 }
 
-constexpr int kMaxSteps = 128;  // supersteps per conv (K <= 2048)
-constexpr int kPadSteps = 4;    // dead supersteps appended for the three-stage prefetch (fetches reach S+4)
 
 // C/D layout of the 16x16 MFMAs: lane (i16, g) holds column i16 (pixel) and rows 4g..4g+3 (output channels)
 template <int MT, int NT, bool GUARD = false>
@@ -549,7 +493,6 @@ __global__ __launch_bounds__(256) void conv_mfma_lds_kernel(const ConvGroup grp)
 // shared by the four waves of the block: with the 5x faster MFMA the per-wave L1 weight stream of the
 // fp32 kernel would be the bound (measured: 35 -> 26 us on the grouped 19->19 3x3 launches).
 // ------------------------------------------------------------------------------------------------
-constexpr int kPad16 = 6;  // dead supersteps behind the weights and the tap table (chunk copies + prefetch)
 constexpr int conv16_chunk(int nt) { return nt <= 2 ? 6 : 3; }  // supersteps per LDS chunk (<= 24 KB)
 
 // ABL: profiling-only ablation mask (tests/microbench): 1 = no activation loads, 2 = no LDS weight reads,
@@ -2108,55 +2051,6 @@ struct PackedConv {
 
 static int g_default_arith = OJF_ARITH_F16X3;
 
-// Range guard of the split-fp16 arithmetic: one flag per process, in two places.  Kernels raise it (guard_raise,
-// ojf_common.h) when a value that a later layer would split leaves the fp16 range (or is NaN): in a device-resident
-// block {flag, skipped integrate calls, pointer to the mirror} - what ojf_integrate* test before they touch a volume, so
-// that a frame whose net tripped the guard (and every frame after it, until the host has dealt with it) is NOT fused -
-// and in a host-mapped mirror, which the host polls without synchronising (ojf_net_forward) or after a stream
-// synchronise (ojf_net_check).  No traffic unless it fires.
-static volatile int *g_ovf_host = nullptr;
-static int *g_ovf_dev = nullptr;  // device block: [0] flag, [1] integrate calls skipped, [2..3] device address of the mirror
-
-static int *overflow_flag()
-{
-    if (!g_ovf_dev) {
-        void *h = nullptr, *hd = nullptr, *d = nullptr;
-        if (hipHostMalloc(&h, sizeof(int), hipHostMallocMapped) != hipSuccess) return nullptr;
-        *static_cast<int *>(h) = 0;
-        if (hipHostGetDevicePointer(&hd, h, 0) != hipSuccess) return nullptr;
-        if (hipMalloc(&d, 16) != hipSuccess) return nullptr;
-        struct { int flag, skipped; void *mirror; } init{0, 0, hd};
-        static_assert(sizeof(init) == 16, "guard block layout");
-        if (hipMemcpy(d, &init, sizeof(init), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        g_ovf_host = static_cast<volatile int *>(h);
-        g_ovf_dev = static_cast<int *>(d);
-    }
-    return g_ovf_dev;
-}
-
-int *range_flag_device() { return overflow_flag(); }  // shared with ojf_seg.hip
-const int *range_guard_if_any() { return g_ovf_dev; }  // ojf_integrate*.hip: NULL while no split-fp16 kernel ever got the flag
-
-// Host side of a fired guard, after the stream was synchronised: the value (0 none, 1 range, 2 dense chain stuck), how many
-// integrate calls were skipped because of it; `clear` re-arms both copies.
-static int guard_take(int *skipped, bool clear)
-{
-    if (!g_ovf_host || !*g_ovf_host) {
-        if (skipped) *skipped = 0;
-        return 0;
-    }
-    const int what = *g_ovf_host;
-    int blk[2] = {what, 0};
-    (void)hipMemcpy(blk, g_ovf_dev, sizeof(blk), hipMemcpyDeviceToHost);
-    if (skipped) *skipped = blk[1];
-    if (clear) {
-        (void)hipMemset(g_ovf_dev, 0, 2 * sizeof(int));
-        (void)hipStreamSynchronize(nullptr);  // (non-blocking streams do not order against the null stream's fill: see alloc_planes)
-        *g_ovf_host = 0;
-    }
-    return what;
-}
-
 // Launch log of a forward pass: every launch site calls mark_launch(name, stream) right after its launch.  It counts the
 // launches (ojf_net_launch_count) and, in profile mode (ojf_net_profile), records a fence-free timing event behind the
 // launch, so that the time between consecutive marks of one stream is that kernel's duration as the stream sees it.
@@ -2197,15 +2091,8 @@ static bool net_trace_on()
     return on;
 }
 
-// Fork / join events between streams of the same device: no timing and no system-scope fence - nothing here is read by
-// the host or another device through these events.
-static unsigned event_flags() { return hipEventDisableTiming | hipEventDisableSystemFence; }
-
-static const char *kChainStuckMsg =
-    "fusion net: dense_chain_kernel gave up waiting for a neighbouring tile (internal error: the results of this forward pass are invalid)";
-static const char *kOverflowMsg =
-    "split-fp16 arithmetic: an activation or input left the fp16 range (|x| > 65504 or NaN); results since the last "
-    "ojf_net_check are invalid - use ojf_net_set_arithmetic(OJF_ARITH_F32) for this network";
+// (ojf_net_conv.h)
+unsigned event_flags() { return hipEventDisableTiming | hipEventDisableSystemFence; }
 
 // Split-fp16 weights are equilibrated per output channel: row oc is multiplied by the power of two that brings its
 // largest magnitude to [2^13, 2^14) before it is split, and the accumulator is multiplied by the inverse in the
@@ -2227,8 +2114,6 @@ static inline void split_weight(float v, _Float16 &hi, _Float16 &lo)
     hi = (_Float16)v;
     lo = (_Float16)(v - (float)hi);
 }
-
-constexpr int kNT = 2;  // packed weights are padded to a multiple of this many output-channel tiles
 
 struct ConvBuilder {
     int c_in_phys, c_out_phys, taps, dil;
@@ -2352,9 +2237,6 @@ static void release(PackedConv &pc)
     if (pc.wp_rows) (void)hipFree(pc.wp_rows);
     pc.wp = pc.bias = pc.rinv = pc.wp_rows = nullptr;
 }
-
-static inline f32x4 *planes(float *p) { return reinterpret_cast<f32x4 *>(p); }
-static inline const f32x4 *planes(const float *p) { return reinterpret_cast<const f32x4 *>(p); }
 
 // ---- fused 3x3 -> 3x3 pair (dense_pair_kernel, ojf_net_pair.h) ----------------------------------------------------
 #ifdef OJF_PAIR_TIMING
@@ -2615,10 +2497,8 @@ static int launch_chain(const PackedChain &pc, float *x, int h, int w, hipStream
     return launch_chain_t<12, 8, 8>(a, st);
 }
 
-// Launches n (<= 4) independent convolutions with the same number of output tiles as ONE grid
-// (blockIdx.y = problem): the four branches of a VortexPooling run together instead of as four
-// under-filled launches with their own ramp-up and tail.
-static int launch_conv_args(const ConvArgs *args, int n, int nt, hipStream_t st, int arith)
+// (declared in ojf_net_conv.h: the training path launches its convolutions here too)
+int launch_conv_args(const ConvArgs *args, int n, int nt, hipStream_t st, int arith)
 {
     ConvGroup grp;
     for (int i = 0; i < n; ++i) grp.g[i] = args[i];
@@ -2725,8 +2605,8 @@ static int launch_conv_args(const ConvArgs *args, int n, int nt, hipStream_t st,
     return check_hip(hipGetLastError(), "conv kernel launch");
 }
 
-// magic of fast_div for divisor d and dividends below `limit` (0 = use a real division)
-static unsigned div_magic(int d, uint64_t limit)
+// (ojf_net_conv.h)
+unsigned div_magic(int d, uint64_t limit)
 {
     if (d <= 1 || limit * (uint64_t)d >= (1ull << 32)) return 0;
     return (unsigned)(((1ull << 32) + (uint64_t)d - 1) / (uint64_t)d);
@@ -3852,7 +3732,8 @@ OJF_API int ojf_net_forward(ojf_net *net, float *est, int est_stride, ojf_stream
     if (!net || !est) return fail("ojf_net_forward: null pointer argument");
     if (est_stride < net->P) return fail("ojf_net_forward: est_stride < n_points");
     hipStream_t st = as_stream(stream);
-    if (net->arith == OJF_ARITH_F16X3 && g_ovf_host && *g_ovf_host) return fail(*g_ovf_host == 2 ? kChainStuckMsg : kOverflowMsg);
+    if (net->arith == OJF_ARITH_F16X3)
+        if (const int rc = guard_refusal()) return rc;
     if (net->use_graph) {
         if (!net->gexec || net->g_est != est || net->g_stride != est_stride) capture_graph(net, est, est_stride);
         if (net->gexec) return check_hip(hipGraphLaunch(net->gexec, st), "hipGraphLaunch (net forward)");
@@ -3953,25 +3834,6 @@ OJF_API int ojf_net_set_arithmetic(int arithmetic)
 
 OJF_API int ojf_net_get_arithmetic(const ojf_net *net) { return net ? net->arith : ojf::g_default_arith; }
 
-OJF_API int ojf_net_check(ojf_stream_t stream)
-{
-    using namespace ojf;
-    OJF_HIP(hipStreamSynchronize(as_stream(stream)));
-    if (const int what = guard_take(nullptr, true)) return fail(what == 2 ? kChainStuckMsg : kOverflowMsg);
-    return 0;
-}
-
-OJF_API int ojf_guard_poll(void) { return ojf::g_ovf_host ? *ojf::g_ovf_host : 0; }
-
-OJF_API int ojf_guard_status(ojf_stream_t stream, int *flag, int *skipped)
-{
-    using namespace ojf;
-    OJF_HIP(hipStreamSynchronize(as_stream(stream)));
-    const int what = guard_take(skipped, false);
-    if (flag) *flag = what;
-    return 0;
-}
-
 OJF_API int ojf_conv2d(const float *in, int in_stride, int in_off, float *out, int out_stride, int out_off,
                        const ojf_conv_layer *layer, int act, int h, int w, ojf_stream_t stream)
 {
@@ -3999,7 +3861,7 @@ OJF_API int ojf_conv2d(const float *in, int in_stride, int in_off, float *out, i
         hipLaunchKernelGGL(planes_to_rows_kernel, dim3((npix * (cout_phys / 4) + 255) / 256), dim3(256), 0, st,
                            planes(pout), cout_phys / 4, npix, out, out_stride, out_off);
         rc = check_hip(hipStreamSynchronize(st), "ojf_conv2d sync");  // test-only API: packs per call
-        if (!rc && guard_take(nullptr, true)) rc = fail(kOverflowMsg);
+        if (!rc && guard_take(nullptr, true)) rc = guard_fail(1);
     }
     free_planes(pin);
     free_planes(pout);
@@ -4089,6 +3951,3 @@ extern "C" __attribute__((visibility("default"))) int ojf_debug_entry_stamps(voi
     return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(ojf::g_entry_stamps), bytes < sizeof(ojf::g_entry_stamps) ? bytes : sizeof(ojf::g_entry_stamps));
 }
 #endif
-
-#include "ojf_net_train.h"
-#include "ojf_train_net.h"

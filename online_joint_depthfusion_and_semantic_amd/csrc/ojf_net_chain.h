@@ -1,5 +1,5 @@
 // All dense Blocks of one head (modules/model.py:4-21,219-283: x <- cat(x, Block_i(x)), i = 0..gf-1) as ONE persistent
-// launch on split-fp16 MFMA (included by ojf_net.hip only).  Round 4; replaces five dense_pair_kernel launches.
+// launch on split-fp16 MFMA (a part of ojf_net.hip, after ojf_net_pair.h).  Round 4; replaces five dense_pair_kernel launches.
 //
 // What the five-launch form left on the table (s_memtime stamps, profiles/r04_pair_experiments.txt): its K loops ran at
 // 84-95 % of the matrix pipe, but 40 % of every launch was not a K loop - the first window fill of 240 blocks at once

@@ -1,4 +1,4 @@
-// Fused 3x3 -> 3x3 convolution pair on split-fp16 MFMA (included by ojf_net.hip only).
+// Fused 3x3 -> 3x3 convolution pair on split-fp16 MFMA (a part of ojf_net.hip: it needs that file's kernels section in front of it).
 //
 // A dense Block of the fusion net (modules/model.py:4-21) is  slot[i+1] = act(conv3x3_b(act(conv3x3_a(slots 0..i)))):
 // the intermediate T (19 channels) is consumed by nobody else.  The generic kernel ran the two convolutions as two

@@ -29,8 +29,6 @@
 
 namespace ojf {
 
-int *range_flag_device();  // ojf_net.hip: the split-fp16 range guard flag (host-mapped), shared by all kernels
-
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));

@@ -1,23 +1,9 @@
-// TRAINING path of the fusion net (modules/pipeline.py:301-363 fuse_training with the net in train() mode; included by
-// ojf_net.hip only).  One fused layer unit of the reference's Sequentials (modules/model.py:4-52,115-141)
-//
-//     conv (1x1 / dilated 3x3, bias) -> BatchNorm2d with BATCH statistics -> ReLU / LeakyReLU / Tanh -> Dropout2d
-//
-// as device kernels for forward and backward; Python (train.py) wraps a unit as ONE torch.autograd.Function and leaves the
-// glue of the net (concatenations, average pools, the 1x1 global-average map, loss) to torch on the same C4-planar
-// tensors, so that autograd accumulates the fan-out gradients and the reference's optimizer / checkpoint code runs
-// unchanged.  All convolutions here use the fp32-input MFMA kernel (conv_mfma_kernel: bitwise a k-ordered fmaf chain):
-// gradients are tiny (d loss / d est ~ 1e-6) and of unbounded dynamic range - the split-fp16 arithmetic of the
-// inference path would need loss scaling; the weight gradient runs on the fp32 MFMA as well (K = pixels).
-//
-//   ojf_train_pack          torch weights [oc][ic][k][k] -> the conv kernel's fragment layout, on the device, every step:
-//                           forward form, or transposed + tap-flipped form (backward-data IS a convolution with it)
-//   ojf_train_conv          convolution on C4 planes (any c_out: chunks of 8 output tiles per launch)
-//   ojf_train_bn_act        per-channel batch mean / 1 / sqrt(var + eps) (fp64 sums, fixed order) + running-stat update, then
-//                           out = drop_c * act(gamma_c * (y - mean_c) * invstd_c + beta_c)
-//   ojf_train_bn_act_bwd    dgamma, dbeta, dbias and dy = gamma * invstd * (dz - mean(dz) - xhat * mean(dz * xhat))
-//   ojf_train_wgrad         dW[oc][ic][tap] = sum_p dy[oc][p] * x[ic][p + tap]  (pixel slabs -> partial sums -> fixed-order sum)
+// Device kernels of the fusion net's TRAINING path and their argument structs: first those of the layer units (packing,
+// BatchNorm statistics, normalise + activate, weight gradient, average pool), then those of the whole-net executor (input /
+// output layout, pool pyramid, global-average branch, fuse-output and loss glue, split-fp16 weight packing).  The design
+// and the host side are in ojf_train.hip; the convolutions themselves are ojf_net.hip's, reached through launch_conv_args.
 #pragma once
+#include "ojf_net_conv.h"
 
 namespace ojf {
 
@@ -654,186 +640,477 @@ __global__ __launch_bounds__(256) void train_avgpool3_kernel(const f32x4 *in, f3
     }
 }
 
-static float *g_train_zero_bias = nullptr;  // 4096 zero floats: the conv kernel always reads a bias vector
+// ---- small kernels of the executor ---------------------------------------------------------------------------------
+struct PackInArgs {
+    const float *src[4];  // NCHW sources [n_i][npix]
+    int nch[4];
+    int n_src, c4, npix;
+    f32x4 *dst;           // planes [c4][npix]
+};
+
+__global__ __launch_bounds__(256) void train_pack_input_kernel(const PackInArgs a)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.npix) return;
+    const int cg = blockIdx.y;
+    f32x4 v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int l = 4 * cg + j;
+        for (int s = 0; s < a.n_src; ++s) {
+            if (l < a.nch[s]) { v[j] = a.src[s][(size_t)l * a.npix + p]; break; }
+            l -= a.nch[s];
+        }
+    }
+    a.dst[(size_t)cg * a.npix + p] = v;
+}
+
+// planes [c4][npix] <-> NCHW [C][npix] (est out / d est in); channels >= C are dropped / zero
+__global__ __launch_bounds__(256) void train_planes_to_nchw_kernel(const f32x4 *pl, int c4, int C, int npix, float *dst)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    const f32x4 v = pl[(size_t)blockIdx.y * npix + p];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (4 * (int)blockIdx.y + j < C) dst[(size_t)(4 * blockIdx.y + j) * npix + p] = v[j];
+}
+
+__global__ __launch_bounds__(256) void train_nchw_to_planes_kernel(const float *src, int C, int npix, f32x4 *pl)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    f32x4 v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (4 * (int)blockIdx.y + j < C) v[j] = src[(size_t)(4 * blockIdx.y + j) * npix + p];
+    pl[(size_t)blockIdx.y * npix + p] = v;
+}
+
+// out[group g] = P^lv(in[group g]) (+ bias of the branch), lv = g / sl4: branch i of a VortexPooling sees i successive
+// nn.AvgPool2d(3, 1, 1) (count_include_pad: zeros outside the image, divide by 9 - every level zero-pads anew).  One block =
+// one 32 x 8 pixel tile of one channel group, the intermediate levels live in LDS with a shrinking halo.  The operator is
+// symmetric, so the backward pass is the same kernel on the gradient (without bias).
+struct TrainPyramidArgs {
+    const f32x4 *in;
+    f32x4 *out;
+    const float *bias[4];  // per branch: [OC] logical, or NULL
+    int h, w, sl4, OC;
+};
+constexpr int kTpW = 32, kTpH = 8, kTpStride = kTpW + 6;
+
+__global__ __launch_bounds__(256) void train_pyramid_kernel(const TrainPyramidArgs a)
+{
+    __shared__ f32x4 buf[2][kTpStride * (kTpH + 6)];
+    const int g = blockIdx.y, lv = g / a.sl4, cg = g - lv * a.sl4;
+    const int tiles_x = (a.w + kTpW - 1) / kTpW;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int x0 = tx * kTpW, y0 = ty * kTpH, npix = a.h * a.w;
+    const f32x4 *plane = a.in + (size_t)g * npix;
+    const f32x4 zero{0.f, 0.f, 0.f, 0.f};
+    f32x4 b = zero;
+    if (a.bias[lv])
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (4 * cg + j < a.OC) b[j] = a.bias[lv][4 * cg + j];
+    if (lv == 0) {
+        const int ly = threadIdx.x / kTpW, lx = threadIdx.x - ly * kTpW;
+        const int gy = y0 + ly, gx = x0 + lx;
+        if (gy < a.h && gx < a.w) a.out[(size_t)g * npix + gy * a.w + gx] = plane[gy * a.w + gx] + b;
+        return;
+    }
+    {
+        const int W0 = kTpW + 2 * lv, H0 = kTpH + 2 * lv;
+        for (int i = threadIdx.x; i < W0 * H0; i += 256) {
+            const int ly = i / W0, lx = i - ly * W0;
+            const int gy = y0 - lv + ly, gx = x0 - lv + lx;
+            const bool in = (unsigned)gy < (unsigned)a.h && (unsigned)gx < (unsigned)a.w;
+            buf[0][ly * kTpStride + lx] = in ? plane[gy * a.w + gx] : zero;
+        }
+    }
+    __syncthreads();
+    for (int l = 1; l <= lv; ++l) {
+        const int halo = lv - l;
+        const int Wl = kTpW + 2 * halo, Hl = kTpH + 2 * halo;
+        const f32x4 *src = buf[(l - 1) & 1];
+        for (int i = threadIdx.x; i < Wl * Hl; i += 256) {
+            const int ly = i / Wl, lx = i - ly * Wl;
+            const int gy = y0 - halo + ly, gx = x0 - halo + lx;
+            const bool in = (unsigned)gy < (unsigned)a.h && (unsigned)gx < (unsigned)a.w;
+            f32x4 s = zero;
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+                for (int dx = 0; dx < 3; ++dx) s += src[(ly + dy) * kTpStride + lx + dx];
+            s = s / 9.0f;
+            if (l < lv) buf[l & 1][ly * kTpStride + lx] = in ? s : zero;
+            else if (in) a.out[(size_t)g * npix + gy * a.w + gx] = s + b;
+        }
+        __syncthreads();
+    }
+}
+
+// ---- global-average branch of a VortexPooling (modules/model.py:103-109,146): AdaptiveAvgPool2d(1) -> 1x1 conv ->
+// up-sampling of the 1x1 map (a broadcast) -> BatchNorm2d.  The BatchNorm sees a constant map: with batch statistics its
+// output is beta (variance 0), nothing upstream receives a gradient, running_mean moves towards the map's value and
+// running_var towards 0; with running statistics it is an affine map of g = W mean(x) + b and gradients flow to W, b,
+// gamma, beta and (as a per-channel constant over all pixels) to x.  One block does the vector work.
+struct GaveTrainArgs {
+    const double *partial;   // [slabs][c4_in][8]: channel sums of x (forward) / of d cat[gave slot] (backward)
+    int c4_in, c4_out, IC, OC, group, slot, npix, training, accumulate;
+    float momentum, eps;
+    const float *W, *b, *gamma, *beta;
+    float *running_mean, *running_var;
+    float *pooled, *xhat, *gis;  // saved for backward: [4 c4_in] mean of x per physical channel, [OC] x-hat, [OC] gamma * invstd
+    float *vec;                  // forward: [4 c4_out] value of the branch's constant map (padding channels 0)
+    float *dW, *db, *dgamma, *dbeta;
+    float *dpooled;              // backward (eval): [4 c4_in] per-channel constant added to d x
+    // The branch's constant map is input channels [0, OC) of the VortexPooling's final 1x1 convolution (weights Wf
+    // [OCf][ICf_total], bias bf): over a constant map that convolution is a per-frame BIAS, Wf[:, :OC] vec - so the map is
+    // never materialised, the final convolution reads the four branch slots only, and backward needs just the channel
+    // sums of the final convolution's dy: d vec = Wf[:, :OC]^T sum_dy,  d Wf[:, :OC] = sum_dy (x) vec.
+    const float *Wf, *bf;
+    int OCf, ICf_total, accumulate_f;
+    float *bias_eff;             // forward: [OCf] bf + Wf[:, :OC] vec -> the final unit's packed bias
+    const float *sum_dy;         // backward: [OCf]
+    float *dWf;                  // backward: the final convolution's weight gradient (columns [0, OC) written here)
+};
+
+// sum of the kTrainSlabs partial rows of physical channel ch, by one wave (lane b takes row b; fixed xor tree)
+__device__ __forceinline__ double gave_slab_sum(const double *partial, int c4, int ch)
+{
+    double v = partial[((size_t)(threadIdx.x & 63) * c4 + (ch >> 2)) * 8 + (ch & 3)];
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+constexpr int kGaveThreads = 1024, kGaveMaxC = 1024;
+
+__global__ __launch_bounds__(kGaveThreads) void train_gave_fwd_kernel(const GaveTrainArgs a)
+{
+    __shared__ float pooled[kGaveMaxC], vecs[kGaveMaxC];
+    const int wave = threadIdx.x >> 6, nw = kGaveThreads / 64;
+    for (int ch = wave; ch < 4 * a.c4_in; ch += nw) {
+        const float m = (float)(gave_slab_sum(a.partial, a.c4_in, ch) / (double)a.npix);
+        if ((threadIdx.x & 63) == 0) { pooled[ch] = m; a.pooled[ch] = m; }
+    }
+    __syncthreads();
+    for (int o = threadIdx.x; o < 4 * a.c4_out; o += kGaveThreads) {
+        float vec = 0.0f;
+        if (o < a.OC) {
+            float g = a.b ? a.b[o] : 0.0f;
+            for (int l = 0; l < a.IC; ++l) g = fmaf(a.W[(size_t)o * a.IC + l], pooled[(l / a.group) * a.slot + l % a.group], g);
+            const float ga = a.gamma ? a.gamma[o] : 1.0f, be = a.beta ? a.beta[o] : 0.0f;
+            if (a.training) {
+                a.running_mean[o] = (1.0f - a.momentum) * a.running_mean[o] + a.momentum * g;
+                a.running_var[o] = (1.0f - a.momentum) * a.running_var[o];
+                a.xhat[o] = 0.0f;
+                a.gis[o] = 0.0f;
+                vec = be;
+            } else {
+                const float is = 1.0f / sqrtf(a.running_var[o] + a.eps);
+                const float xh = (g - a.running_mean[o]) * is;
+                a.xhat[o] = xh;
+                a.gis[o] = ga * is;
+                vec = xh * ga + be;
+            }
+        }
+        a.vec[o] = vec;
+        vecs[o] = vec;
+    }
+    __syncthreads();
+    for (int o = threadIdx.x; o < a.OCf; o += kGaveThreads) {  // the constant map's share of the final convolution = a bias
+        float b = a.bf ? a.bf[o] : 0.0f;
+        for (int c = 0; c < a.OC; ++c) b = fmaf(a.Wf[(size_t)o * a.ICf_total + c], vecs[c], b);
+        a.bias_eff[o] = b;
+    }
+}
+
+__global__ __launch_bounds__(kGaveThreads) void train_gave_bwd_kernel(const GaveTrainArgs a)
+{
+    __shared__ float dg[kGaveMaxC], sdy[kGaveMaxC];
+    for (int o = threadIdx.x; o < a.OCf; o += kGaveThreads) sdy[o] = a.sum_dy[o];
+    __syncthreads();
+    for (int c = threadIdx.x; c < a.OC; c += kGaveThreads) {
+        float dv = 0.0f;  // d vec = Wf[:, :OC]^T sum_dy
+        for (int o = 0; o < a.OCf; ++o) dv = fmaf(a.Wf[(size_t)o * a.ICf_total + c], sdy[o], dv);
+        if (a.dbeta) a.dbeta[c] = (a.accumulate ? a.dbeta[c] : 0.0f) + dv;
+        if (a.dgamma) a.dgamma[c] = (a.accumulate ? a.dgamma[c] : 0.0f) + dv * a.xhat[c];
+        const float d = dv * a.gis[c];  // 0 under batch statistics
+        dg[c] = d;
+        if (a.db) a.db[c] = (a.accumulate ? a.db[c] : 0.0f) + d;
+    }
+    __syncthreads();
+    if (a.dW)
+        for (int i = threadIdx.x; i < a.OC * a.IC; i += kGaveThreads) {
+            const int o = i / a.IC, l = i - o * a.IC;
+            a.dW[i] = (a.accumulate ? a.dW[i] : 0.0f) + dg[o] * a.pooled[(l / a.group) * a.slot + l % a.group];
+        }
+    if (a.dWf)
+        for (int i = threadIdx.x; i < a.OCf * a.OC; i += kGaveThreads) {
+            const int o = i / a.OC, c = i - o * a.OC;
+            float *d = a.dWf + (size_t)o * a.ICf_total + c;
+            *d = (a.accumulate_f ? *d : 0.0f) + sdy[o] * a.vec[c];
+        }
+    if (a.training) return;  // nothing flows back to x under batch statistics (dg == 0)
+    for (int ch = threadIdx.x; ch < 4 * a.c4_in; ch += kGaveThreads) {
+        const int s = ch / a.slot, in = ch - s * a.slot, l = s * a.group + in;
+        float d = 0.0f;
+        if (in < a.group && l < a.IC)
+            for (int o = 0; o < a.OC; ++o) d = fmaf(a.W[(size_t)o * a.IC + l], dg[o], d);
+        a.dpooled[ch] = d / (float)a.npix;
+    }
+}
+
+// planes[g][p] = vec[4g .. 4g+3] (add != 0: +=)
+__global__ __launch_bounds__(256) void train_bcast_planes_kernel(const float *vec, f32x4 *pl, int npix, int add)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    const f32x4 v = *reinterpret_cast<const f32x4 *>(vec + 4 * blockIdx.y);
+    f32x4 *d = pl + (size_t)blockIdx.y * npix + p;
+    *d = add ? *d + v : v;
+}
+
+// ---- the frame step's glue around the net (modules/pipeline.py:104-135, utils/loss.py:65-103) -------------------------
+// fused[r][k] = (max(w, 0) v + clamp(est, +-init)) / (max(w, 0) + 1) at pixel valid[r], sample k: the "weighted update"
+// of pipeline.py:107-116 followed by the masking of :121-127, from the plane layout [P][n] into the API's rows [Nv][P].
+struct FuseOutArgs {
+    const float *est, *fv, *fw;  // [P][n]
+    const long long *valid;      // [Nv] pixel indices
+    float *rows;                 // forward: fused [Nv][P]; backward: d fused [Nv][P] (read)
+    float *d_est;                // backward: [P][n], zeroed by the caller
+    int n, P;
+    long long n_valid;
+    float init;
+};
+
+__global__ __launch_bounds__(256) void train_fuse_output_kernel(const FuseOutArgs a)
+{
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.n_valid) return;
+    const long long p = a.valid[r];
+    for (int k = 0; k < a.P; ++k) {
+        const size_t i = (size_t)k * a.n + p;
+        float w = a.fw[i];
+        w = w < 0.0f ? 0.0f : w;                                        // pipeline.py:113-114
+        float e = a.est[i];
+        e = e < -a.init ? -a.init : (e > a.init ? a.init : e);           // :109-111 (NaN passes through like torch.clamp)
+        a.rows[(size_t)r * a.P + k] = (w * a.fv[i] + e) / (w + 1.0f);   // :116
+    }
+}
+
+__global__ __launch_bounds__(256) void train_fuse_output_bwd_kernel(const FuseOutArgs a)
+{
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.n_valid) return;
+    const long long p = a.valid[r];
+    for (int k = 0; k < a.P; ++k) {
+        const size_t i = (size_t)k * a.n + p;
+        float w = a.fw[i];
+        w = w < 0.0f ? 0.0f : w;
+        const float e = a.est[i];
+        const bool pass = !(e < -a.init) && !(e > a.init);  // torch.clamp: the gradient passes inside the closed interval
+        a.d_est[i] = pass ? a.rows[(size_t)r * a.P + k] / (w + 1.0f) : 0.0f;
+    }
+}
+
+// FusionLoss (utils/loss.py:65-103): w1 mean|e - t| + w2 mean (e - t)^2 + w3 mean_j (1 - cos_j), where the cosine runs
+// over the reference's RESHAPED sign tensors: column j of the [P, Nv] reinterpretation of the flat [Nv, P] array, i.e. the
+// flat elements i Nv + j, i < P.  Thread j owns exactly those elements, so it also carries their share of the first two
+// sums; per-block fp64 partial sums in a fixed tree, added in block order by the finishing block: bit-reproducible.
+constexpr int kLossThreads = 256;
+struct LossArgs {
+    const float *est, *tgt;   // flat [Nv * P]
+    long long nv;
+    int P;
+    float w1, w2, w3;
+    double *partial;          // [blocks][4]
+    float *loss;
+    const float *grad_out;    // backward: d loss (device scalar)
+    float *d_est;             // backward: [Nv * P]
+    int blocks;
+};
+
+__device__ __forceinline__ float loss_sign(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
+
+__global__ __launch_bounds__(kLossThreads) void train_loss_partial_kernel(const LossArgs a)
+{
+    __shared__ double red[kLossThreads / 64][3];
+    const long long j = (long long)blockIdx.x * kLossThreads + threadIdx.x;
+    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    if (j < a.nv) {
+        float dot = 0.0f, n1 = 0.0f, n2 = 0.0f;
+        for (int i = 0; i < a.P; ++i) {
+            const size_t f = (size_t)i * a.nv + j;
+            const float e = a.est[f], t = a.tgt[f], d = e - t;
+            s1 += (double)fabsf(d);
+            s2 += (double)(d * d);
+            const float se = loss_sign(e), st = loss_sign(t);
+            dot += se * st; n1 += se * se; n2 += st * st;
+        }
+        s3 = (double)(1.0f - dot / sqrtf((n1 + 1e-12f) * (n2 + 1e-12f)));
+    }
+    double v[3] = {s1, s2, s3};
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        double x = v[q];
+        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) a.partial[(size_t)blockIdx.x * 4 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+__global__ __launch_bounds__(64) void train_loss_finish_kernel(const LossArgs a)
+{
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int b = threadIdx.x; b < a.blocks; b += 64)  // lane l adds blocks l, l + 64, ... in order
+        for (int q = 0; q < 3; ++q) s[q] += a.partial[(size_t)b * 4 + q];
+    for (int q = 0; q < 3; ++q)
+        for (int off = 32; off > 0; off >>= 1) s[q] += __shfl_xor(s[q], off, 64);
+    if (threadIdx.x == 0) {
+        const double n = (double)a.nv * (double)a.P;
+        *a.loss = (float)((double)a.w1 * s[0] / n + (double)a.w2 * s[1] / n + (double)a.w3 * s[2] / (double)a.nv);
+    }
+}
+
+__global__ __launch_bounds__(256) void train_loss_bwd_kernel(const LossArgs a)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long total = a.nv * a.P;
+    if (i >= total) return;
+    const float g = *a.grad_out / (float)total;
+    const float d = a.est[i] - a.tgt[i];
+    a.d_est[i] = g * (a.w1 * loss_sign(d) + 2.0f * a.w2 * d);  // the sign-cosine term is piecewise constant
+}
+
+// ---- split-fp16 weights for the FORWARD convolutions, packed on the device -------------------------------------------
+// The forward pass's convolutions see BatchNorm-scaled activations of order one: the inference path's split-fp16 arithmetic
+// (three fp16 MFMAs per product block, fp32 accumulate, row-equilibrated weights: DESIGN.md 3.2) applies unchanged and runs
+// the MFMA part 5.3x faster than the fp32-input instruction.  Gradients (tiny, of unbounded range) stay on fp32 MFMAs.
+// Layout = finish()'s: [superstep][oc tile][hi | lo][lane] x 8 halfs, K entry G = 8 S + 2 (lane / 16) + j / 4.
+struct Pack16Args {
+    const float *w;        // [OC][ic_total][taps]
+    float *rs;             // [n_ot * 16] power-of-two row scales (written by the row-max pass)
+    float *rinv;           // [n_ot * 16] their inverses
+    _Float16 *wp;          // packed halves
+    int OC, IC, taps, group, slot, c4, nsteps, n_ot, oc_base, ic_base, ic_total;
+};
+
+__global__ __launch_bounds__(256) void train_pack16_rowscale_kernel(const Pack16Args a)
+{
+    __shared__ float red[4];
+    const int oc = blockIdx.x;  // row of THIS weight tensor
+    float mx = 0.0f;
+    const int n = a.IC * a.taps;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const int ic = i / a.taps, t = i - ic * a.taps;
+        mx = fmaxf(mx, fabsf(a.w[((size_t)oc * a.ic_total + a.ic_base + ic) * a.taps + t]));
+    }
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+        float rs = 1.0f;
+        if (mx > 0.0f && mx < 3.0e38f) {  // row_scale(): the largest magnitude of the row lands in [2^13, 2^14)
+            int e = 0;
+            (void)frexpf(mx, &e);
+            int k = 14 - e;
+            k = k > 100 ? 100 : (k < -100 ? -100 : k);
+            rs = ldexpf(1.0f, k);
+        }
+        a.rs[a.oc_base + oc] = rs;
+        a.rinv[a.oc_base + oc] = 1.0f / rs;
+    }
+}
+
+__global__ __launch_bounds__(256) void train_pack16_kernel(const Pack16Args a)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long total = (long)a.nsteps * a.n_ot * 512;  // (S, ot, lane, j)
+    if (i >= total) return;
+    const int j = (int)(i & 7), lane = (int)((i >> 3) & 63);
+    const long rest = i >> 9;
+    const int ot = (int)(rest % a.n_ot), S = (int)(rest / a.n_ot);
+    const int row = ot * 16 + (lane & 15), G = 8 * S + 2 * (lane >> 4) + (j >> 2);
+    const int oc = row - a.oc_base;
+    if (oc < 0 || oc >= a.OC || G >= a.taps * a.c4) return;  // (the buffer starts zeroed; other tensors of a stack own the other rows)
+    const int t = G / a.c4, ch = 4 * (G - t * a.c4) + (j & 3);
+    const int ic = train_unslot(ch, a.group, a.slot, a.IC);
+    float v = 0.0f;
+    if (ic >= 0) v = a.rs[row] * a.w[((size_t)oc * a.ic_total + a.ic_base + ic) * a.taps + t];
+    const _Float16 hi = (_Float16)v;
+    const _Float16 lo = (_Float16)(v - (float)hi);
+    const size_t base = ((size_t)S * a.n_ot + ot) * 2 * 64 * 8;
+    a.wp[base + (size_t)lane * 8 + j] = hi;
+    a.wp[base + 64 * 8 + (size_t)lane * 8 + j] = lo;
+}
+
+// Backward-data form of the same: rows = the convolution's INPUT channels (physical, chunk of <= 128 rows starting at
+// row0), K entry (tap, 4 output channels) <- w[oc][ic][taps - 1 - tap]; a stack of up to four weight tensors shares the K
+// axis (kper output channels each: the four branch entries of a VortexPooling).
+struct Pack16TArgs {
+    const float *w[4];     // [OC][ic_total][taps] each
+    int n_src, kper;       // K channels [b * kper, b * kper + OC) belong to tensor b
+    float *rs, *rinv;      // [rows of the whole layer, padded]
+    _Float16 *wp;          // this chunk's packed halves
+    int OC, IC, taps, group, slot, c4k, nsteps, n_ot, row0, rows, ic_base, ic_total;
+};
+
+__global__ __launch_bounds__(256) void train_pack16t_rowscale_kernel(const Pack16TArgs a)
+{
+    __shared__ float red[4];
+    const int r = blockIdx.x;  // physical input channel
+    const int ic = train_unslot(r, a.group, a.slot, a.IC);
+    float mx = 0.0f;
+    if (ic >= 0)
+        for (int b = 0; b < a.n_src; ++b)
+            for (int i = threadIdx.x; i < a.OC * a.taps; i += 256) {
+                const int oc = i / a.taps, t = i - oc * a.taps;
+                mx = fmaxf(mx, fabsf(a.w[b][((size_t)oc * a.ic_total + a.ic_base + ic) * a.taps + t]));
+            }
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+        float rs = 1.0f;
+        if (mx > 0.0f && mx < 3.0e38f) {
+            int e = 0;
+            (void)frexpf(mx, &e);
+            int k = 14 - e;
+            k = k > 100 ? 100 : (k < -100 ? -100 : k);
+            rs = ldexpf(1.0f, k);
+        }
+        a.rs[r] = rs;
+        a.rinv[r] = 1.0f / rs;
+    }
+}
+
+__global__ __launch_bounds__(256) void train_pack16t_kernel(const Pack16TArgs a)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long total = (long)a.nsteps * a.n_ot * 512;
+    if (i >= total) return;
+    const int j = (int)(i & 7), lane = (int)((i >> 3) & 63);
+    const long rest = i >> 9;
+    const int ot = (int)(rest % a.n_ot), S = (int)(rest / a.n_ot);
+    const int row = a.row0 + ot * 16 + (lane & 15), G = 8 * S + 2 * (lane >> 4) + (j >> 2);
+    float v = 0.0f;
+    if (row < a.rows && G < a.taps * a.c4k) {
+        const int tap = G / a.c4k, ch = 4 * (G - tap * a.c4k) + (j & 3);
+        const int b = ch / a.kper, oc = ch - b * a.kper;
+        const int ic = train_unslot(row, a.group, a.slot, a.IC);
+        if (b < a.n_src && oc < a.OC && ic >= 0)
+            v = a.rs[row] * a.w[b][((size_t)oc * a.ic_total + a.ic_base + ic) * a.taps + (a.taps - 1 - tap)];
+    }
+    const _Float16 hi = (_Float16)v;
+    const _Float16 lo = (_Float16)(v - (float)hi);
+    const size_t base = ((size_t)S * a.n_ot + ot) * 2 * 64 * 8;
+    a.wp[base + (size_t)lane * 8 + j] = hi;
+    a.wp[base + 64 * 8 + (size_t)lane * 8 + j] = lo;
+}
 
 }  // namespace ojf
-
-// ---- C ABI ----------------------------------------------------------------------------------------------------------
-OJF_API size_t ojf_train_packed_floats(int c_out_phys, int c_in_phys, int ksize)
-{
-    using namespace ojf;
-    if (c_out_phys < 1 || c_in_phys < 4 || c_in_phys % 4 || (ksize != 1 && ksize != 3)) return 0;
-    const int n_ot = round_up(round_up(c_out_phys, 16) / 16, kNT), nsteps = (ksize * ksize * (c_in_phys / 4) + 3) / 4;
-    if (nsteps > kMaxSteps) return 0;
-    return (size_t)n_ot * (nsteps + kPadSteps) * 256;
-}
-
-OJF_API int ojf_train_pack(const float *w, const float *bias, int OC, int IC, int ksize, int group, int slot, int c_in_phys,
-                           int c_out_phys, int transposed, float *packed, float *bias_packed, ojf_stream_t stream)
-{
-    using namespace ojf;
-    if (!w || !packed || OC < 1 || IC < 1 || group < 1 || slot < group) return fail("ojf_train_pack: bad argument");
-    // forward: rows = output channels (c_out_phys), K = input planes (c_in_phys); transposed: rows = input planes, K = output channels
-    const int rows = transposed ? c_in_phys : c_out_phys, kch = transposed ? c_out_phys : c_in_phys;
-    if (ojf_train_packed_floats(rows, kch, ksize) == 0) return fail("ojf_train_pack: unsupported layer shape (K too long or channels not padded to 4)");
-    PackArgs a;
-    a.w = w; a.bias = transposed ? nullptr : bias; a.wp = packed; a.bp = transposed ? nullptr : bias_packed;
-    a.OC = OC; a.IC = IC; a.taps = ksize * ksize; a.group = group; a.slot = slot;
-    a.c4 = kch / 4; a.nsteps = (a.taps * a.c4 + 3) / 4; a.n_ot = round_up(round_up(rows, 16) / 16, kNT); a.transposed = transposed ? 1 : 0;
-    a.oc_base = 0; a.partial = 0; a.ic_base = 0; a.ic_total = IC;
-    const long total = (long)a.n_ot * (a.nsteps + kPadSteps) * 256;
-    hipLaunchKernelGGL(train_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), a);
-    return check_hip(hipGetLastError(), "train_pack_kernel launch");
-}
-
-OJF_API int ojf_train_conv(const float *in, int in_g0, int c_in_phys, float *out, int out_g0, int c_out_phys, const float *packed,
-                           const float *bias_packed, int ksize, int dil, int h, int w, ojf_stream_t stream)
-{
-    using namespace ojf;
-    if (!in || !out || !packed) return fail("ojf_train_conv: null pointer argument");
-    if (ojf_train_packed_floats(c_out_phys, c_in_phys, ksize) == 0 || dil < 1 || h < 1 || w < 1) return fail("ojf_train_conv: unsupported shape");
-    if (!g_train_zero_bias) {
-        OJF_HIP(hipMalloc(reinterpret_cast<void **>(&g_train_zero_bias), 4096 * sizeof(float)));
-        OJF_HIP(hipMemset(g_train_zero_bias, 0, 4096 * sizeof(float)));
-        OJF_HIP(hipStreamSynchronize(nullptr));
-    }
-    const int taps = ksize * ksize, c4 = c_in_phys / 4, nsteps = (taps * c4 + 3) / 4;
-    const int n_ot = round_up(round_up(c_out_phys, 16) / 16, kNT), og_total = round_up(c_out_phys, 4) / 4;
-    if (n_ot * 16 > 4096) return fail("ojf_train_conv: too many output channels");
-    for (int ot0 = 0; ot0 < n_ot; ot0 += 8) {  // a launch covers up to 8 output tiles per wave
-        const int nt = n_ot - ot0 < 8 ? n_ot - ot0 : 8;
-        ConvArgs a;
-        a.ovf = nullptr; a.accum = 0; a.dscale = nullptr;
-        a.in = planes(in); a.out = planes(out); a.out_rows = nullptr;
-        a.wp = planes(packed) + (size_t)ot0 * (nsteps + kPadSteps) * 64;
-        a.bias = (bias_packed ? bias_packed : g_train_zero_bias) + (size_t)ot0 * 16; a.rinv = nullptr;
-        a.in_g0 = in_g0; a.out_g0 = out_g0 + ot0 * 4; a.rows_stride = 0; a.rows_n = 0;
-        a.h = h; a.w = w; a.npix = h * w; a.taps = taps; a.dil = dil; a.c4 = c4; a.nsteps = nsteps;
-        a.w_magic = 0; a.c4_magic = 0;
-        const int left = og_total - ot0 * 4;
-        a.og_store = left < nt * 4 ? left : nt * 4;
-        a.act = OJF_ACT_NONE; a.act_n = 0; a.scale = 1.0f;
-        if (launch_conv_args(&a, 1, nt, as_stream(stream), OJF_ARITH_F32)) return -2;
-    }
-    return 0;
-}
-
-OJF_API int ojf_train_avgpool3(const float *in, float *out, int c_phys, int h, int w, ojf_stream_t stream)
-{
-    using namespace ojf;
-    if (!in || !out || in == out || c_phys < 4 || c_phys % 4 || h < 1 || w < 1) return fail("ojf_train_avgpool3: bad argument");
-    const int bx = (h * w + 255) / 256 < 256 ? (h * w + 255) / 256 : 256;
-    hipLaunchKernelGGL(train_avgpool3_kernel, dim3(bx, c_phys / 4), dim3(256), 0, as_stream(stream), planes(in), planes(out), h, w);
-    return check_hip(hipGetLastError(), "train_avgpool3_kernel launch");
-}
-
-// Per-channel sums over the frame as kTrainSlabs partial rows ([slab][c_phys / 4][8] doubles: sums in [0..3], sums of
-// squares in [4..7]; the caller adds the rows): the global-average pooling of a VortexPooling in the training path.
-OJF_API int ojf_train_channel_sums(const float *y, int y_g0, int c_phys, int h, int w, double *partial, ojf_stream_t stream)
-{
-    using namespace ojf;
-    if (!y || !partial || c_phys < 4 || c_phys % 4 || h < 1 || w < 1) return fail("ojf_train_channel_sums: bad argument");
-    hipLaunchKernelGGL(train_stats_partial_kernel, dim3(kTrainSlabs, c_phys / 4), dim3(256), 0, as_stream(stream), planes(y), y_g0, h * w, partial);
-    return check_hip(hipGetLastError(), "train_stats_partial_kernel launch");
-}
-
-OJF_API size_t ojf_train_partial_doubles(int c_phys) { return (size_t)ojf::kTrainSlabs * (c_phys / 4) * 8; }
-
-static ojf::BnActArgs train_bn_args(const float *y, int y_g0, int c_phys, int C, int h, int w, const float *mean, const float *invstd,
-                                    const float *gamma, const float *beta, const float *drop, int act, float scale, int has_bn, int training)
-{
-    ojf::BnActArgs a;
-    a.y = ojf::planes(y); a.out = nullptr; a.dout = nullptr; a.dy = nullptr;
-    a.mean = mean; a.invstd = invstd; a.gamma = gamma; a.beta = beta; a.drop = drop; a.partial = nullptr;
-    a.y_g0 = y_g0; a.out_g0 = 0; a.dout_g0 = 0; a.dy_g0 = 0; a.c4 = c_phys / 4; a.C = C; a.npix = h * w; a.act = act;
-    a.has_bn = has_bn; a.training = training; a.scale = scale;
-    a.mean_out = a.invstd_out = a.running_mean = a.running_var = nullptr; a.momentum = 0.0f; a.eps = 0.0f;
-    a.dgamma = a.dbeta = a.dbias = nullptr; a.sum_dy = nullptr; a.accumulate = 0; a.bnd = nullptr; a.bnd_stride = 0; a.dy_scale_out = nullptr;
-    return a;
-}
-
-OJF_API int ojf_train_bn_act(const float *y, int y_g0, float *out, int out_g0, int c_phys, int C, int h, int w, const float *gamma,
-                             const float *beta, const float *drop, int act, float scale, int has_bn, int training, float momentum,
-                             float eps, float *running_mean, float *running_var, double *partial, float *mean, float *invstd,
-                             ojf_stream_t stream)
-{
-    using namespace ojf;
-    if (!y || !out || c_phys % 4 || C > c_phys) return fail("ojf_train_bn_act: bad argument");
-    if (has_bn && (!mean || !invstd || !partial || !running_mean || !running_var))
-        return fail("ojf_train_bn_act: BatchNorm needs mean / invstd outputs, the partial-sum scratch and the running statistics");
-    hipStream_t st = as_stream(stream);
-    if (has_bn && training)
-        hipLaunchKernelGGL(train_stats_partial_kernel, dim3(kTrainSlabs, c_phys / 4), dim3(256), 0, st, planes(y), y_g0, h * w, partial);
-    BnActArgs a = train_bn_args(y, y_g0, c_phys, C, h, w, nullptr, nullptr, gamma, beta, drop, act, scale, has_bn, training ? 1 : 0);
-    a.out = planes(out); a.out_g0 = out_g0; a.partial = partial;
-    a.mean_out = mean; a.invstd_out = invstd; a.running_mean = running_mean; a.running_var = running_var; a.momentum = momentum; a.eps = eps;
-    const int bx = (h * w + 255) / 256 < 128 ? (h * w + 255) / 256 : 128;
-    hipLaunchKernelGGL(train_bn_act_fwd_kernel, dim3(bx, c_phys / 4), dim3(256), 0, st, BnGroup{{a, a, a, a}});
-    return check_hip(hipGetLastError(), "train_bn_act kernels launch");
-}
-
-OJF_API int ojf_train_bn_act_bwd(const float *y, int y_g0, const float *dout, int dout_g0, float *dy, int dy_g0, int c_phys, int C,
-                                 int h, int w, const float *mean, const float *invstd, const float *gamma, const float *beta,
-                                 const float *drop, int act, float scale, int has_bn, int training, double *partial,
-                                 float *dgamma, float *dbeta, float *dbias, int accumulate, ojf_stream_t stream)
-{
-    using namespace ojf;
-    if (!y || !dout || !dy || !partial || c_phys % 4 || C > c_phys || (has_bn && (!mean || !invstd)))
-        return fail("ojf_train_bn_act_bwd: bad argument");
-    hipStream_t st = as_stream(stream);
-    BnActArgs a = train_bn_args(y, y_g0, c_phys, C, h, w, mean, invstd, gamma, beta, drop, act, scale, has_bn, training);
-    a.dout = planes(dout); a.dout_g0 = dout_g0; a.dy = planes(dy); a.dy_g0 = dy_g0; a.partial = partial;
-    a.dgamma = dgamma; a.dbeta = dbeta; a.dbias = dbias; a.accumulate = accumulate ? 1 : 0;
-    const BnGroup grp{{a, a, a, a}};
-    hipLaunchKernelGGL(train_bn_bwd_reduce_kernel, dim3(kTrainSlabs, c_phys / 4), dim3(256), 0, st, grp);
-    const int bx = (h * w + 255) / 256 < 128 ? (h * w + 255) / 256 : 128;
-    hipLaunchKernelGGL(train_bn_bwd_apply_kernel, dim3(bx, c_phys / 4), dim3(256), 0, st, grp);
-    return check_hip(hipGetLastError(), "train_bn_bwd kernels launch");
-}
-
-namespace ojf {
-struct WgradPlan { int ocp, icp, slabs; };
-static WgradPlan wgrad_plan(int c_out_phys, int c_in_phys, int taps, int npix, int units = 1)
-{
-    WgradPlan p;
-    p.ocp = round_up(c_out_phys, 32);
-    p.icp = round_up(c_in_phys, 32);
-    // two waves per SIMD (2048 one-wave blocks) hide the load latency; at most 256 slabs for the reduction
-    const int waves = units * taps * (p.ocp / 32) * (p.icp / 32);  // (units: layers of identical shape sharing one grouped launch)
-    int slabs = (2048 + waves - 1) / waves;
-    slabs = slabs > 256 ? 256 : slabs;
-    const int max_slabs = (npix + 63) / 64;
-    slabs = slabs > max_slabs ? max_slabs : slabs;
-    p.slabs = slabs < 1 ? 1 : slabs;
-    return p;
-}
-}  // namespace ojf
-
-OJF_API size_t ojf_train_wgrad_partial_floats(int c_out_phys, int c_in_phys, int ksize, int h, int w)
-{
-    const ojf::WgradPlan p = ojf::wgrad_plan(c_out_phys, c_in_phys, ksize * ksize, h * w);
-    return (size_t)p.slabs * ksize * ksize * p.ocp * p.icp;
-}
-
-OJF_API int ojf_train_wgrad(const float *x, int x_g0, int c_in_phys, const float *dy, int dy_g0, int c_out_phys, int OC, int IC,
-                            int ksize, int dil, int group, int slot, int h, int w, float *partial, float *dw, int accumulate, ojf_stream_t stream)
-{
-    using namespace ojf;
-    if (!x || !dy || !partial || !dw || c_in_phys % 4 || c_out_phys % 4 || (ksize != 1 && ksize != 3) || OC > c_out_phys)
-        return fail("ojf_train_wgrad: bad argument");
-    hipStream_t st = as_stream(stream);
-    const int taps = ksize * ksize;
-    const WgradPlan p = wgrad_plan(c_out_phys, c_in_phys, taps, h * w);
-    WgradArgs a;
-    a.x = planes(x); a.dy = planes(dy); a.partial = partial; a.x_g0 = x_g0; a.c4_in = c_in_phys / 4; a.dy_g0 = dy_g0; a.c4_out = c_out_phys / 4;
-    a.h = h; a.w = w; a.npix = h * w; a.taps = taps; a.dil = dil; a.slabs = p.slabs; a.ocp = p.ocp; a.icp = p.icp;
-    a.ovf = nullptr;
-    hipLaunchKernelGGL(train_wgrad_mfma_kernel<false>, dim3(p.slabs, (p.ocp / 32) * (p.icp / 32), taps), dim3(64), 0, st,
-                       WgradGroup{{a, a, a, a}, (p.ocp / 32) * (p.icp / 32)}, div_magic(w, (uint64_t)h * w + 2 * kWgChunk));
-    WgradReduceArgs r;
-    r.partial = partial; r.dw = dw; r.slabs = p.slabs; r.taps = taps; r.ocp = p.ocp; r.icp = p.icp; r.OC = OC; r.IC = IC;
-    r.group = group; r.slot = slot; r.c_in_phys = c_in_phys; r.accumulate = accumulate ? 1 : 0; r.oc_base = 0; r.ic_base = 0; r.ic_total = IC; r.dy_scale = nullptr;
-    const long total = (long)taps * OC * c_in_phys * 8;
-    hipLaunchKernelGGL(train_wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, WgradReduceGroup{{r, r, r, r}});
-    return check_hip(hipGetLastError(), "train_wgrad kernels launch");
-}

@@ -246,14 +246,14 @@ class HipTrainNet:
         _lib.require_gpu()
         self.net = net
         self.inplace_grads = bool(inplace_grads)  # see _grad_target
-        # executor: the whole forward / backward pass as two libojf calls (ojf_trainer_*, csrc/ojf_train_net.h: C++ layer
+        # executor: the whole forward / backward pass as two libojf calls (ojf_trainer_*, csrc/ojf_train.hip: C++ layer
         # walk, grouped VortexPooling branches) behind ONE autograd node; False = one autograd node per layer unit (the
         # round-2 path, kept for A/B runs and for graph=True)
         self.executor = bool(executor)
         # Convolutions of the executor.  ``arithmetic``: 'f16x3' (split-fp16, the inference arithmetic) | 'f32' for the
         # forward pass.  ``backward_arithmetic`` (FUSION_MODEL.train_arithmetic_bwd; default = ``arithmetic``): under a
         # split-fp16 forward, backward-data and the weight gradients run in split-fp16 as well - every dy tensor is stored
-        # under a power of two derived in the SAME pass from a guaranteed bound on its magnitude (csrc/ojf_net_train.h
+        # under a power of two derived in the SAME pass from a guaranteed bound on its magnitude (csrc/ojf_train_kernels.h
         # BnActArgs::bnd), so no gradient can leave the fp16 range whatever the loss scale; 'f32' keeps the backward
         # convolutions on the fp32-input MFMA path.
         self.arithmetic = arithmetic

@@ -19,6 +19,7 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 
 def test_restated_constants_are_the_launch_sites():
     net = open(os.path.join(CSRC, 'ojf_net.hip')).read()
+    conv = open(os.path.join(CSRC, 'ojf_net_conv.h')).read()  # what the net shares with the training unit
     chain = open(os.path.join(CSRC, 'ojf_net_chain.h')).read()
     common = open(os.path.join(CSRC, 'ojf_common.h')).read()
 
@@ -31,7 +32,7 @@ def test_restated_constants_are_the_launch_sites():
     assert const(net, 'persist_bpc') == ec.PERSIST_BPC
     assert const(net, 'kChainWaves') == ec.CHAIN_WAVES
     assert const(net, 'kSumBlocks') == ec.SUM_BLOCKS
-    assert const(net, 'kNT') == ec.K_NT
+    assert const(conv, 'kNT') == ec.K_NT
     assert (const(chain, 'kChainNG'), const(chain, 'kChainMaxLayers')) == (ec.CHAIN_NG, ec.CHAIN_MAX_LAYERS)
     assert 'kChainSyncInts = kChainFlags0 + %d;' % ec.CHAIN_MAX_TILES in net
     # the banding threshold and the superstep chunk of launch_conv_args

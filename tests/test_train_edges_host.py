@@ -20,41 +20,44 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 
 
 def test_restated_constants_are_the_sources():
-    train = open(os.path.join(CSRC, 'ojf_net_train.h')).read()
-    net = open(os.path.join(CSRC, 'ojf_train_net.h')).read()
+    # the training unit: device kernels in the header, plan / launches / C entries in the .hip file
+    kern = open(os.path.join(CSRC, 'ojf_train_kernels.h')).read()
+    host = open(os.path.join(CSRC, 'ojf_train.hip')).read()
 
     def const(src, name):
         m = re.search(r'constexpr int [^;]*\b%s = (\d+)[,;]' % name, src)
         assert m, name
         return int(m.group(1))
 
-    assert const(train, 'kTrainSlabs') == ec.TRAIN_SLABS
-    assert const(train, 'kWgChunk') == ec.WG_CHUNK
-    assert (const(net, 'kTpW'), const(net, 'kTpH')) == (ec.TP_W, ec.TP_H)
-    assert const(net, 'kLossThreads') == ec.LOSS_THREADS
+    assert const(kern, 'kTrainSlabs') == ec.TRAIN_SLABS
+    assert const(kern, 'kWgChunk') == ec.WG_CHUNK
+    assert (const(kern, 'kTpW'), const(kern, 'kTpH')) == (ec.TP_W, ec.TP_H)
+    assert const(kern, 'kLossThreads') == ec.LOSS_THREADS
     # the two reduction loops (statistics, BatchNorm backward): four loads 256 apart, step 1024, tail step 256
-    assert len(re.findall(r'for \(; p \+ %d < p1; p \+= %d\)' % (ec.UNROLL_LAST, ec.UNROLL_STEP), train)) == 2
-    assert len(re.findall(r'for \(; p < p1; p \+= %d\)' % ec.BLOCK, train)) == 2
-    assert len(re.findall(r'\[p\], \w+\[p \+ 256\], \w+\[p \+ 512\], \w+\[p \+ %d\]\}' % ec.UNROLL_LAST, train)) == 3
-    assert len(re.findall(r'const int per = \(a?\.?npix \+ kTrainSlabs - 1\) / kTrainSlabs;', train)) == 2
-    assert len(re.findall(r'dim3\(kTrainSlabs, c_phys / 4\), dim3\(%d\)' % ec.BLOCK, train)) == 3
+    assert len(re.findall(r'for \(; p \+ %d < p1; p \+= %d\)' % (ec.UNROLL_LAST, ec.UNROLL_STEP), kern)) == 2
+    assert len(re.findall(r'for \(; p < p1; p \+= %d\)' % ec.BLOCK, kern)) == 2
+    assert len(re.findall(r'\[p\], \w+\[p \+ 256\], \w+\[p \+ 512\], \w+\[p \+ %d\]\}' % ec.UNROLL_LAST, kern)) == 3
+    assert len(re.findall(r'const int per = \(a?\.?npix \+ kTrainSlabs - 1\) / kTrainSlabs;', kern)) == 2
+    assert len(re.findall(r'dim3\(kTrainSlabs, c_phys / 4\), dim3\(%d\)' % ec.BLOCK, host)) == 3
     # the streaming loops: bx = min(ceil(npix / 256), 128) at the two C entries and in the executor; first3, middle, tail
-    bx = r'const int bx = \((?:h \* w|t->npix) \+ 255\) / 256 < %d \? \((?:h \* w|t->npix) \+ 255\) / 256 : %d;' % (ec.STREAM_MAX_BX, ec.STREAM_MAX_BX)
-    assert len(re.findall(bx, train)) == 2 and len(re.findall(bx, net)) >= 1
-    assert train.count('const bool first3 = p + 2 * stride < a.npix;') == 2
-    assert train.count('for (; p + 2 * stride < a.npix; p += 3 * stride)') == 2
-    assert train.count('for (; p < a.npix; p += stride)') == 2
+    # (both live in ojf_train.hip now: the C entries size the frame as h * w, the executor as t->npix)
+    bx = r'const int bx = \(%s \+ 255\) / 256 < %d \? \(%s \+ 255\) / 256 : %d;'
+    entry_bx, executor_bx = (bx % (n, ec.STREAM_MAX_BX, n, ec.STREAM_MAX_BX) for n in (r'h \* w', r't->npix'))
+    assert len(re.findall(entry_bx, host)) == 2 and len(re.findall(executor_bx, host)) >= 1
+    assert kern.count('const bool first3 = p + 2 * stride < a.npix;') == 2
+    assert kern.count('for (; p + 2 * stride < a.npix; p += 3 * stride)') == 2
+    assert kern.count('for (; p < a.npix; p += stride)') == 2
     # the weight gradient's plan and the kernel's slab length
-    assert 'int slabs = (%d + waves - 1) / waves;' % ec.WG_WAVES in train and 'slabs = slabs > %d ? %d : slabs;' % (ec.WG_MAX_SLABS, ec.WG_MAX_SLABS) in train
-    assert 'const int max_slabs = (npix + 63) / 64;' in train and ec.WG_CHUNK == 64
-    assert 'p.ocp = round_up(c_out_phys, %d);' % ec.WG_TILE in train and 'p.icp = round_up(c_in_phys, %d);' % ec.WG_TILE in train
-    assert 'const int per = ((a.npix + a.slabs - 1) / a.slabs + 1) & ~1;' in train
-    assert 'const int n_og = min(8, a.c4_out - ot * 8), n_ig = min(8, a.c4_in - it * 8);' in train
+    assert 'int slabs = (%d + waves - 1) / waves;' % ec.WG_WAVES in host and 'slabs = slabs > %d ? %d : slabs;' % (ec.WG_MAX_SLABS, ec.WG_MAX_SLABS) in host
+    assert 'const int max_slabs = (npix + 63) / 64;' in host and ec.WG_CHUNK == 64
+    assert 'p.ocp = round_up(c_out_phys, %d);' % ec.WG_TILE in host and 'p.icp = round_up(c_in_phys, %d);' % ec.WG_TILE in host
+    assert 'const int per = ((a.npix + a.slabs - 1) / a.slabs + 1) & ~1;' in kern
+    assert 'const int n_og = min(8, a.c4_out - ot * 8), n_ig = min(8, a.c4_in - it * 8);' in kern
     # the small launches
-    assert 'const int bx = (h * w + 255) / 256 < %d ? (h * w + 255) / 256 : %d;' % (ec.POOL_MAX_BX, ec.POOL_MAX_BX) in train
-    assert 'static inline dim3 px_grid(int npix, int gy) { return dim3((unsigned)((npix + 255) / 256), (unsigned)gy); }' in net
-    assert 'for (int b = threadIdx.x; b < a.blocks; b += %d)' % ec.LOSS_FINISH_LANES in net
-    assert 'for (int ot0 = 0; ot0 < n_ot; ot0 += 8)' in train
+    assert 'const int bx = (h * w + 255) / 256 < %d ? (h * w + 255) / 256 : %d;' % (ec.POOL_MAX_BX, ec.POOL_MAX_BX) in host
+    assert 'static inline dim3 px_grid(int npix, int gy) { return dim3((unsigned)((npix + 255) / 256), (unsigned)gy); }' in host
+    assert 'for (int b = threadIdx.x; b < a.blocks; b += %d)' % ec.LOSS_FINISH_LANES in kern
+    assert 'for (int ot0 = 0; ot0 < n_ot; ot0 += 8)' in host
 
 
 @pytest.mark.parametrize('npix', [1, 2, 63, 65, 255, 257, 1023, 16448, 51200, 65536, 114700])

@@ -473,6 +473,31 @@ def test_gradient_jumps_of_any_size_stay_in_range(cuda, inplace, training):
     tn(x)  # and the next forward pass is not refused (round 3: a set flag surfaced there, for the rest of the process)
 
 
+def test_a_guard_raised_by_the_inference_net_refuses_the_trainer_until_checked(cuda):
+    """One range-guard flag per process, seen by every unit of the library: the inference net raises it (as in
+    test_net_gpu.test_f16x3_range_guard: un-normalised weight channels through a split-fp16 engine), and the training executor,
+    compiled as a unit of its own, must see THAT flag - its next split-fp16 forward pass is refused until the event has been
+    reported through the engine's check(), and afterwards gives the bits it gave before the event."""
+    from online_joint_depthfusion_and_semantic_amd import _lib
+    from online_joint_depthfusion_and_semantic_amd.engine import FusionNetEngine
+    from test_net_gpu import _large_weight_inputs, _run, seeded_net
+    h, w = 24, 40
+    net = _net('v3', False, h, w).to(cuda).eval()
+    x, _ = _guard_inputs(cuda, h, w, False)
+    tn = HipTrainNet(net)
+    before = tn(x).detach().clone()
+    eng = FusionNetEngine(seeded_net('v3', False, h, w, seed=3), h, w, cuda, arithmetic='f16x3')
+    _run(eng, _large_weight_inputs(h, w), h, w, cuda)
+    torch.cuda.synchronize(cuda)  # (the forward entries poll the flag's host mirror without synchronising: the kernels must have run)
+    with pytest.raises(_lib.OjfError, match='fp16 range'):
+        tn(x)
+    with pytest.raises(_lib.OjfError, match='fp16 range'):
+        eng.check()
+    eng.check()  # the check cleared the flag
+    assert torch.equal(before, tn(x).detach())
+    eng.close()
+
+
 def test_backward_arithmetic_f32_keeps_the_backward_convolutions_on_fp32_mfma(cuda):
     """FUSION_MODEL.train_arithmetic_bwd: 'f32' keeps every backward pass on the fp32-input MFMA path (the choice is
     exposed); its gradients agree with the split-fp16 backward to the fp32 bar."""

@@ -1,6 +1,6 @@
 """The training kernels' frame-dependent decisions, restated in plain Python, and the rows that pin them.
 
-csrc/ojf_net_train.h and csrc/ojf_train_net.h cut a frame of npix = h * w pixels in seven ways; each is restated here without the
+csrc/ojf_train_kernels.h and csrc/ojf_train.hip cut a frame of npix = h * w pixels in seven ways; each is restated here without the
 package (tests/test_train_edges_host.py reads the constants back from the sources and checks the two C entries that expose a plan):
 
   stats_plan     train_stats_partial_body, train_bn_bwd_reduce_kernel, ojf_train_channel_sums: 64 slabs of ceil(npix / 64) pixels,

@@ -1,7 +1,7 @@
 // Profiling-only microbenchmark (not product, not a test): the five dense Blocks of a head as five dense_pair_kernel
 // launches (fp32 planes) against ONE dense_chain_kernel launch (split planes): max |difference| per Block and us per chain.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off [-DOJF_CHAIN_TIMING] -c tools/microbench/chain_bench.hip -o /tmp/cb.o
-//        hipcc --offload-arch=gfx950 /tmp/cb.o online_joint_depthfusion_and_semantic_amd/csrc/ojf_api.o -o tools/microbench/chain_bench.bin
+//        hipcc --offload-arch=gfx950 /tmp/cb.o online_joint_depthfusion_and_semantic_amd/csrc/ojf_api.o online_joint_depthfusion_and_semantic_amd/csrc/ojf_guard.o -o tools/microbench/chain_bench.bin
 #include <cmath>
 #include <cstdio>
 #include <cstring>

@@ -1,6 +1,6 @@
 // Profiling-only microbenchmark (not product, not a test): times conv_mfma_kernel variants on one layer shape.
-// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I. tests/microbench/conv_bench.hip \
-//        online_joint_depthfusion_and_semantic_amd/csrc/ojf_api.o -o gpurun_out/conv_bench   (see run_conv_bench.sh)
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I. tools/microbench/conv_bench.hip \
+//        online_joint_depthfusion_and_semantic_amd/csrc/ojf_api.o online_joint_depthfusion_and_semantic_amd/csrc/ojf_guard.o -o tools/microbench/conv_bench.exe
 #include <cstdio>
 #include <vector>
 #include "../../online_joint_depthfusion_and_semantic_amd/csrc/ojf_net.hip"

@@ -2,7 +2,7 @@
 // (conv_f16x3_kernel<MT, NT, SKIP, ABL>) next to the fp32-MFMA kernel on one layer shape.
 //   ABL bits: 1 no activation loads, 2 no LDS weight reads, 4 no MFMA, 8 no fp16 split
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I include -c tests/microbench/conv_f16x3_bench.hip -o /tmp/b.o
-//        hipcc --offload-arch=gfx950 /tmp/b.o online_joint_depthfusion_and_semantic_amd/csrc/ojf_api.o -o tests/microbench/conv_f16x3_bench.bin
+//        hipcc --offload-arch=gfx950 /tmp/b.o online_joint_depthfusion_and_semantic_amd/csrc/ojf_api.o online_joint_depthfusion_and_semantic_amd/csrc/ojf_guard.o -o tests/microbench/conv_f16x3_bench.bin
 #include <cmath>
 #include <cstdio>
 #include <random>

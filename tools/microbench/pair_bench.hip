@@ -1,7 +1,7 @@
 // Profiling-only microbenchmark (not product, not a test): dense_pair_kernel per dense Block i = 0..4 at 320x240,
 // wall time per launch and s_memtime phase stamps of one block (compile with -DOJF_PAIR_TIMING).
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DOJF_PAIR_TIMING -c tools/microbench/pair_bench.hip -o /tmp/pb.o
-//        hipcc --offload-arch=gfx950 /tmp/pb.o online_joint_depthfusion_and_semantic_amd/csrc/ojf_api.o -o tools/microbench/pair_bench.bin
+//        hipcc --offload-arch=gfx950 /tmp/pb.o online_joint_depthfusion_and_semantic_amd/csrc/ojf_api.o online_joint_depthfusion_and_semantic_amd/csrc/ojf_guard.o -o tools/microbench/pair_bench.bin
 #include <cmath>
 #include <cstdio>
 #include <random>
