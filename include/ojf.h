@@ -946,6 +946,54 @@ int ojf_mesh_simplify(const float *vertices_dev, int nv, const int32_t *faces_de
                       int32_t *out_faces_dev, int32_t *face_source_dev, uint32_t face_capacity, uint32_t *counts_dev,
                       ojf_stream_t stream);
 
+/* ---- REGISTER (the rigid transform between two fused scenes; definition: csrc/ojf_register.hip) ----------
+ * Volume-to-volume registration on signed distance fields.  The MOVING scene is an fp16 TSDF [mX,mY,mZ] (metres) with its
+ * weights, the FIXED scene either an fp16 TSDF + weights [fX,fY,fZ] (fixed_field_dev NULL) or an f32 field [fX,fY,fZ] in metres
+ * (fixed_tsdf_dev and fixed_weights_dev NULL; a non-finite voxel is "no value").  Origins f64[3] and resolutions are those of
+ * the volume frame (voxel (i,j,k) has its centre at origin + (i+0.5, j+0.5, k+0.5) resolution) and are rounded to fp32: callers
+ * shift both worlds so that the scenes lie about their origins (registration.py does).  The pose P f64[12] (3x4 row-major) maps
+ * points of the moving world to the fixed world - the `transform` of ojf_resample_volumes with destination = moving.
+ * ojf_register_select: the points of a volume - voxels whose three indices are multiples of `stride` (>= 1), that are observed
+ *   (weight > 0, TSDF not NaN) and have |TSDF| < band (> 0) - as u32 linear indices in increasing order.  count_dev[0] receives
+ *   their number; list_dev (or NULL: count only) the first `capacity` of them.  workspace_dev:
+ *   ojf_register_workspace_bytes(X*Y*Z) bytes, 4-byte aligned.
+ * ojf_register_workspace_bytes(n): the workspace of ojf_register / ojf_register_associate for n points (8-byte aligned), which
+ *   also serves ojf_register_select on a volume of n voxels; 0 for n = 0 or n >= 2^31.
+ * ojf_register: `iterations` Gauss-Newton steps (one associate + one solve launch each) of one stage on the points list_dev
+ *   u32[n_points] of the moving volume.  field_band: a point where |field| >= field_band is no inlier (pass +inf for an f32
+ *   field); dist: nor is one whose residual exceeds dist.  pose_dev f64[12] in/out: continue_from_pose == 0 starts from
+ *   E_init_host (one more launch writes it and status {0, -1}); otherwise the call continues from what pose_dev and status_dev
+ *   hold.  stats_dev f64[OJF_REGISTER_MAX_ITERATIONS][4]: rows first_iteration .. first_iteration + iterations - 1 are written
+ *   (inlier count, mean squared residual, |omega|, |tau|); status_dev int[2] {0 | 1 fewer inliers than
+ *   min_inlier_fraction n_points | 2 singular system | 3 non-finite step, iteration of the failure or -1}.  A failed step always
+ *   restores E_init_host and freezes the rest (later stats rows are 0).  Never waits.
+ * ojf_register_associate: one step from the host pose E_pose_host: pose_dev the updated pose, sums_dev f64[OJF_TRACK_TERMS],
+ *   jr_dev (or NULL) f32[n_points][7] = (J_0..J_5, r) of every point (0 for outliers), reason_dev (or NULL) u8[n_points]
+ *   (0 inlier, 1 outside the fixed grid, 2 a corner without a value, 3 field saturated, 4 residual too large, 5 no gradient).
+ *   For tests and diagnostics.
+ * Bad arguments - a malformed box, a non-finite origin or resolution, stride < 1, a band, field_band or dist that is not > 0,
+ *   n_points == 0, misaligned or null pointers, a short workspace - are refused before any HIP call, with a text that names the
+ *   argument. */
+#define OJF_REGISTER_MAX_ITERATIONS 128
+size_t ojf_register_workspace_bytes(size_t n);
+int ojf_register_select(const uint16_t *tsdf_dev, const uint16_t *weights_dev, int X, int Y, int Z, float band, int stride,
+                        void *workspace_dev, size_t workspace_bytes, uint32_t *list_dev /* or NULL */, uint32_t capacity,
+                        uint32_t *count_dev, ojf_stream_t stream);
+int ojf_register(const uint16_t *moving_tsdf_dev, int mX, int mY, int mZ, const double *moving_origin_host,
+                 double moving_resolution, const uint32_t *list_dev, uint32_t n_points, const uint16_t *fixed_tsdf_dev,
+                 const uint16_t *fixed_weights_dev, const float *fixed_field_dev, int fX, int fY, int fZ,
+                 const double *fixed_origin_host, double fixed_resolution, double field_band, double dist, int iterations,
+                 int first_iteration, double min_inlier_fraction, const double *E_init_host, int continue_from_pose,
+                 void *workspace_dev, size_t workspace_bytes, double *pose_dev, double *stats_dev, int *status_dev,
+                 ojf_stream_t stream);
+int ojf_register_associate(const uint16_t *moving_tsdf_dev, int mX, int mY, int mZ, const double *moving_origin_host,
+                           double moving_resolution, const uint32_t *list_dev, uint32_t n_points, const uint16_t *fixed_tsdf_dev,
+                           const uint16_t *fixed_weights_dev, const float *fixed_field_dev, int fX, int fY, int fZ,
+                           const double *fixed_origin_host, double fixed_resolution, double field_band, double dist,
+                           double min_inlier_fraction, const double *E_pose_host, void *workspace_dev, size_t workspace_bytes,
+                           double *pose_dev, double *sums_dev, float *jr_dev, uint8_t *reason_dev, int *status_dev,
+                           ojf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

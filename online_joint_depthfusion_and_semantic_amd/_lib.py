@@ -46,7 +46,8 @@ RENDER_MAX_VIEWS = 64  # include/ojf.h OJF_RENDER_MAX_VIEWS
 TRACK_MAX_LEVELS = 4  # include/ojf.h OJF_TRACK_MAX_LEVELS
 TRACK_MAX_ITERATIONS = 128  # include/ojf.h OJF_TRACK_MAX_ITERATIONS
 TRACK_TERMS = 29  # include/ojf.h OJF_TRACK_TERMS
-PROJECTIVE_MAX_VIEWS = 32  # include/ojf.h OJF_PROJECTIVE_MAX_VIEWS
+REGISTER_MAX_ITERATIONS = 128  # include/ojf.h OJF_REGISTER_MAX_ITERATIONS
+PROJECTIVE_MAX_VIEWS = 32 # include/ojf.h OJF_PROJECTIVE_MAX_VIEWS
 COLOR_MAX_VIEWS = 32  # include/ojf.h OJF_COLOR_MAX_VIEWS
 RASTER_MAX_VIEWS = 32  # include/ojf.h OJF_RASTER_MAX_VIEWS
 LABEL_MAX_VIEWS = 32  # include/ojf.h OJF_LABEL_MAX_VIEWS
@@ -224,6 +225,18 @@ SIGNATURES = {
     # source, vertex capacity, out faces, face source, face capacity, counts, stream
     'ojf_mesh_simplify': (_i, [_vp, _i, _vp, _i, _vp, _f, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _vp, _c.c_uint32, _vp, _vp,
                                _c.c_uint32, _vp, _vp]),
+    'ojf_register_workspace_bytes': (_sz, [_sz]),
+    # tsdf, weights, X, Y, Z, band, stride, workspace, workspace_bytes, list, capacity, count, stream
+    'ojf_register_select': (_i, [_vp, _vp, _i, _i, _i, _f, _i, _vp, _sz, _vp, _c.c_uint32, _vp, _vp]),
+    # moving tsdf, mX, mY, mZ, moving origin, moving resolution, list, n_points, fixed tsdf, fixed weights, fixed field, fX, fY, fZ,
+    # fixed origin, fixed resolution, field_band, dist, iterations, first_iteration, min_inlier_fraction, E_init, continue_from_pose,
+    # workspace, workspace_bytes, pose, stats, status, stream
+    'ojf_register': (_i, [_vp, _i, _i, _i, _vp, _d, _vp, _c.c_uint32, _vp, _vp, _vp, _i, _i, _i, _vp, _d, _d, _d, _i, _i, _d, _vp, _i,
+                          _vp, _sz, _vp, _vp, _vp, _vp]),
+    # (the scene as above), field_band, dist, min_inlier_fraction, E_pose, workspace, workspace_bytes, pose, sums, jr, reason, status,
+    # stream
+    'ojf_register_associate': (_i, [_vp, _i, _i, _i, _vp, _d, _vp, _c.c_uint32, _vp, _vp, _vp, _i, _i, _i, _vp, _d, _d, _d, _d, _vp,
+                                    _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _LIB = None

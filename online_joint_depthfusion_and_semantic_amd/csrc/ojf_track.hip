@@ -44,17 +44,10 @@
 // Launches: one pyramid (which also writes P = E_init and the status {0, -1}), then per level from L-1 down to 0 and per
 // iteration one associate and one solve: 1 + 2·sum(iterations).  Kernel boundaries order the iterations; the host never
 // waits.  No atomics, no inline assembly; every output is written once: the same bits on every run.
-#include "ojf_common.h"
-
-#include <math.h>
+// The terms, the block sums and the solve kernel of (b) and (c) are in ojf_gauss_newton.h, which ojf_register.hip shares.
+#include "ojf_gauss_newton.h"
 
 namespace ojf {
-
-constexpr int kTrackThreads = 256;
-constexpr int kTrackPixPerThread = 4;
-constexpr int kTrackPixPerBlock = kTrackThreads * kTrackPixPerThread;
-constexpr int kTrackTerms = OJF_TRACK_TERMS;
-constexpr int kSolveChunk = 64;  // block rows per LDS chunk of the solve (14.8 KB)
 
 struct PyramidArgs {
     const float *depth;
@@ -253,165 +246,12 @@ __global__ __launch_bounds__(kTrackThreads) void track_associate_kernel(AssocArg
             A.jr[7 * (size_t)pix + 6] = why ? 0.0f : res;
         }
         if (why) continue;
-        int e = 0;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-#pragma unroll
-            for (int j = i; j < 6; ++j) acc[e++] += (double)J[i] * (double)J[j];
-        }
-#pragma unroll
-        for (int i = 0; i < 6; ++i) acc[21 + i] += (double)J[i] * (double)res;
-        acc[27] += (double)res * (double)res;
-        acc[28] += 1.0;
+        add_terms(acc, J, res);
     }
-#pragma unroll
-    for (int e = 0; e < kTrackTerms; ++e) {
-        double s = acc[e];
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-        acc[e] = s;
-    }
-    __shared__ double part[kTrackThreads / 64][kTrackTerms];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int e = 0; e < kTrackTerms; ++e) part[wave][e] = acc[e];
-    }
-    __syncthreads();
-    if (threadIdx.x < kTrackTerms) {
-        double s = 0.0;
-        for (int wv = 0; wv < kTrackThreads / 64; ++wv) s += part[wv][threadIdx.x];
-        A.rows[(size_t)blockIdx.x * kTrackTerms + threadIdx.x] = s;
-    }
-}
-
-struct SolveArgs {
-    const double *rows;
-    int nblocks;
-    double *pose;
-    int *status;
-    double *stats;   // row `iter` of [n_iter, 4]
-    double *sums;    // [29] or NULL
-    int iter;
-    double min_count;
-    double init[12];
-};
-
-__device__ bool solve6(const double A[6][6], const double b[6], double x[6])
-{
-    double dmax = A[0][0];
-    for (int j = 1; j < 6; ++j) dmax = fmax(dmax, A[j][j]);
-    const double thr = 1e-6 * dmax;
-    double L[6][6] = {};
-    for (int j = 0; j < 6; ++j) {
-        double d = A[j][j];
-        for (int k = 0; k < j; ++k) d = d - L[j][k] * L[j][k];
-        if (!(d > thr)) return false;
-        L[j][j] = sqrt(d);
-        for (int i = j + 1; i < 6; ++i) {
-            double s = A[i][j];
-            for (int k = 0; k < j; ++k) s = s - L[i][k] * L[j][k];
-            L[i][j] = s / L[j][j];
-        }
-    }
-    double y[6];
-    for (int i = 0; i < 6; ++i) {
-        double s = b[i];
-        for (int k = 0; k < i; ++k) s = s - L[i][k] * y[k];
-        y[i] = s / L[i][i];
-    }
-    for (int i = 5; i >= 0; --i) {
-        double s = y[i];
-        for (int k = i + 1; k < 6; ++k) s = s - L[k][i] * x[k];
-        x[i] = s / L[i][i];
-    }
-    return true;
-}
-
-__global__ __launch_bounds__(kTrackThreads) void track_solve_kernel(SolveArgs S)
-{
-    // the rows arrive in LDS a chunk at a time with independent loads; lane e then adds its column in block order (a
-    // chain of dependent global loads would cost ~0.2 us per block)
-    __shared__ double chunk[kSolveChunk * kTrackTerms];
-    __shared__ double sum[kTrackTerms];
-    const int frozen = S.status[0];
-    if (frozen) {
-        if (threadIdx.x == 0) {
-            double *st = S.stats + 4 * (size_t)S.iter;
-            st[0] = st[1] = st[2] = st[3] = 0.0;
-        }
-        return;
-    }
-    double acc = 0.0;
-    for (int b0 = 0; b0 < S.nblocks; b0 += kSolveChunk) {
-        const int nb = S.nblocks - b0 < kSolveChunk ? S.nblocks - b0 : kSolveChunk;
-        for (int i = threadIdx.x; i < nb * kTrackTerms; i += kTrackThreads) chunk[i] = S.rows[(size_t)b0 * kTrackTerms + i];
-        __syncthreads();
-        if (threadIdx.x < kTrackTerms)
-            for (int b = 0; b < nb; ++b) acc += chunk[b * kTrackTerms + threadIdx.x];
-        __syncthreads();
-    }
-    if (threadIdx.x < kTrackTerms) {
-        sum[threadIdx.x] = acc;
-        if (S.sums) S.sums[threadIdx.x] = acc;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    double *st = S.stats + 4 * (size_t)S.iter;
-    const double cnt = sum[28];
-    st[0] = cnt;
-    st[1] = cnt > 0.0 ? sum[27] / cnt : 0.0;
-    st[2] = st[3] = 0.0;
-    int code = 0;
-    double x[6];
-    if (cnt < S.min_count) {
-        code = 1;
-    } else {
-        double A[6][6], b[6];
-        int e = 0;
-        for (int i = 0; i < 6; ++i)
-            for (int j = i; j < 6; ++j) A[i][j] = A[j][i] = sum[e++];
-        for (int i = 0; i < 6; ++i) b[i] = -sum[21 + i];
-        if (!solve6(A, b, x)) code = 2;
-        else
-            for (int i = 0; i < 6; ++i)
-                if (!isfinite(x[i])) code = 3;
-    }
-    if (code) {
-        S.status[0] = code;
-        S.status[1] = S.iter;
-        for (int i = 0; i < 12; ++i) S.pose[i] = S.init[i];
-        return;
-    }
-    const double w[3] = {x[0], x[1], x[2]}, tau[3] = {x[3], x[4], x[5]};
-    const double th = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-    double Ri[3][3];
-    if (th < 1e-12) {
-        Ri[0][0] = 1.0; Ri[0][1] = -w[2]; Ri[0][2] = w[1];
-        Ri[1][0] = w[2]; Ri[1][1] = 1.0; Ri[1][2] = -w[0];
-        Ri[2][0] = -w[1]; Ri[2][1] = w[0]; Ri[2][2] = 1.0;
-    } else {
-        const double k[3] = {w[0] / th, w[1] / th, w[2] / th};
-        const double s = sin(th), c = 1.0 - cos(th);
-        const double Kx[3][3] = {{0.0, -k[2], k[1]}, {k[2], 0.0, -k[0]}, {-k[1], k[0], 0.0}};
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) {
-                const double dl = i == j ? 1.0 : 0.0;
-                Ri[i][j] = (dl + s * Kx[i][j]) + c * (k[i] * k[j] - dl);
-            }
-    }
-    double P[12];
-    for (int i = 0; i < 12; ++i) P[i] = S.pose[i];
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) S.pose[4 * i + j] = Ri[i][0] * P[j] + Ri[i][1] * P[4 + j] + Ri[i][2] * P[8 + j];
-        S.pose[4 * i + 3] = (Ri[i][0] * P[3] + Ri[i][1] * P[7] + Ri[i][2] * P[11]) + tau[i];
-    }
-    st[2] = th;
-    st[3] = sqrt(tau[0] * tau[0] + tau[1] * tau[1] + tau[2] * tau[2]);
+    block_terms_to_row(acc, A.rows + (size_t)blockIdx.x * kTrackTerms);
 }
 
 static int level_blocks(int h, int w, int l) { return (((h >> l) * (w >> l)) + kTrackPixPerBlock - 1) / kTrackPixPerBlock; }
-
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 static size_t pyramid_bytes(int h, int w, int levels)
 {
@@ -479,14 +319,6 @@ static void fill_assoc(AssocArgs &A, const PyramidArgs &P, int l, const double *
     A.cos_thr = (float)cos(angle * M_PI / 180.0);
 }
 
-static void fill_solve(SolveArgs &S, const double *rows, int nblocks, double *pose, int *status, double *stats,
-                       double *sums, int iter, double min_count, const double *init)
-{
-    S.rows = rows; S.nblocks = nblocks; S.pose = pose; S.status = status; S.stats = stats; S.sums = sums;
-    S.iter = iter; S.min_count = min_count;
-    for (int i = 0; i < 12; ++i) S.init[i] = init[i];
-}
-
 static int launch_pyramid(const PyramidArgs &P, hipStream_t s)
 {
     const int total = P.off[P.levels];
@@ -499,9 +331,7 @@ static int launch_step(const AssocArgs &A, const SolveArgs &S, hipStream_t s)
 {
     hipLaunchKernelGGL(track_associate_kernel, dim3(S.nblocks), dim3(kTrackThreads), 0, s, A);
     OJF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(track_solve_kernel, dim3(1), dim3(kTrackThreads), 0, s, S);
-    OJF_HIP(hipGetLastError());
-    return 0;
+    return launch_solve(S, s);
 }
 
 }  // namespace ojf

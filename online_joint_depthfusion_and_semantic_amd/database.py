@@ -559,6 +559,22 @@ class Database(torch.utils.data.Dataset):
             self.label_probs[dst_scene] = fresh['label_probs']
         self.state[dst_scene] = self.state[dst_scene] or self.state[src_scene]
 
+    def register(self, dst_scene, src_scene, transform=None, **kw):
+        """The rigid transform between the estimated volumes of two scenes (registration.register_volumes, Gauss-Newton on
+        signed distance fields): it maps points of ``dst_scene``'s world to ``src_scene``'s - what ``merge(dst_scene, src_scene,
+        transform=...)`` takes.  ``transform`` is the initial guess (default: one world); ``kw`` goes to ``register_volumes``
+        (band, stages, min_inlier_fraction).  Returns its dict {'transform' f64 [3,4], 'ok', 'status', 'failed_iteration',
+        'stats', 'n_points'}.  Reads the TSDF and the weights of both scenes and writes no volume; host state is refused."""
+        from . import registration
+        if dst_scene == src_scene:
+            raise ValueError('Database.register: a scene cannot be registered to itself')
+        scenes = []
+        for s in (dst_scene, src_scene):
+            tsdf, w = self.scenes_est[s].volume, self.fusion_weights[s]
+            self._resident(s, 'register', tsdf, w)
+            scenes.append({'tsdf': tsdf, 'weights': w, 'origin': self._origin64(s), 'resolution': float(self.resolution[s])})
+        return registration.register_volumes(scenes[0], scenes[1], transform=transform, **kw)
+
     def save_to_workspace(self, workspace, mode, save_mode='ply', simplify=None):
         """database.py:141-177: every scene that holds integrated frames goes to the workspace's output directory as
         ``<scene>.tsdf_<mode>.hf5`` / ``.weights_<mode>.hf5`` / ``.semantic_<mode>.hf5`` ('tsdf'), ``<scene>_<mode>.ply``
