@@ -994,6 +994,56 @@ int ojf_register_associate(const uint16_t *moving_tsdf_dev, int mX, int mY, int 
                            double *pose_dev, double *sums_dev, float *jr_dev, uint8_t *reason_dev, int *status_dev,
                            ojf_stream_t stream);
 
+/* ---- TVL1 (robust fusion of depth views: per-voxel histograms and their TV-L1 minimiser; definition: csrc/ojf_tvl1.hip,
+ * DESIGN.md §22; the reference's counterpart is deps/mesh-fusion/libfusiongpu/fusion_zach_tvl1.cu) -------------------------
+ * The histogram volume hist_dev is fp16 [X,Y,Z,S], voxel-major, 16-byte aligned, S = 8 * ceil((n_bins + 1) / 8) for
+ *   2 <= n_bins <= OJF_HIST_MAX_BINS (one or two 16-byte chunks per voxel) - the record layout of the label volume: channels
+ *   0..n_bins-1 hold the running means h_b of the votes, channel n_bins the weight W (0: never observed); all zeros at reset;
+ *   the channels behind W are padding that no call reads or writes.  Bin b has its centre at the normalised distance
+ *   l_b = 2b / (n_bins - 1) - 1 (-1: -trunc, +1: +trunc).
+ * ojf_fuse_depth_hist: fuses n views (1 <= n <= OJF_HIST_MAX_VIEWS, one h x w for all) into hist_dev in place.  Every voxel
+ *   centre is projected into each view in turn exactly as ojf_fuse_projective does (same constants, nearest pixel, depth_dev /
+ *   mask_dev tests, near).  With s = d - zc, a view votes when s >= -trunc (carve == 1: free space in front of a surface votes
+ *   the last bin) or when -trunc <= s <= trunc (carve == 0); the vote is split linearly over the two bins that bracket
+ *   t = min(s, trunc) / trunc, the nearer bin taking the larger share; h_b = (W*h_b + vote_b) / (W + 1), then
+ *   W = min(W + 1, max_weight), rounded to fp16 after every view.  trunc > 0, 1 <= max_weight <= 2048, near >= 0, pinhole K.
+ *   One owner lane per voxel: no atomics, no workspace, the same bits on every run, and n views in one call give the bits of
+ *   n calls of one view.  One kernel, never waits.
+ * ojf_tvl1_workspace_bytes: the workspace of ojf_tvl1_solve for a box (about 33 bytes per voxel); 0 for a box it refuses.
+ * ojf_tvl1_solve: `iterations` (>= 0) Chambolle-Pock iterations towards the minimiser of
+ *   TV(u) + lambda * sum_voxels sum_b h_b |u - l_b| over the observed voxels (W > 0) of hist_dev.  An edge between two
+ *   6-neighbours counts when both are observed and inside the box (a Neumann boundary everywhere else); unobserved voxels are
+ *   never written and never influence an observed one.  u_dev f32 [X,Y,Z] (16-byte aligned, normalised distance in [-1, 1])
+ *   is the caller's: read and written at the observed voxels only.  lambda > 0; tau, sigma > 0 with tau * sigma <= 1/12.
+ *   restart: OJF_TVL1_RESTART runs the set-up pass (the edge bits, the list of the bricks that hold an observed voxel), zeroes
+ *   the dual and sets u of every observed voxel to clamp(sum_b h_b l_b / sum_b h_b); OJF_TVL1_CONTINUE goes on from u_dev and
+ *   the workspace as the previous call on the same hist_dev and box left them - N iterations in one call give the bits of any
+ *   split of N over consecutive calls; OJF_TVL1_REFRESH says that hist_dev has changed since (views were fused): the set-up
+ *   pass runs again, a voxel observed for the first time starts at its clamp(...) value with a zero dual, the others go on.
+ *   Or-ing OJF_TVL1_ALL_BRICKS into _RESTART / _REFRESH lists every brick of the box (the same bits; for measurements).
+ *   workspace_dev: ojf_tvl1_workspace_bytes bytes, 256-byte aligned, owned by the (hist_dev, u_dev) pair between calls.
+ *   Two launches for the set-up, one per iteration, all on `stream`; never waits.
+ * ojf_tvl1_write: for every observed voxel, tsdf_dev fp16 [X,Y,Z] = trunc * u and weights_dev fp16 [X,Y,Z] = W; every other
+ *   voxel keeps what it holds.  One kernel, never waits.
+ * Bad arguments (hist_dev off the 16-byte grid, n_bins outside 2..OJF_HIST_MAX_BINS, tau * sigma > 1/12, lambda <= 0,
+ *   negative iterations, a misaligned or short workspace, and what ojf_fuse_projective refuses) are refused before any HIP
+ *   call.  The exact fp32 operation order is in csrc/ojf_tvl1.hip. */
+#define OJF_HIST_MAX_BINS 15
+#define OJF_HIST_MAX_VIEWS 32
+#define OJF_TVL1_CONTINUE 0
+#define OJF_TVL1_RESTART 1
+#define OJF_TVL1_REFRESH 2
+#define OJF_TVL1_ALL_BRICKS 4
+int ojf_fuse_depth_hist(uint16_t *hist_dev /* fp16 [X,Y,Z,S] */, int n_bins, int X, int Y, int Z, const double *origin_host,
+                        double resolution, int n, const double *K_host /* f64[n][9] */, const double *E_host /* f64[n][12] */,
+                        const float *depth_dev /* f32[n,h,w] */, const uint8_t *mask_dev /* u8[n,h,w] or NULL */, int h, int w,
+                        float trunc, float max_weight, float near, int carve, ojf_stream_t stream);
+size_t ojf_tvl1_workspace_bytes(int X, int Y, int Z);
+int ojf_tvl1_solve(const uint16_t *hist_dev, int n_bins, int X, int Y, int Z, float lambda, float tau, float sigma, int iterations,
+                   int restart, float *u_dev /* f32 [X,Y,Z] */, void *workspace_dev, size_t workspace_bytes, ojf_stream_t stream);
+int ojf_tvl1_write(const uint16_t *hist_dev, int n_bins, int X, int Y, int Z, const float *u_dev, float trunc,
+                   uint16_t *tsdf_dev /* fp16 [X,Y,Z] */, uint16_t *weights_dev /* fp16 [X,Y,Z] */, ojf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

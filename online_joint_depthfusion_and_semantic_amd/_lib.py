@@ -51,6 +51,8 @@ PROJECTIVE_MAX_VIEWS = 32 # include/ojf.h OJF_PROJECTIVE_MAX_VIEWS
 COLOR_MAX_VIEWS = 32  # include/ojf.h OJF_COLOR_MAX_VIEWS
 RASTER_MAX_VIEWS = 32  # include/ojf.h OJF_RASTER_MAX_VIEWS
 LABEL_MAX_VIEWS = 32  # include/ojf.h OJF_LABEL_MAX_VIEWS
+HIST_MAX_BINS, HIST_MAX_VIEWS = 15, 32  # include/ojf.h OJF_HIST_MAX_BINS / OJF_HIST_MAX_VIEWS
+TVL1_CONTINUE, TVL1_RESTART, TVL1_REFRESH, TVL1_ALL_BRICKS = 0, 1, 2, 4  # include/ojf.h OJF_TVL1_*
 RESAMPLE_REPLACE, RESAMPLE_MERGE = 0, 1  # include/ojf.h OJF_RESAMPLE_REPLACE / OJF_RESAMPLE_MERGE
 MESH_DISTANCE_BIN, MESH_DISTANCE_SCAN, MESH_DISTANCE_FILL, MESH_DISTANCE_GATHER, MESH_DISTANCE_ALL = 1, 2, 4, 8, 15  # OJF_MESH_DISTANCE_*
 COMPONENTS_BRICK, COMPONENTS_SEAM, COMPONENTS_FLATTEN, COMPONENTS_RANK, COMPONENTS_LIST, COMPONENTS_ALL = 1, 2, 4, 8, 16, 31  # OJF_COMPONENTS_*
@@ -237,6 +239,13 @@ SIGNATURES = {
     # stream
     'ojf_register_associate': (_i, [_vp, _i, _i, _i, _vp, _d, _vp, _c.c_uint32, _vp, _vp, _vp, _i, _i, _i, _vp, _d, _d, _d, _d, _vp,
                                     _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # histogram volume, n_bins, X, Y, Z, origin, resolution, n, K, E, depth, mask, h, w, trunc, max_weight, near, carve, stream
+    'ojf_fuse_depth_hist': (_i, [_vp, _i, _i, _i, _i, _vp, _d, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _i, _vp]),
+    'ojf_tvl1_workspace_bytes': (_sz, [_i, _i, _i]),
+    # histogram volume, n_bins, X, Y, Z, lambda, tau, sigma, iterations, restart, u, workspace, workspace_bytes, stream
+    'ojf_tvl1_solve': (_i, [_vp, _i, _i, _i, _i, _f, _f, _f, _i, _i, _vp, _vp, _sz, _vp]),
+    # histogram volume, n_bins, X, Y, Z, u, trunc, tsdf, weights, stream
+    'ojf_tvl1_write': (_i, [_vp, _i, _i, _i, _i, _vp, _f, _vp, _vp, _vp]),
 }
 
 _LIB = None

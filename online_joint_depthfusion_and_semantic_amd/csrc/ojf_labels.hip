@@ -33,13 +33,15 @@
 //
 // Shape.  Fusion: one lane owns one voxel for the whole call (lanes run along the contiguous z axis) and walks the n views
 // in order.  The projection of every (voxel, view) is the bulk of the sweep; only the voxels inside the band of a view
-// (1-2 % of a room) touch their record, and they do it per view: a read-modify-write of the record straight in memory -
+// (1-2 % of a room) touch their record, and they do it per view (record_fuse, ojf_records.h, shared with the depth
+// histograms of ojf_tvl1.hip): a read-modify-write of the record straight in memory -
 // C/8 whole chunks as 16-byte accesses, then the C mod 8 classes of the last chunk and W as 2-byte accesses, which is
 // what keeps the padding unread.  Nothing of the record is held across views (C = 256 is 132 dwords; values are rounded
 // to fp16 after every view anyway, so n views in one call give the bits of n calls of one view), the same lane reads what
 // it stored in program order, and the kernel needs 4 dwords of record at a time whatever C is.  No atomics, no LDS, no
 // workspace, one launch.  The decision: one lane per voxel, W first, the record only where W > 0.
 #include "ojf_projview.h"
+#include "ojf_records.h"
 
 namespace ojf {
 
@@ -60,9 +62,6 @@ struct LabelLaunch {
     ProjView v[OJF_LABEL_MAX_VIEWS];
 };
 
-// step 4 for one class
-__device__ __forceinline__ uint16_t label_mean(uint16_t P, float w0, float w1, float p) { return f2h((w0 * h2f(P) + p) / w1); }
-
 // step 3's clamp of a probability
 __device__ __forceinline__ float label_prob(float x) { return (x >= 0.0f && x <= 1.0f) ? x : 0.0f; }
 
@@ -75,44 +74,19 @@ __global__ __launch_bounds__(kLabelBlock) void label_fuse_kernel(LabelLaunch L)
     float xs[1], ys[1], zs[1];
     voxel_indices<1>(g, P.Y, P.Z, xs, ys, zs);
     uint16_t *const rec = P.vol + (size_t)g * (size_t)P.S;
-    const int full = P.C >> 3;  // chunks that hold classes only
-
     for (int v = 0; v < P.n; ++v) {
         uint32_t px;
         float s;
         if (!project_depth(L.v[v], P.im, v, xs[0], ys[0], zs[0], px, s)) continue;
         if (!(s >= -P.band && s <= P.band)) continue;
-        const float *row = nullptr;
-        int label = -1;
         if constexpr (PROBS) {
-            row = P.probs + (size_t)px * (size_t)P.prob_stride;
+            const float *const row = P.probs + (size_t)px * (size_t)P.prob_stride;
+            record_fuse(rec, P.C, P.max_weight, [&](int k) { return label_prob(row[k]); });
         } else {
-            label = P.labels[px];
+            const int label = P.labels[px];
             if (label >= P.C) continue;
+            record_fuse(rec, P.C, P.max_weight, [&](int k) { return (k == label) ? 1.0f : 0.0f; });
         }
-        const float w0 = h2f(rec[P.C]);
-        const float w1 = w0 + 1.0f;
-        for (int c = 0; c < full; ++c) {
-            uint4 *const chunk = reinterpret_cast<uint4 *>(rec) + c;
-            const uint4 r = *chunk;
-            uint32_t q[4] = {r.x, r.y, r.z, r.w};
-            float p[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                if constexpr (PROBS) p[e] = label_prob(row[8 * c + e]);
-                else p[e] = (8 * c + e == label) ? 1.0f : 0.0f;
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) set16(q, e, label_mean((uint16_t)get16(q, e), w0, w1, p[e]));
-            *chunk = make_uint4(q[0], q[1], q[2], q[3]);
-        }
-        for (int k = 8 * full; k < P.C; ++k) {
-            float p;
-            if constexpr (PROBS) p = label_prob(row[k]);
-            else p = (k == label) ? 1.0f : 0.0f;
-            rec[k] = label_mean(rec[k], w0, w1, p);
-        }
-        rec[P.C] = f2h(fminf(w1, P.max_weight));
     }
 }
 
@@ -178,7 +152,7 @@ OJF_API int ojf_fuse_label_probs(uint16_t *vol, int n_classes, int X, int Y, int
     fill_proj_images(A.im, depth, mask, h, w, near);
     A.probs = probs; A.labels = labels;
     A.total = (uint32_t)((int64_t)X * Y * Z);
-    A.Y = Y; A.Z = Z; A.n = n; A.C = n_classes; A.S = 8 * ((n_classes + 8) / 8); A.prob_stride = prob_stride;
+    A.Y = Y; A.Z = Z; A.n = n; A.C = n_classes; A.S = record_size(n_classes); A.prob_stride = prob_stride;
     A.band = band; A.max_weight = max_weight;
     make_proj_views(K, E, origin, res, n, L.v);
     const uint32_t blocks = (A.total + kLabelBlock - 1) / kLabelBlock;
@@ -200,7 +174,7 @@ OJF_API int ojf_label_decide(const uint16_t *vol, int n_classes, int X, int Y, i
     DecideArgs A;
     A.vol = vol; A.ids = ids; A.scores = scores;
     A.total = (uint32_t)((int64_t)X * Y * Z);
-    A.C = n_classes; A.S = 8 * ((n_classes + 8) / 8);
+    A.C = n_classes; A.S = record_size(n_classes);
     const uint32_t blocks = (A.total + kLabelBlock - 1) / kLabelBlock;
     hipLaunchKernelGGL(label_decide_kernel, dim3(blocks), dim3(kLabelBlock), 0, as_stream(stream), A);
     OJF_HIP(hipGetLastError());

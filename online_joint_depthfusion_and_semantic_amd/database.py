@@ -66,6 +66,9 @@ class Database(torch.utils.data.Dataset):
         self.ids_gt, self.ids_est, self.scores = {}, {}, {}
         self.colors = {}  # scene -> fp16 [X,Y,Z,4] colour volume (color.py), only for scenes integrate_color was called on
         self.label_probs = {}  # scene -> fp16 [X,Y,Z,S] class distribution (label_probs.py), only for scenes integrate_label_probs was called on
+        self.depth_hists = {}  # scene -> (fp16 [X,Y,Z,S] depth histograms, n_bins) (tvl1.py), only for scenes integrate_depth_hist was called on
+        self._tvl1_solvers = {}  # scene -> tvl1.Solver: u and the workspace of regularize, kept for warm starts
+        self._tvl1_changed = set()  # scenes whose histograms took views since their solver last ran
         self.tracked_poses = {}  # frame_id -> f64 [4,4] camera-to-world: frames fused with a tracked pose (drivers.test_fusion)
 
         for s in dataset.scenes:
@@ -107,6 +110,8 @@ class Database(torch.utils.data.Dataset):
             sample['colors'] = self.colors[item]
         if self.label_probs.get(item) is not None:
             sample['label_probs'] = self.label_probs[item]
+        if self.depth_hists.get(item) is not None:
+            sample['depth_hist'] = self.depth_hists[item][0]
         return sample
 
     def __len__(self):
@@ -127,6 +132,8 @@ class Database(torch.utils.data.Dataset):
                 self.colors[s] = self._dev(self.colors[s])
             if self.label_probs.get(s) is not None:
                 self.label_probs[s] = self._dev(self.label_probs[s])
+            if self.depth_hists.get(s) is not None:
+                self.depth_hists[s] = (self._dev(self.depth_hists[s][0]), self.depth_hists[s][1])
             if gt:
                 o = self.origin[s]
                 self.origin[s] = o.double().cpu() if torch.is_tensor(o) else torch.from_numpy(np.asarray(o, np.float64))
@@ -149,6 +156,9 @@ class Database(torch.utils.data.Dataset):
                 self.colors[s] = host(self.colors[s])
             if self.label_probs.get(s) is not None:
                 self.label_probs[s] = host(self.label_probs[s])
+            if self.depth_hists.get(s) is not None:
+                self.depth_hists[s] = (host(self.depth_hists[s][0]), self.depth_hists[s][1])
+                self._tvl1_solvers.pop(s, None)  # (the solver's state is not carried to the host: the next regularize restarts)
             if self.semantics:
                 self.ids_est[s].volume = host(self.ids_est[s].volume)
                 self.scores[s].volume = host(self.scores[s].volume)
@@ -170,6 +180,13 @@ class Database(torch.utils.data.Dataset):
                 ops.volume_fill(p, 0.0)
             elif p is not None:
                 self.label_probs[s] = np.zeros(p.shape, dtype=np.float16)
+            if self.depth_hists.get(s) is not None:
+                hist, n_bins = self.depth_hists[s]
+                if _is_dev(hist):
+                    ops.volume_fill(hist, 0.0)
+                else:
+                    self.depth_hists[s] = (np.zeros(hist.shape, dtype=np.float16), n_bins)
+                self._tvl1_solvers.pop(s, None)
             if _is_dev(self.scenes_est[s].volume):
                 ops.volume_fill(self.scenes_est[s].volume, self.initial_value)
                 ops.volume_fill(self.fusion_weights[s], 0.0)
@@ -192,6 +209,8 @@ class Database(torch.utils.data.Dataset):
         self.fusion_weights[scene_id] = None
         self.colors.pop(scene_id, None)
         self.label_probs.pop(scene_id, None)
+        self.depth_hists.pop(scene_id, None)
+        self._tvl1_solvers.pop(scene_id, None)
         if self.semantics:
             self.ids_est[scene_id] = None
             self.scores[scene_id] = None
@@ -438,6 +457,50 @@ class Database(torch.utils.data.Dataset):
                                               depth=dev(depth), intrinsics=intrinsics, extrinsics=extrinsics, mask=dev(mask),
                                               probs=dev(probs), labels=dev(labels), **kw)
 
+    def integrate_depth_hist(self, scene_id, depth, intrinsics, extrinsics, mask=None, n_bins=9, **kw):
+        """Fuse one or more depth maps into the scene's depth-histogram volume (tvl1.py; allocated, zeroed, on first use; the bin
+        count is fixed then): depth / mask / poses as for ``integrate_depth``; ``kw`` goes to ``tvl1.integrate_depth_hist``
+        (truncation - default: the initial value -, max_weight, near, carve).  The estimated TSDF and the fusion weights are not
+        touched: ``regularize`` writes them."""
+        from . import tvl1
+        tsdf = self.scenes_est[scene_id].volume
+        have = self.depth_hists.get(scene_id)
+        self._resident(scene_id, 'integrate_depth_hist', tsdf, optional=(None if have is None else have[0],))
+        if have is not None and have[1] != int(n_bins):
+            raise ValueError('Database.integrate_depth_hist: scene {!r} has histograms of {} bins, not {}'.format(scene_id, have[1], n_bins))
+        kw.setdefault('truncation', self.initial_value)
+        dev = lambda x: _to_dev(x, tsdf.device)  # noqa: E731
+        with self._side_volume(self.depth_hists, scene_id, lambda: (tvl1.new_volume(tsdf.shape, n_bins, tsdf.device), int(n_bins))) as (vol, B):
+            tvl1.integrate_depth_hist(vol, B, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]), depth=dev(depth),
+                                      intrinsics=intrinsics, extrinsics=extrinsics, mask=dev(mask), **kw)
+        self._tvl1_changed.add(scene_id)
+
+    def regularize(self, scene_id, lam=2.0, iterations=25, restart=True, truncation=None, **kw):
+        """Solve the TV-L1 problem of the scene's depth histograms (tvl1.Solver: ``iterations`` Chambolle-Pock iterations with
+        data weight ``lam``) and write the result into the estimated TSDF (``truncation`` - default: the initial value - times the
+        normalised field) and the fusion weights (the histograms' weights) at the observed voxels.  restart=False continues from
+        the previous call's state, taking in the views fused since; ``kw`` goes to ``Solver.solve`` (tau, sigma)."""
+        from . import tvl1
+        have = self.depth_hists.get(scene_id)
+        if have is None:
+            raise ValueError('Database.regularize: scene {!r} has no depth histograms (integrate_depth_hist)'.format(scene_id))
+        hist, B = have
+        tsdf, w = self.scenes_est[scene_id].volume, self.fusion_weights[scene_id]
+        self._resident(scene_id, 'regularize', hist, tsdf, w)
+        solver = self._tvl1_solvers.get(scene_id)
+        if solver is None or solver.shape != tuple(tsdf.shape) or solver.device != tsdf.device:
+            solver, restart = tvl1.Solver(tsdf.shape, tsdf.device), True
+        solver.solve(hist, B, lam, iterations, restart=restart, changed=scene_id in self._tvl1_changed, **kw)
+        solver.write(tsdf, w, self.initial_value if truncation is None else truncation)
+        self._tvl1_solvers[scene_id] = solver
+        self._tvl1_changed.discard(scene_id)
+        self.state[scene_id] = True
+
+    def _refuse_depth_hist(self, scene_id, who):
+        if self.depth_hists.get(scene_id) is not None:
+            raise ValueError('Database.{}: scene {!r} has depth histograms (integrate_depth_hist), which are not carried through '
+                             '{}: remove them first (depth_hists.pop) or fuse into the new box'.format(who, scene_id, who))
+
     def decide_labels(self, scene_id=None):
         """Write the decision of the class-distribution volumes - of one scene, or of every scene that has one - into ids_est /
         scores (label_probs.decide_labels): a voxel with a vote takes the first class of its largest mean and that mean, the
@@ -477,6 +540,7 @@ class Database(torch.utils.data.Dataset):
         volumes read every voxel of it.  What the old box does not cover holds the initial value / weight 0 / label 0.
         ``origin``, ``resolution`` and the bbox / origin of every Voxelgrid of the scene follow."""
         from . import resample as rs
+        self._refuse_depth_hist(scene_id, 'resample')
         est = self._estimated_volumes(scene_id, 'resample')
         gt = self.scenes_gt[scene_id].volume
         ids_gt = self.ids_gt[scene_id].volume if self.semantics and self.semantic_grid else None
@@ -518,6 +582,7 @@ class Database(torch.utils.data.Dataset):
         (index N // 2 on every axis); returns the integer shift (i, j, k) in voxels.  A whole-voxel shift is exact: every voxel
         that stays inside the box keeps its bits, the voxels that come in hold the initial value / weight 0 / label 0.  The call
         a live driver makes when the tracked camera nears a face of the box."""
+        self._refuse_depth_hist(scene_id, 'recentre')
         o, res = self._origin64(scene_id), float(self.resolution[scene_id])
         shape = np.array(self.scenes_est[scene_id].volume.shape, dtype=np.int64)
         p = np.asarray(ops._origin_array(point))
@@ -540,6 +605,8 @@ class Database(torch.utils.data.Dataset):
         from . import color, label_probs, resample as rs
         if dst_scene == src_scene:
             raise ValueError('Database.merge: a scene cannot be merged into itself')
+        self._refuse_depth_hist(dst_scene, 'merge')
+        self._refuse_depth_hist(src_scene, 'merge')
         src = self._estimated_volumes(src_scene, 'merge')
         dst = self._estimated_volumes(dst_scene, 'merge')
         shape, dev = tuple(dst['tsdf'].shape), dst['tsdf'].device
@@ -600,7 +667,7 @@ class Database(torch.utils.data.Dataset):
         """database.py:172-261: 'tsdf' (volumes), 'ply' (mesh), 'test' (volumes + mesh + label-coloured mesh whose
         alpha channel carries the label id).  A scene with a colour volume also gets ``<scene>_color.ply`` (the mesh with
         its sampled vertex colours, alpha 255 where coloured) beside every mesh and ``<scene>.color.hf5`` beside the volumes; a scene
-        with a class-distribution volume gets ``<scene>.label_probs.hf5`` there.  simplify (cell size in voxels; default off):
+        with a class-distribution volume gets ``<scene>.label_probs.hf5`` there, one with depth histograms ``<scene>.depth_hist.hf5``.  simplify (cell size in voxels; default off):
         the meshes go through the quadric vertex clustering of mesh_simplify.py first."""
         if scene_id is None:
             raise NotImplementedError
@@ -634,6 +701,8 @@ class Database(torch.utils.data.Dataset):
             arrays['color'] = ('color', host(self.colors[scene_id]))
         if self.label_probs.get(scene_id) is not None:
             arrays['label_probs'] = ('label_probs', host(self.label_probs[scene_id]))
+        if self.depth_hists.get(scene_id) is not None:
+            arrays['depth_hist'] = ('depth_hist', host(self.depth_hists[scene_id][0]))
         from .datasets import save_volume_hdf
         for name, (key, arr) in arrays.items():  # same file / dataset names as database.py:184-201 (npz without h5py)
             save_volume_hdf(os.path.join(path, '{}.{}.hf5'.format(base, name)), key, arr)

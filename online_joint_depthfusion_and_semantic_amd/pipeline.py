@@ -40,13 +40,16 @@ class Pipeline(torch.nn.Module):
             self._fusion_network = FusionNet_v2(config.FUSION_MODEL)
         elif name == 'v3':
             self._fusion_network = FusionNet_v3(config.FUSION_MODEL)
-        elif name == 'tsdf':
-            # classical projective TSDF averaging (projective.py): no network - an empty module with an empty state_dict, so
-            # that .to() / .eval() / checkpoint code written for the learned modes keeps working
+        elif name in ('tsdf', 'tvl1'):
+            # classical projective TSDF averaging (projective.py) or robust TV-L1 fusion of depth histograms (tvl1.py): no network -
+            # an empty module with an empty state_dict, so that .to() / .eval() / checkpoint code written for the learned modes
+            # keeps working
             self._fusion_network = torch.nn.Module()
         else:  # the reference's v1 cannot even be constructed (model.py:58)
-            raise ValueError('FUSION_MODEL.name must be "v2", "v3" or "tsdf"')
-        self._classical = name == 'tsdf'
+            raise ValueError('FUSION_MODEL.name must be "v2", "v3", "tsdf" or "tvl1"')
+        self._classical = name in ('tsdf', 'tvl1')
+        self._tvl1 = name == 'tvl1'
+        self._tvl1_frames = {}  # scene -> frames fused into its histograms (the solver runs after every tvl1_every of them)
 
         if config.DATA.semantics and config.DATA.semantic_strategy == 'predict':
             from .adapnet import AdapNet
@@ -310,6 +313,8 @@ class Pipeline(torch.nn.Module):
         ``prefetch``: the chunk the NEXT call will bring (the same batch objects).  Its batched 2-D pass is enqueued on a
         side stream before this chunk's frame steps and runs beside them; the next call finds the labels ready.  Bits do not
         depend on it (the same graph replay, another stream)."""
+        if self._tvl1 and prefetch:
+            raise ValueError('Pipeline.fuse_sequence: FUSION_MODEL.name "tvl1" does not support the look-ahead (prefetch)')
         self.device = torch.device(device)
         sems = self._take_prefetched(batches)
         if sems is None:
@@ -727,6 +732,20 @@ class Pipeline(torch.nn.Module):
         self._commit_frame(database, scene_id, volume)
         return sem_ids
 
+    # ---- FUSION_MODEL.name 'tvl1': depth histograms and their TV-L1 minimiser in place of the running mean (tvl1.py) -----------
+    def _tvl1_options(self):
+        """None (any other mode) or {n_bins, lam, iterations, every}: FUSION_MODEL hist_bins (default 9), tvl1_lambda (2.0),
+        tvl1_iterations (25; warm-started, after every tvl1_every (1) frames of a scene)."""
+        if not self._tvl1:
+            return None
+        fm = self.config.FUSION_MODEL
+        o = dict(n_bins=int(fm.get('hist_bins', 9)), lam=float(fm.get('tvl1_lambda', 2.0)), iterations=int(fm.get('tvl1_iterations', 25)),
+                 every=int(fm.get('tvl1_every', 1)))
+        if not 2 <= o['n_bins'] <= _lib.HIST_MAX_BINS or not 0.0 < o['lam'] < float('inf') or o['iterations'] < 0 or o['every'] < 1:
+            raise ValueError('Pipeline: FUSION_MODEL hist_bins in 2..{}, tvl1_lambda > 0, tvl1_iterations >= 0 and tvl1_every >= 1 '
+                             'expected, got {}'.format(_lib.HIST_MAX_BINS, o))
+        return o
+
     # ---- FUSION_MODEL.name 'tsdf': classical projective TSDF averaging, no network (projective.py) -------------------------
     def _fuse_classical(self, batches, sems, database):
         """The frame steps of ``batches`` (in order) as projective.integrate_depth calls: the frame, mask, pose and labels that
@@ -735,7 +754,9 @@ class Pipeline(torch.nn.Module):
         ``sems[i]``: the frame's (sem_ids, scores) from a batched 2-D pass, or None.  FUSION_MODEL keys: truncation
         (default DATA.init_value), max_weight (128), carve (False); with fuse_color, the images of a run go into the scene's
         colour volume as one call as well, and with fuse_label_probs its label images (the sem_ids the depth call fuses) into
-        the scene's class-distribution volume."""
+        the scene's class-distribution volume.  With FUSION_MODEL.name 'tvl1' the depth call is Database.integrate_depth_hist
+        (carve defaults to True; ids_est / scores are left alone), a run also ends where a scene's frame count reaches a
+        multiple of tvl1_every, and Database.regularize(restart=False) follows it there."""
         from . import projective
         fm = self.config.FUSION_MODEL
         kw = dict(truncation=fm.get('truncation', None) or self.config.DATA.init_value,
@@ -744,6 +765,9 @@ class Pipeline(torch.nn.Module):
         sem = bool(self.config.DATA.semantics)
         color_kw = self._color_options()
         label_kw = self._label_options()
+        tv = self._tvl1_options()
+        if tv is not None:
+            kw['carve'] = bool(fm.get('carve', True))
         run, run_key = [], None
 
         def flush():
@@ -754,11 +778,16 @@ class Pipeline(torch.nn.Module):
             # (frame, mask, K, E, sem_ids, scores, image) per frame: every stack of the run is made once and serves all three calls
             depth, mask, K, E = (torch.stack([r[i] for r in run]) for i in range(4))
             labels, label_scores = (torch.stack([r[i] for r in run]) for i in (4, 5)) if sem else (None, None)
-            projective.integrate_depth(
-                volume['current'], volume['weights'], origin=volume['origin'], resolution=float(volume['resolution']),
-                depth=depth, mask=mask, intrinsics=K, extrinsics=E, ids=volume['ids_est'] if sem else None,
-                scores=volume['scores'] if sem else None, labels=labels, label_scores=label_scores, **kw)
-            self._commit_frame(database, scene_id, volume)
+            if tv is not None:
+                database.integrate_depth_hist(scene_id, depth, K, E, mask=mask, n_bins=tv['n_bins'], **kw)
+                if self._tvl1_frames[scene_id] % tv['every'] == 0:
+                    database.regularize(scene_id, lam=tv['lam'], iterations=tv['iterations'], restart=False, truncation=kw['truncation'])
+            else:
+                projective.integrate_depth(
+                    volume['current'], volume['weights'], origin=volume['origin'], resolution=float(volume['resolution']),
+                    depth=depth, mask=mask, intrinsics=K, extrinsics=E, ids=volume['ids_est'] if sem else None,
+                    scores=volume['scores'] if sem else None, labels=labels, label_scores=label_scores, **kw)
+                self._commit_frame(database, scene_id, volume)
             if color_kw is not None:
                 database.integrate_color(scene_id, torch.cat([r[6] for r in run]), depth, K, E, mask=mask, **color_kw)
             if label_kw is not None:
@@ -776,6 +805,11 @@ class Pipeline(torch.nn.Module):
             run.append((frame, mask, torch.as_tensor(b['intrinsics'][0]).detach().cpu().to(torch.float64), E[:3], sem_ids, scores,
                         b['image'].to(self.device) if color_kw is not None else None))
             self._frames_fused += 1
+            if tv is not None:
+                self._tvl1_frames[scene_id] = self._tvl1_frames.get(scene_id, 0) + 1
+                if self._tvl1_frames[scene_id] % tv['every'] == 0:
+                    flush()
+                    run_key = None
         flush()
 
     # ---- several scenes per call (SURVEY.md §7 "hard parts") ------------------------------------------
@@ -792,6 +826,8 @@ class Pipeline(torch.nn.Module):
         join, and with FUSION_MODEL.fuse_label_probs their label votes - for ``semantic_strategy: gt``; the learned modes refuse
         'predict' here (the ids of the batched 2-D pass stay inside the side-by-side frame steps; ``fuse`` and ``fuse_sequence``
         take it, and so does the classical mode)."""
+        if self._tvl1:
+            raise ValueError('Pipeline.fuse_many: FUSION_MODEL.name "tvl1" is supported by fuse and fuse_sequence only')
         if not self._classical and self._label_options() is not None and self.config.DATA.semantic_strategy == 'predict':
             raise ValueError('Pipeline.fuse_many: FUSION_MODEL.fuse_label_probs with semantic_strategy "predict" is supported by '
                              'fuse and fuse_sequence only (and by FUSION_MODEL.name "tsdf")')
