@@ -1044,6 +1044,48 @@ int ojf_tvl1_solve(const uint16_t *hist_dev, int n_bins, int X, int Y, int Z, fl
 int ojf_tvl1_write(const uint16_t *hist_dev, int n_bins, int X, int Y, int Z, const float *u_dev, float trunc,
                    uint16_t *tsdf_dev /* fp16 [X,Y,Z] */, uint16_t *weights_dev /* fp16 [X,Y,Z] */, ojf_stream_t stream);
 
+/* ---- LABEL TV (the fused class distributions regularised in space: the convex relaxation of the Potts model on the label
+ * volume; definition: csrc/ojf_label_tv.hip; the reference has no counterpart) -------------------------------
+ * probs_dev is a label volume as ojf_fuse_label_probs makes it: fp16 [X,Y,Z,S], 16-byte aligned, S = 8 * ceil((C + 1) / 8),
+ *   channels 0..C-1 = P_k, channel C = W (a voxel with W > 0 is observed), here with 2 <= C <= OJF_LABEL_TV_MAX_CLASSES.
+ *   The solver minimises  sum_k TV(u_k) - lambda * sum_x omega(x) <u(x), P(x)>  over fields with u(x) in the simplex at
+ *   every observed voxel, omega = min(W, w_sat) / w_sat; an edge between two 6-neighbours counts when both are observed and
+ *   inside the box; unobserved voxels are never written and never influence an observed one.
+ * The workspace (256-byte aligned, owned by one probs_dev and box between calls): a 256-byte header {u32 count of listed
+ *   bricks, i32 status, ...}, then for the nb = ceil(X/4) * ceil(Y/8) * ceil(Z/32) bricks of 4 x 8 x 32 voxels, each part
+ *   rounded up to 256 bytes: u32 [nb] (brick holds an observed voxel), i32 [nb] (brick -> slot, -1: not listed), u32 [nb]
+ *   (slot -> brick), u8 [nb][1024] (voxel flags; bit 3: observed; voxel (lx, ly, lz) of a brick at (lx * 8 + ly) * 32 + lz),
+ *   and then the state, f32 [capacity][C][1024] five times: u, ub, p_x, p_y, p_z - 20 * C * 1024 bytes per listed brick.
+ * ojf_label_tv_workspace_bytes: the bytes for `capacity_bricks` slots; with 0, what ojf_label_tv_setup alone needs (and where
+ *   the state begins: a larger workspace starts with the same bytes).  0 for what it refuses.
+ * ojf_label_tv_setup: the set-up pass - flags, brick list, slot table - and the count of listed bricks into the header and
+ *   into *count_dev (device memory), which is what the caller sizes the state by.  Two launches; never waits.
+ * ojf_label_tv_solve: mode OJF_LABEL_TV_RESTART sets u = ub = the simplex projection of P and a zero dual on the listed
+ *   bricks; OJF_LABEL_TV_CONTINUE goes on from the state the previous call with the same capacity left - N iterations in one
+ *   call give the bits of any split of N over consecutive calls.  There is no refresh: when probs_dev took views, set up and
+ *   restart.  lambda > 0, w_sat > 0, tau, sigma > 0 with tau * sigma <= 1/12, iterations >= 0.  *status_dev (device memory)
+ *   and the header's status: 0 solved; 1 more bricks are listed than capacity_bricks - every kernel of the solve and of a
+ *   following write does nothing; 2 there is no state to work on (no set-up pass on this workspace, a continue before any
+ *   restart or with another capacity or class count).  One launch, one more for a restart, two per iteration; never waits.
+ * ojf_label_tv_write: for every observed voxel ids_dev u8 [X,Y,Z] = the smallest k with the largest u_k, scores_dev fp16
+ *   [X,Y,Z] = that u_k, and, if probs_out_dev is given (a record volume of the same C, 16-byte aligned; probs_dev itself is
+ *   allowed), its channels k = u_k with W copied bit for bit and the padding untouched.  Every other voxel keeps what it holds.
+ * Bad arguments (probs_dev off the 16-byte grid, n_classes outside 2..OJF_LABEL_TV_MAX_CLASSES, tau * sigma > 1/12,
+ *   lambda <= 0, w_sat <= 0, negative iterations, a misaligned or short workspace) are refused before any HIP call.  The exact
+ *   fp32 operation order is in csrc/ojf_label_tv.hip. */
+#define OJF_LABEL_TV_MAX_CLASSES 32
+#define OJF_LABEL_TV_CONTINUE 0
+#define OJF_LABEL_TV_RESTART 1
+size_t ojf_label_tv_workspace_bytes(int X, int Y, int Z, int n_classes, uint32_t capacity_bricks);
+int ojf_label_tv_setup(const uint16_t *probs_dev /* fp16 [X,Y,Z,S] */, int n_classes, int X, int Y, int Z, void *workspace_dev,
+                       size_t workspace_bytes, uint32_t *count_dev, ojf_stream_t stream);
+int ojf_label_tv_solve(const uint16_t *probs_dev, int n_classes, int X, int Y, int Z, float lambda, float w_sat, float tau, float sigma,
+                       int iterations, int mode, uint32_t capacity_bricks, void *workspace_dev, size_t workspace_bytes,
+                       int32_t *status_dev, ojf_stream_t stream);
+int ojf_label_tv_write(const uint16_t *probs_dev, int n_classes, int X, int Y, int Z, const void *workspace_dev, size_t workspace_bytes,
+                       uint8_t *ids_dev /* u8 [X,Y,Z] */, uint16_t *scores_dev /* fp16 [X,Y,Z] */,
+                       uint16_t *probs_out_dev /* fp16 [X,Y,Z,S] or NULL */, ojf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,7 @@ RASTER_MAX_VIEWS = 32  # include/ojf.h OJF_RASTER_MAX_VIEWS
 LABEL_MAX_VIEWS = 32  # include/ojf.h OJF_LABEL_MAX_VIEWS
 HIST_MAX_BINS, HIST_MAX_VIEWS = 15, 32  # include/ojf.h OJF_HIST_MAX_BINS / OJF_HIST_MAX_VIEWS
 TVL1_CONTINUE, TVL1_RESTART, TVL1_REFRESH, TVL1_ALL_BRICKS = 0, 1, 2, 4  # include/ojf.h OJF_TVL1_*
+LABEL_TV_MAX_CLASSES, LABEL_TV_CONTINUE, LABEL_TV_RESTART = 32, 0, 1  # include/ojf.h OJF_LABEL_TV_*
 RESAMPLE_REPLACE, RESAMPLE_MERGE = 0, 1  # include/ojf.h OJF_RESAMPLE_REPLACE / OJF_RESAMPLE_MERGE
 MESH_DISTANCE_BIN, MESH_DISTANCE_SCAN, MESH_DISTANCE_FILL, MESH_DISTANCE_GATHER, MESH_DISTANCE_ALL = 1, 2, 4, 8, 15  # OJF_MESH_DISTANCE_*
 COMPONENTS_BRICK, COMPONENTS_SEAM, COMPONENTS_FLATTEN, COMPONENTS_RANK, COMPONENTS_LIST, COMPONENTS_ALL = 1, 2, 4, 8, 16, 31  # OJF_COMPONENTS_*
@@ -246,6 +247,14 @@ SIGNATURES = {
     'ojf_tvl1_solve': (_i, [_vp, _i, _i, _i, _i, _f, _f, _f, _i, _i, _vp, _vp, _sz, _vp]),
     # histogram volume, n_bins, X, Y, Z, u, trunc, tsdf, weights, stream
     'ojf_tvl1_write': (_i, [_vp, _i, _i, _i, _i, _vp, _f, _vp, _vp, _vp]),
+    'ojf_label_tv_workspace_bytes': (_sz, [_i, _i, _i, _i, _c.c_uint32]),
+    # label volume, n_classes, X, Y, Z, workspace, workspace_bytes, count, stream
+    'ojf_label_tv_setup': (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    # label volume, n_classes, X, Y, Z, lambda, w_sat, tau, sigma, iterations, mode, capacity_bricks, workspace, workspace_bytes,
+    # status, stream
+    'ojf_label_tv_solve': (_i, [_vp, _i, _i, _i, _i, _f, _f, _f, _f, _i, _i, _c.c_uint32, _vp, _sz, _vp, _vp]),
+    # label volume, n_classes, X, Y, Z, workspace, workspace_bytes, ids, scores, probs_out or NULL, stream
+    'ojf_label_tv_write': (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
 }
 
 _LIB = None

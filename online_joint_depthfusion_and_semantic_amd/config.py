@@ -51,7 +51,10 @@ def default_config(h=240, w=320, semantics=False, use_semantics=None, n_classes=
                          'fuse_color': False, 'color_band': init_value,
                          # also cast every fused frame's label image as a one-hot vote into a per-voxel class distribution per
                          # scene (label_probs.py), within label_band of the surface; Database.decide_labels() turns it into labels
-                         'fuse_label_probs': False, 'label_band': init_value},
+                         'fuse_label_probs': False, 'label_band': init_value,
+                         # None: off; a dict of lam / iterations / w_sat: the labels of the class distributions are decided by
+                         # Database.regularize_labels (label_tv.py: neighbours have a say), not by decide_labels
+                         'label_tv': None},
         'SEMANTIC_2D_MODEL': {'stage': 2, 'n_classes': n_classes},
         'TRAINING': {'optimization': {'accumulation_steps': 8, 'clipping': True}},
         'TESTING': {'outlier_filter_val': 2, 'track_invalid_poses': False},

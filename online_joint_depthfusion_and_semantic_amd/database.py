@@ -69,6 +69,7 @@ class Database(torch.utils.data.Dataset):
         self.depth_hists = {}  # scene -> (fp16 [X,Y,Z,S] depth histograms, n_bins) (tvl1.py), only for scenes integrate_depth_hist was called on
         self._tvl1_solvers = {}  # scene -> tvl1.Solver: u and the workspace of regularize, kept for warm starts
         self._tvl1_changed = set()  # scenes whose histograms took views since their solver last ran
+        self._label_tv_solvers = {}  # scene -> label_tv.Solver: the workspace of regularize_labels, kept for the next call
         self.tracked_poses = {}  # frame_id -> f64 [4,4] camera-to-world: frames fused with a tracked pose (drivers.test_fusion)
 
         for s in dataset.scenes:
@@ -156,6 +157,7 @@ class Database(torch.utils.data.Dataset):
                 self.colors[s] = host(self.colors[s])
             if self.label_probs.get(s) is not None:
                 self.label_probs[s] = host(self.label_probs[s])
+                self._label_tv_solvers.pop(s, None)
             if self.depth_hists.get(s) is not None:
                 self.depth_hists[s] = (host(self.depth_hists[s][0]), self.depth_hists[s][1])
                 self._tvl1_solvers.pop(s, None)  # (the solver's state is not carried to the host: the next regularize restarts)
@@ -180,6 +182,7 @@ class Database(torch.utils.data.Dataset):
                 ops.volume_fill(p, 0.0)
             elif p is not None:
                 self.label_probs[s] = np.zeros(p.shape, dtype=np.float16)
+            self._label_tv_solvers.pop(s, None)
             if self.depth_hists.get(s) is not None:
                 hist, n_bins = self.depth_hists[s]
                 if _is_dev(hist):
@@ -211,6 +214,7 @@ class Database(torch.utils.data.Dataset):
         self.label_probs.pop(scene_id, None)
         self.depth_hists.pop(scene_id, None)
         self._tvl1_solvers.pop(scene_id, None)
+        self._label_tv_solvers.pop(scene_id, None)
         if self.semantics:
             self.ids_est[scene_id] = None
             self.scores[scene_id] = None
@@ -514,6 +518,27 @@ class Database(torch.utils.data.Dataset):
             ids, scores = self.ids_est[s].volume, self.scores[s].volume
             self._resident(s, 'decide_labels', vol, ids, scores)
             label_probs.decide_labels(vol, self.n_classes, ids, scores)
+
+    def regularize_labels(self, scene_id=None, lam=4.0, iterations=30, w_sat=4.0, keep_distribution=False):
+        """``decide_labels`` with the neighbours having a say (label_tv.py): solve the multi-label TV problem of the
+        class-distribution volumes - of one scene, or of every scene that has one - from a restart (``iterations``
+        Chambolle-Pock iterations, data weight ``lam``, a voxel's distribution counting in full from the fusion weight
+        ``w_sat``) and write the decision into ids_est / scores, the volumes ``decide_labels`` writes; the voxels without a vote
+        keep what they hold.  keep_distribution: the scene's class-distribution volume takes the regularised distribution
+        (its weights stay)."""
+        from . import label_tv
+        for s in ([scene_id] if scene_id is not None else list(self.label_probs)):
+            vol = self.label_probs.get(s)
+            if vol is None:
+                raise ValueError('Database.regularize_labels: scene {!r} has no class-distribution volume (integrate_label_probs)'.format(s))
+            ids, scores = self.ids_est[s].volume, self.scores[s].volume
+            self._resident(s, 'regularize_labels', vol, ids, scores)
+            solver = self._label_tv_solvers.get(s)
+            if solver is None or solver.shape != tuple(vol.shape[:3]) or solver.device != vol.device or solver.n_classes != self.n_classes:
+                solver = label_tv.Solver(vol.shape[:3], self.n_classes, vol.device)
+            solver.solve(vol, lam=lam, iterations=iterations, w_sat=w_sat)
+            solver.write(ids, scores, vol if keep_distribution else None)
+            self._label_tv_solvers[s] = solver
 
     # ---- the box: re-box, resample, merge (resample.py) ------------------------------------------------------
     def _estimated_volumes(self, scene_id, who):

@@ -163,7 +163,11 @@ def test_fusion(config, dataset, device, rank=0, world=1, state_dict=None, log=p
     database.filter(value=config.TESTING.outlier_filter_val)  # on device; to_numpy() only for export
     semantics = bool(config.DATA.semantics)
     if semantics and config.FUSION_MODEL.get('fuse_label_probs', False):
-        database.decide_labels()  # the per-voxel vote replaces the one-slot labels wherever a frame voted (label_probs.py)
+        label_tv = config.FUSION_MODEL.get('label_tv', None)
+        if label_tv is not None:
+            database.regularize_labels(**{k: label_tv[k] for k in ('lam', 'iterations', 'w_sat') if k in label_tv})  # (label_tv.py)
+        else:
+            database.decide_labels()  # the per-voxel vote replaces the one-slot labels wherever a frame voted (label_probs.py)
     if semantics:
         database.filter_semantics(value=5)  # test_fusion.py:88-89
 
