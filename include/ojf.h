@@ -1086,6 +1086,37 @@ int ojf_label_tv_write(const uint16_t *probs_dev, int n_classes, int X, int Y, i
                        uint8_t *ids_dev /* u8 [X,Y,Z] */, uint16_t *scores_dev /* fp16 [X,Y,Z] */,
                        uint16_t *probs_out_dev /* fp16 [X,Y,Z,S] or NULL */, ojf_stream_t stream);
 
+/* ---- FRAMES (the live depth frame made ready for tracking and fusion: edge rejection, bilateral filter, vertex / normal map;
+ * definition: csrc/ojf_frames.hip; the reference only erodes its depth maps) ----------------------------------
+ * ojf_depth_prepare: n frames depth_dev f32 [n,h,w] (with mask_dev u8 [n,h,w] or NULL) through, in this order,
+ *   validity (finite, near <= d <= far, mask != 0; an invalid pixel counts as d = 0 and is never a neighbour),
+ *   edge rejection (a valid pixel with a valid 8-neighbour further than edge_abs + edge_rel * d in depth is dropped; the test
+ *     reads the validity of the first step, so nothing cascades; off when both thresholds are 0),
+ *   a bilateral filter of radius 0..4 (0 copies) over the pixels that are left, with the spatial weights spatial_host f32
+ *     [(2 * radius + 1)^2] (row-major window, values in 0..1, centre 1; NULL for radius 0) and the polynomial range kernel
+ *     (1 - t^2)^2 for |t| < 1, t = (d_n - d) / (range0 + range2 * d^2),
+ *   the camera-space vertex map V = ((c - cx) * ifx * f, (r - cy) * ify * f, f) of the filtered depth f and its unit normals
+ *     (cross product of central differences, one-sided beside a pixel that is not valid; flipped to face the camera) - only
+ *     when normals_out_dev is given or cos_min != 0 - with K_host f32 [n][4] = (1/fx, 1/fy, cx, cy) per frame,
+ *   and an incidence test (a pixel without a normal, or whose normal makes a cosine below cos_min with the direction to the
+ *     camera, is dropped; off when cos_min == 0).
+ *   depth_out_dev f32 [n,h,w]: the filtered depth, 0 where the pixel is not valid - what every operator above reads as "no
+ *   depth"; valid_out_dev u8 [n,h,w] (0 / 1) or NULL; normals_out_dev f32 [n,h,w,3] or NULL, 0 where the pixel is not valid
+ *   or has no normal.  Every output element is written exactly once.
+ * One launch for all stages (per 64 frames): a workgroup keeps a 32 x 8 pixel tile with its halo of at most radius + 2 in
+ *   LDS from the raw frame to the outputs.  No global intermediate, no atomics, no workspace, never waits; the same bits on
+ *   every run and for every split of the frames into calls.
+ * Refused before any HIP call: null depth_dev / depth_out_dev; n, h, w < 1 or n * h * w >= 2^31; radius outside 0..4;
+ *   radius > 0 without spatial_host, or with a weight outside 0..1 or a centre that is not 1; range0 <= 0, range2 < 0, a
+ *   negative threshold, near < 0, far < near, cos_min outside 0..1, anything non-finite but far; K_host NULL with
+ *   normals_out_dev or cos_min != 0; a float pointer off the 4-byte grid; an output that overlaps an input or another output
+ *   (a tile reads its neighbours' pixels: there is no in-place operation).  The exact fp32 operation order is in
+ *   csrc/ojf_frames.hip. */
+int ojf_depth_prepare(const float *depth_dev /* f32[n,h,w] */, const uint8_t *mask_dev /* u8[n,h,w] or NULL */, int n, int h, int w,
+                      const float *K_host /* f32[n][4] or NULL */, int radius, const float *spatial_host, float range0, float range2,
+                      float edge_abs, float edge_rel, float near, float far, float cos_min, float *depth_out_dev,
+                      uint8_t *valid_out_dev /* or NULL */, float *normals_out_dev /* f32[n,h,w,3] or NULL */, ojf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

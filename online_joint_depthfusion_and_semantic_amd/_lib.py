@@ -255,6 +255,9 @@ SIGNATURES = {
     'ojf_label_tv_solve': (_i, [_vp, _i, _i, _i, _i, _f, _f, _f, _f, _i, _i, _c.c_uint32, _vp, _sz, _vp, _vp]),
     # label volume, n_classes, X, Y, Z, workspace, workspace_bytes, ids, scores, probs_out or NULL, stream
     'ojf_label_tv_write': (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
+    # depth, mask, n, h, w, K, radius, spatial, range0, range2, edge_abs, edge_rel, near, far, cos_min, depth out, valid out,
+    # normals out, stream
+    'ojf_depth_prepare': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _f, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
 }
 
 _LIB = None

@@ -54,7 +54,10 @@ def default_config(h=240, w=320, semantics=False, use_semantics=None, n_classes=
                          'fuse_label_probs': False, 'label_band': init_value,
                          # None: off; a dict of lam / iterations / w_sat: the labels of the class distributions are decided by
                          # Database.regularize_labels (label_tv.py: neighbours have a say), not by decide_labels
-                         'label_tv': None},
+                         'label_tv': None,
+                         # None: off; a dict of frames.prepare_depth options (range0, radius, sigma_space, edge_abs, ...): names
+                         # 'tsdf' and 'tvl1' send every frame and its mask through it first; the network modes refuse it
+                         'depth_filter': None},
         'SEMANTIC_2D_MODEL': {'stage': 2, 'n_classes': n_classes},
         'TRAINING': {'optimization': {'accumulation_steps': 8, 'clipping': True}},
         'TESTING': {'outlier_filter_val': 2, 'track_invalid_poses': False},

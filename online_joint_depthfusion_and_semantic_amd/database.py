@@ -45,6 +45,12 @@ def _to_dev(x, device):
     return None if x is None else torch.as_tensor(x).to(device)
 
 
+def _filtered(depth, mask, intrinsics, filter):
+    """(depth, mask) of a call's ``filter=`` dict: the device frames through frames.prepare_depth, the validity as the mask."""
+    from . import frames
+    return frames.filtered(depth, mask, intrinsics, filter)
+
+
 class Database(torch.utils.data.Dataset):
 
     def __init__(self, dataset, config):
@@ -399,29 +405,37 @@ class Database(torch.utils.data.Dataset):
                                                intrinsics=intrinsics, extrinsics=extrinsics, depth=out['depth'])
         return out
 
-    def track(self, scene_id, depth, intrinsics, extrinsics, reference_extrinsics=None, **kw):
+    def track(self, scene_id, depth, intrinsics, extrinsics, reference_extrinsics=None, filter=None, **kw):
         """Camera pose of a depth frame against the estimated volume of a scene (tracking.py, frame-to-model ICP):
         tracking starts at ``extrinsics`` and the model is ray-cast at ``reference_extrinsics`` (default: the same pose);
         ``kw`` goes to ``tracking.track_frame`` (mask, levels, iterations, thresholds).  Unobserved voxels are transparent.
+        ``filter``: a dict of ``frames.prepare_depth`` options - the frame and its mask go through it first (None: as they are).
         Returns {'extrinsics' f64 [4,4], 'ok', 'status', 'stats'}.  Works on resident and on host (to_numpy) state."""
         from . import tracking
         tsdf = self._device_volume(self.scenes_est[scene_id].volume, torch.float16)
         w = self._device_volume(self.fusion_weights[scene_id], torch.float16)
+        if filter is not None:
+            depth, kw['mask'] = _filtered(_to_dev(depth, tsdf.device), _to_dev(kw.get('mask'), tsdf.device), intrinsics, filter)
         return tracking.track_frame(tsdf, w, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]),
                                     depth=depth, intrinsics=intrinsics, extrinsics=extrinsics,
                                     reference_extrinsics=reference_extrinsics, **kw)
 
-    def integrate_depth(self, scene_id, depth, intrinsics, extrinsics, mask=None, labels=None, label_scores=None, **kw):
+    def integrate_depth(self, scene_id, depth, intrinsics, extrinsics, mask=None, labels=None, label_scores=None, filter=None, **kw):
         """Fuse one or more depth maps into the resident volumes of a scene by classical projective TSDF averaging
         (projective.py, no network): depth [h,w] / [n,h,w], poses as for ``render``; ``labels`` (u8, with optional
         ``label_scores``) also update ids_est / scores when the database has semantics; ``kw`` goes to
-        ``projective.integrate_depth`` (truncation - default: the initial value -, max_weight, near, carve)."""
+        ``projective.integrate_depth`` (truncation - default: the initial value -, max_weight, near, carve).  ``filter``: a dict of
+        ``frames.prepare_depth`` options (radius, sigma_space, range0, range2, edge_abs, edge_rel, near, far, max_angle) - the
+        depth maps and their mask go through it first, with these intrinsics (None: they are fused as they are); the same
+        keyword on ``integrate_color``, ``integrate_label_probs``, ``integrate_depth_hist`` and ``track``."""
         from . import projective
         tsdf, w = self.scenes_est[scene_id].volume, self.fusion_weights[scene_id]
         self._resident(scene_id, 'integrate_depth', tsdf, w)
         kw.setdefault('truncation', self.initial_value)
         sem = bool(self.semantics) and labels is not None
         dev = lambda x: _to_dev(x, tsdf.device)  # noqa: E731
+        if filter is not None:
+            depth, mask = _filtered(dev(depth), dev(mask), intrinsics, filter)
         projective.integrate_depth(tsdf, w, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]),
                                    depth=dev(depth), intrinsics=intrinsics, extrinsics=extrinsics, mask=dev(mask),
                                    ids=self.ids_est[scene_id].volume if sem else None,
@@ -429,26 +443,29 @@ class Database(torch.utils.data.Dataset):
                                    labels=dev(labels) if sem else None, label_scores=dev(label_scores) if sem else None, **kw)
         self.state[scene_id] = True
 
-    def integrate_color(self, scene_id, image, depth, intrinsics, extrinsics, mask=None, **kw):
+    def integrate_color(self, scene_id, image, depth, intrinsics, extrinsics, mask=None, filter=None, **kw):
         """Fuse the colour images of one or more frames into the scene's colour volume (color.py; allocated, zeroed, on first
         use): image u8 [n,]h,w,3|4 or float [n,]3,h,w on the 0..255 scale (the batch dict's), depth / mask / poses of the
         same frames as for ``integrate_depth``; ``kw`` goes to ``color.integrate_color`` (band - default: the initial value -,
-        max_weight, near).  Geometry and labels are not touched."""
+        max_weight, near); ``filter`` as for ``integrate_depth``.  Geometry and labels are not touched."""
         from . import color
         tsdf = self.scenes_est[scene_id].volume
         self._resident(scene_id, 'integrate_color', tsdf, optional=(self.colors.get(scene_id),))
         kw.setdefault('band', self.initial_value)
         dev = lambda x: _to_dev(x, tsdf.device)  # noqa: E731
+        if filter is not None:
+            depth, mask = _filtered(dev(depth), dev(mask), intrinsics, filter)
         with self._side_volume(self.colors, scene_id, lambda: color.new_volume(tsdf.shape, tsdf.device)) as vol:
             color.integrate_color(vol, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]), image=dev(image),
                                   depth=dev(depth), intrinsics=intrinsics, extrinsics=extrinsics, mask=dev(mask), **kw)
 
-    def integrate_label_probs(self, scene_id, depth, intrinsics, extrinsics, mask=None, probs=None, labels=None, **kw):
+    def integrate_label_probs(self, scene_id, depth, intrinsics, extrinsics, mask=None, probs=None, labels=None, filter=None, **kw):
         """Fuse the label observations of one or more frames into the scene's class-distribution volume (label_probs.py;
         allocated, zeroed, on first use): exactly one of ``probs`` (float [n,]h,w,>=n_classes, a distribution per pixel -
         ``SegEngine.predict_probs``) and ``labels`` (u8 [n,]h,w, a one-hot vote per pixel); depth / mask / poses of the same
         frames as for ``integrate_depth``; ``kw`` goes to ``label_probs.integrate_label_probs`` (band - default: the initial
-        value -, max_weight, near).  Geometry, ids_est and scores are not touched: ``decide_labels`` writes the labels."""
+        value -, max_weight, near); ``filter`` as for ``integrate_depth``.  Geometry, ids_est and scores are not touched:
+        ``decide_labels`` writes the labels."""
         from . import label_probs
         if not self.semantics:
             raise ValueError('Database.integrate_label_probs: the database has no semantics (n_classes)')
@@ -456,16 +473,18 @@ class Database(torch.utils.data.Dataset):
         self._resident(scene_id, 'integrate_label_probs', tsdf, optional=(self.label_probs.get(scene_id),))
         kw.setdefault('band', self.initial_value)
         dev = lambda x: _to_dev(x, tsdf.device)  # noqa: E731
+        if filter is not None:
+            depth, mask = _filtered(dev(depth), dev(mask), intrinsics, filter)
         with self._side_volume(self.label_probs, scene_id, lambda: label_probs.new_volume(tsdf.shape, self.n_classes, tsdf.device)) as vol:
             label_probs.integrate_label_probs(vol, self.n_classes, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]),
                                               depth=dev(depth), intrinsics=intrinsics, extrinsics=extrinsics, mask=dev(mask),
                                               probs=dev(probs), labels=dev(labels), **kw)
 
-    def integrate_depth_hist(self, scene_id, depth, intrinsics, extrinsics, mask=None, n_bins=9, **kw):
+    def integrate_depth_hist(self, scene_id, depth, intrinsics, extrinsics, mask=None, n_bins=9, filter=None, **kw):
         """Fuse one or more depth maps into the scene's depth-histogram volume (tvl1.py; allocated, zeroed, on first use; the bin
         count is fixed then): depth / mask / poses as for ``integrate_depth``; ``kw`` goes to ``tvl1.integrate_depth_hist``
-        (truncation - default: the initial value -, max_weight, near, carve).  The estimated TSDF and the fusion weights are not
-        touched: ``regularize`` writes them."""
+        (truncation - default: the initial value -, max_weight, near, carve); ``filter`` as for ``integrate_depth``.  The estimated
+        TSDF and the fusion weights are not touched: ``regularize`` writes them."""
         from . import tvl1
         tsdf = self.scenes_est[scene_id].volume
         have = self.depth_hists.get(scene_id)
@@ -474,6 +493,8 @@ class Database(torch.utils.data.Dataset):
             raise ValueError('Database.integrate_depth_hist: scene {!r} has histograms of {} bins, not {}'.format(scene_id, have[1], n_bins))
         kw.setdefault('truncation', self.initial_value)
         dev = lambda x: _to_dev(x, tsdf.device)  # noqa: E731
+        if filter is not None:
+            depth, mask = _filtered(dev(depth), dev(mask), intrinsics, filter)
         with self._side_volume(self.depth_hists, scene_id, lambda: (tvl1.new_volume(tsdf.shape, n_bins, tsdf.device), int(n_bins))) as (vol, B):
             tvl1.integrate_depth_hist(vol, B, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]), depth=dev(depth),
                                       intrinsics=intrinsics, extrinsics=extrinsics, mask=dev(mask), **kw)

@@ -36,6 +36,15 @@ class Pipeline(torch.nn.Module):
         config.FUSION_MODEL.resy = config.DATA.resy
 
         name = config.FUSION_MODEL.name
+        # FUSION_MODEL.depth_filter: None, or the frames.prepare_depth options every frame and its mask go through in front of the
+        # classical modes' fusion calls
+        self._depth_filter = config.FUSION_MODEL.get('depth_filter', None)
+        if self._depth_filter is not None:
+            if name not in ('tsdf', 'tvl1'):
+                raise ValueError('Pipeline: FUSION_MODEL.depth_filter is supported by FUSION_MODEL.name "tsdf" and "tvl1" only (the '
+                                 'fusion net\'s parity with the reference depends on the raw frame)')
+            from . import frames
+            frames.check_filter(dict(self._depth_filter))
         if name == 'v2':
             self._fusion_network = FusionNet_v2(config.FUSION_MODEL)
         elif name == 'v3':
@@ -778,6 +787,10 @@ class Pipeline(torch.nn.Module):
             # (frame, mask, K, E, sem_ids, scores, image) per frame: every stack of the run is made once and serves all three calls
             depth, mask, K, E = (torch.stack([r[i] for r in run]) for i in range(4))
             labels, label_scores = (torch.stack([r[i] for r in run]) for i in (4, 5)) if sem else (None, None)
+            if self._depth_filter is not None:
+                # once per run, for the depth, colour and label calls alike: what ``filter=`` on each of them would compute
+                from . import frames
+                depth, mask = frames.filtered(depth, mask, K, dict(self._depth_filter))
             if tv is not None:
                 database.integrate_depth_hist(scene_id, depth, K, E, mask=mask, n_bins=tv['n_bins'], **kw)
                 if self._tvl1_frames[scene_id] % tv['every'] == 0:
