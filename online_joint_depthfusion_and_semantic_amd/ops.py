@@ -116,6 +116,15 @@ class IntegrateWorkspace:
                                               mode, _lib.stream_ptr(device))
         _lib.check(rc, 'ojf_integrate_workspace_init')
 
+    GUARD_LATCH_WORD = 66  # csrc/ojf_integrate.h kGuardLatch: header word with the last call's range-guard decision
+
+    def guard_latch(self):
+        """A copy (4 bytes, device to device, on the current stream) of the range-guard decision of the last integrate call
+        enqueued with this workspace on this stream: non-zero = the call skipped, its frame did not reach the volumes.  The
+        workspace's own word is overwritten by the next call that uses it."""
+        at = 4 * self.GUARD_LATCH_WORD
+        return self.buf[at:at + 4].clone()
+
 
 def extract_to_net(depth, Ki, E, origin, resolution, tsdf, weights, engine, *, pad_value=-0.1):
     """``extract`` + ``engine.prepare_input`` in one launch (ojf_extract_to_net): the gathered values / weights and the raw

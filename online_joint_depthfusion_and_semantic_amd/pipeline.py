@@ -24,6 +24,22 @@ from .integrator import Integrator
 from .model import FusionNet_v2, FusionNet_v3
 
 
+def guard_frames_to_fuse_again(ring, records, device_count):
+    """Which remembered frames a range-guard recovery fuses again (FUSION_MODEL.guard_policy 'f32').  ``ring``: the remembered
+    frames in the order they were fused; ``records``: per frame, whether ITS integrate call skipped (the call's own latched
+    decision, Pipeline._guard_note); ``device_count``: the number of skipped integrate calls the device counted since the last
+    report.  Returns the skipped frames, in ring order - they need not be the last ones: with a stream per scene a later slot may
+    have latched "not set" before an earlier slot's net raised the flag.  Raises OjfError when the records and the device
+    disagree (a frame was skipped that nobody remembers, or the other way round): nothing can be fused again reliably then."""
+    if len(records) != len(ring):
+        raise _lib.OjfError('range guard: %d frames are remembered but %d records of their integrate calls' % (len(ring), len(records)))
+    again = [frame for frame, skipped in zip(ring, records) if skipped]
+    if len(again) != int(device_count):
+        raise _lib.OjfError('range guard: the device counted %d skipped frames, the records of the %d remembered frames say %d'
+                            % (int(device_count), len(ring), len(again)))
+    return again
+
+
 class Pipeline(torch.nn.Module):
 
     def __init__(self, config):
@@ -82,6 +98,8 @@ class Pipeline(torch.nn.Module):
         self.profile = False  # True / N: fuse() brackets its three stages with HIP events on every (N-th) frame
         self._frames_fused = 0
         self._marks = []
+        # fuse_training calls that found / did not find their batch announced (announce_training_frame)
+        self.announce_hits = self.announce_misses = 0
 
     # ---- live stage timing (HIP events on the launch stream; bench.py) ---------------------------
     def _mark(self, first=False):
@@ -593,10 +611,19 @@ class Pipeline(torch.nn.Module):
             return 'raise'
         return self.config.FUSION_MODEL.get('guard_policy', 'raise')
 
-    def _guard_remember(self, batch, database):
+    def _guard_note(self, slot, workspace):
+        """guard_policy 'f32': keeps, per slot, a copy of the decision the integrate call just enqueued on this stream will have
+        taken (ops.IntegrateWorkspace.guard_latch: the slot's workspace is reused by the slot's next call).  The healthy path's
+        whole cost: 4 bytes, device to device, per frame; nothing is read before a recovery."""
+        if self._guard_policy() == 'f32':
+            self.__dict__.setdefault('_guard_latches', {})[slot] = workspace.guard_latch()
+
+    def _guard_remember(self, batch, database, slot=0):
+        if self._guard_policy() != 'f32':  # (a frame fused behind a recovery, on the fp32 engine: there is nothing to recover to)
+            return
         ring = self.__dict__.setdefault('_guard_ring', [])
         marks = self.__dict__.setdefault('_guard_marks', [])
-        ring.append((batch, database))
+        ring.append((batch, database, self.__dict__.get('_guard_latches', {}).pop(slot, None)))
         if len(ring) % self._GUARD_EVERY == 0:
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(self.device))
@@ -624,10 +651,15 @@ class Pipeline(torch.nn.Module):
         lib.ojf_net_check(_lib.stream_ptr(self.device))  # (reports what `flag` said and clears it)
         ring = self.__dict__.get('_guard_ring', [])
         n = skipped.value
-        if n > len(ring):
-            raise _lib.OjfError('range guard: %d frames were skipped but only %d are remembered' % (n, len(ring)))
-        redo = ring[len(ring) - n:] if n else []
-        self.__dict__['_guard_ring'], self.__dict__['_guard_marks'] = [], []
+        # (every stream that fused a remembered frame has been joined to this one, which ojf_guard_status has drained: one read)
+        latches = [r[2] for r in ring]
+        if any(l is None for l in latches):
+            raise _lib.OjfError('range guard: a remembered frame has no record of its integrate call')
+        records = torch.stack(latches).cpu().ne(0).any(dim=1).tolist() if latches else []
+        redo = guard_frames_to_fuse_again([r[:2] for r in ring], records, n)
+        # per remembered frame, in order: (frame_id, did its integrate call skip) - which frames the recovery below fuses again
+        self.last_guard_skips = [(r[0]['frame_id'][0], s) for r, s in zip(ring, records)]
+        self.__dict__['_guard_ring'], self.__dict__['_guard_marks'], self.__dict__['_guard_latches'] = [], [], {}
         self.config.FUSION_MODEL.arithmetic = 'f32'
         self.guard_events = self.__dict__.get('guard_events', 0) + 1
         warnings.warn('split-fp16 range guard fired: FUSION_MODEL.arithmetic switched to f32 for this network, '
@@ -737,6 +769,7 @@ class Pipeline(torch.nn.Module):
                       sem_ids=sem_ids if sem else None, sem_scores=scores if sem else None,
                       id_vol=volume['ids_est'] if sem else None, score_vol=volume['scores'] if sem else None,
                       mode=self._integrate_mode, mask=mask)  # filtered frame of pipeline.py:196 formed in the kernels
+        self._guard_note(slot, ws)
         mark()
         self._commit_frame(database, scene_id, volume)
         return sem_ids
@@ -901,8 +934,8 @@ class Pipeline(torch.nn.Module):
                 raise
             # guard_policy 'f32': the frames of this call that were enqueued behind the event are among the skipped ones
             # (remember them first); the one the poll refused and those after it follow, one at a time on the fp32 engine
-            for b in batches[:enqueued]:
-                self._guard_remember(b, database)
+            for i, b in enumerate(batches[:enqueued]):
+                self._guard_remember(b, database, i)
             self._guard_recover(err)
             for b, sem in zip(batches[enqueued:], sems[enqueued:]):
                 self._fuse_guarded(b, database, sem, None, True)
@@ -910,8 +943,8 @@ class Pipeline(torch.nn.Module):
         for st in streams[:len(batches) - 1]:
             main.wait_stream(st)
         if recover:
-            for b in batches:
-                self._guard_remember(b, database)
+            for i, b in enumerate(batches):
+                self._guard_remember(b, database, i)  # (scene i ran on slot i: its own record)
 
     def _fuse_many_joint(self, batches, database, sems, fp, main, streams):
         """fuse_many's frame steps with the gather and the scatter of ALL scenes as single launches (round 6):
@@ -956,6 +989,8 @@ class Pipeline(torch.nn.Module):
             main.wait_stream(st)
         self._mark()
         ops.integrate_many([p['scatter'] for p in prep], n_points=P, n_tail=n_tail, trunc=self.config.DATA.init_value)
+        for i, p in enumerate(prep):  # (every scene of the launch latches for itself)
+            self._guard_note(i, p['scatter']['workspace'])
         self._mark()
         self._frames_fused += len(prep) - 1  # (the first mark counted one)
         for p in prep:
@@ -1010,7 +1045,12 @@ class Pipeline(torch.nn.Module):
             return int(mask_flat.sum())
         slots = self.__dict__.setdefault('_count_slots', [])
         at = self.__dict__.get('_count_at', 0)
-        if len(slots) < 4:  # a small ring: a slot is reused three frames later, long after its value was read
+        # A ring of four.  A frame step that was not announced reads its slot inside the same call.  An announcement's slot is read
+        # by the fuse_training call after next at the latest (_take_announced drops it then); with an announcement and a miss in
+        # every frame the requests in between are: the miss of the frame step in front of it, the next announcement, and - when
+        # it is dropped instead of read - the miss of its own frame step.  That is at most three newer requests while a value is
+        # still wanted, so the slot that the fourth reuses has been read or given up.
+        if len(slots) < 4:
             slots.append((torch.empty(1, dtype=torch.int32).pin_memory(), torch.cuda.Event()))
         buf, ev = slots[at % len(slots)]
         self.__dict__['_count_at'] = at + 1
@@ -1032,7 +1072,10 @@ class Pipeline(torch.nn.Module):
 
     # ---- training frame step (pipeline.py:251-363) -----------------------------------------------
     def announce_training_frame(self, batch, device=None):
-        """Tells the pipeline which batch the NEXT ``fuse_training`` call will bring (the same object).  The part of that frame
+        """Tells the pipeline which batch the ``fuse_training`` call AFTER the coming one will bring (the same object; call order
+        announce(i + 1), fuse_training(i) - announcing the very next call's batch works too).  Up to two announcements are held,
+        matched by object identity and consumed by the first ``fuse_training`` that brings the object; ``None`` clears them
+        (``_take_announced``).  The part of that frame
         step that depends on the batch alone - the filtered frame of pipeline.py:196 and the number of valid rays, the one value
         the host must read to shape ``tsdf_fused`` / ``tsdf_target`` [1, Nv, 9] - is enqueued NOW, in front of the current
         frame's work, so that its answer is on the host long before the next call asks for it.  Without the announcement the count
@@ -1042,12 +1085,37 @@ class Pipeline(torch.nn.Module):
         4.8-5.5 ms).  With it the host may run up to one frame ahead.  Optional and bit-neutral: the same launches, earlier.  The
         reference has no counterpart (its ``nonzero`` drains the queue in the middle of every frame, pipeline.py:125-131)."""
         if batch is None:
-            self.__dict__['_announced'] = None
+            self.__dict__['_announced'] = []
             return
         self.device = torch.device(device if device is not None else getattr(self, 'device', 'cpu'))
         frame, filtered = self._frames(batch)
         valid_mask = filtered.reshape(frame.numel()) != 0
-        self.__dict__['_announced'] = (batch, frame, filtered, valid_mask, self._async_count(valid_mask))
+        held = self.__dict__.setdefault('_announced', [])
+        # [batch, frame, filtered, valid_mask, count, fuse_training calls of OTHER batches it has seen]
+        held.append([batch, frame, filtered, valid_mask, self._async_count(valid_mask), 0])
+        del held[:-2]  # (the one waiting for the frame step in between, and this one)
+
+    def _take_announced(self, batch):
+        """The announcement of ``batch`` (the same object, on this call's device) or None, for ``fuse_training``.  The documented
+        order is announce(i + 1), fuse_training(i): an announcement outlives ONE frame step of another batch and is dropped by the
+        second, as is one made for another device.  ``announce_hits`` / ``announce_misses`` count the calls either way."""
+        hit, keep = None, []
+        # ('cuda' and 'cuda:<current>' are one device: a frame tensor's device always carries its index)
+        dev = torch.empty(0, device=self.device).device
+        for a in self.__dict__.get('_announced') or []:
+            if a[1].device != dev:
+                continue
+            if hit is None and a[0] is batch:
+                hit = a
+            elif a[5] == 0:
+                a[5] = 1
+                keep.append(a)
+        self.__dict__['_announced'] = keep
+        if hit is None:
+            self.announce_misses += 1
+        else:
+            self.announce_hits += 1
+        return hit
 
     def fuse_training(self, batch, database, device):
         if self._classical:
@@ -1055,9 +1123,9 @@ class Pipeline(torch.nn.Module):
                                'network to train (use "v2" or "v3")')
         self.device = torch.device(device)
         sem_ids, scores = self._frame_semantics(batch)
-        ann = self.__dict__.pop('_announced', None)
-        if ann is not None and ann[0] is batch and ann[1].device == self.device:
-            frames, valid_mask, count = ann[1:3], ann[3], ann[4]  # (enqueued a frame ago: the count is on the host by now)
+        ann = self._take_announced(batch)
+        if ann is not None:
+            frames, valid_mask, count = tuple(ann[1:3]), ann[3], ann[4]  # (enqueued a frame ago: the count is on the host by now)
         else:
             frames = valid_mask = count = None
         scene_id, volume, frame, filtered, Ki, E, h, w = self._prepare_frame(batch, database, filtered=True, frames=frames)

@@ -606,11 +606,12 @@ class HipTrainNet:
         drop_sig = tuple((i, d.p, mods[i][0].out_channels) for i, d in drops)
         scales = {}
         if drops:
-            keeps = self.__dict__.setdefault('_keeps', {})  # (per executor: a backward pass reads the factors of ITS forward pass)
-            keep = keeps.get(slot)
-            if keep is None or keep[0] != drop_sig or keep[1].device != dev:
+            # per executor (frame shape, device, slot), on its handle: a backward pass reads the factors of ITS forward pass, and the
+            # executor of another frame shape may run a forward pass in between
+            keep = tr.keep
+            if keep is None or keep[0] != drop_sig:
                 kv = torch.cat([torch.full((mods[i][0].out_channels,), 1.0 - d.p) for i, d in drops]).to(dev)
-                keep = keeps[slot] = (drop_sig, kv, torch.empty_like(kv), torch.empty_like(kv), torch.empty_like(kv, dtype=torch.bool))
+                keep = tr.keep = (drop_sig, kv, torch.empty_like(kv), torch.empty_like(kv), torch.empty_like(kv, dtype=torch.bool))
             rand, factors = keep[2], keep[3]
             torch.rand(rand.shape, device=dev, out=rand)
             torch.lt(rand, keep[1], out=keep[4])
@@ -782,6 +783,7 @@ class _TrainerHandle:
         self.gen = 0  # generation of the forward pass whose activations the trainer holds
         self.table = None   # this trainer's layer table (ojf_train_layer[n]): pointers / flags of ITS last forward pass
         self.grad_sig = None  # the p.grad tensors whose addresses the table holds (steady state of in-place accumulation)
+        self.keep = None  # Dropout2d: (layer signature, keep probabilities, draw, factors, mask) of this executor's forward passes
 
     def __del__(self):
         try:

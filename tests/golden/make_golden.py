@@ -8,7 +8,8 @@ imported unmodified, are the ground truth:
     modules/integrator.py Integrator.forward
     modules/pipeline.py   Pipeline.fuse / fuse_training (torchvision.models stubbed: AdapNet is
                           imported by pipeline.py but never constructed for semantic_strategy 'gt')
-    modules/model.py      FusionNet_v3
+    modules/model.py      FusionNet_v3, FusionNet_v2 (--net-v2)
+    utils/metrics.py      evaluation, semantic_evaluation (--semantic-evaluation)
 Rules: torch.set_num_threads(1) so that the reference's duplicate-index writes are
 deterministic ("highest entry wins"), seeded inputs from the shared synthetic generator, eval mode.
 
@@ -117,6 +118,22 @@ def save_npz_lzma(path, arrays):
             buf = io.BytesIO()
             np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
             z.writestr(k + '.npy', buf.getvalue())
+
+
+def save_npz_lzma_parts(prefix, arrays, limit=900 * 1024):
+    """save_npz_lzma into ``prefix``_p0.npz, _p1.npz, ...: arrays in their order, a new part whenever the raw bytes of
+    the current one would pass ``limit`` (random fp32 weights do not compress, and no committed file may pass 1 MiB).
+    tests/helpers.py::golden_parts reads them back as one dict."""
+    parts, size = [{}], 0
+    for k, v in arrays.items():
+        n = np.asanyarray(v).nbytes
+        if parts[-1] and size + n > limit:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += n
+    for i, part in enumerate(parts):
+        save_npz_lzma('%s_p%d.npz' % (prefix, i), part)
 
 
 def run_extract_integrate_box(h=13, w=15, frames=(0, 3)):
@@ -469,6 +486,59 @@ def run_training_train_mode(h=48, w=64, grid=64):
     return out
 
 
+def run_fusionnet_v2(h, w, use_semantics):
+    """The reference's FusionNet_v2 (modules/model.py:164-216) on its own: seeded state_dict, seeded inputs of the
+    form tests/test_net_gpu.py::_inputs draws, ``net_est`` [h * w, 9] in eval mode.  The semantic plane is built the
+    way modules/pipeline.py does, (1 + id) / n_classes with 30 classes."""
+    from modules.model import FusionNet_v2
+    mcfg = NS(n_points=9, growth_factor=6, use_semantics=use_semantics, output_scale=1.0, resx=w, resy=h)
+    torch.manual_seed(11)
+    net = FusionNet_v2(mcfg)
+    seeded_state(net, 11)
+    net.eval()
+    g = torch.Generator().manual_seed(21 + int(use_semantics))
+    x = dict(tsdf_values=(torch.rand(1, 9, h, w, generator=g) - 0.5) * 0.2,
+             tsdf_weights=torch.rand(1, 9, h, w, generator=g) * 4,
+             tsdf_frame=torch.rand(1, 1, h, w, generator=g) * 4)
+    sem_ids = torch.randint(0, 30, (h, w), generator=g, dtype=torch.uint8)
+    x['semantic_frame'] = ((1 + sem_ids.float()) / 30).view(1, 1, h, w)
+    with torch.no_grad():
+        y = net(x)
+    out = {'state_' + k: v.numpy() for k, v in net.state_dict().items()}
+    rows = lambda t: t[0].permute(1, 2, 0).reshape(h * w, -1).contiguous().numpy()
+    out['net_fusion_values'] = rows(x['tsdf_values'])
+    out['net_fusion_weights'] = rows(x['tsdf_weights'])
+    out['net_depth'] = x['tsdf_frame'][0, 0].numpy()
+    out['net_sem_ids'] = sem_ids.numpy()
+    out['net_est'] = rows(y)
+    return out
+
+
+def run_semantic_evaluation(n=12, n_class=12):
+    """utils/metrics.py:69-108 on a seeded n^3 case: classes 1-3 in both volumes, 4 and 5 only in the estimate, 6 and 7
+    only in the target, 8 only under the mask (so it is absent from both after masking), 9-11 absent everywhere; the
+    mask removes about a third of the voxels.  Kept: the inputs and both returned values (the per-class IoU as ids and
+    values in the order of the returned dict)."""
+    from utils import metrics as ref_metrics
+    rng = np.random.default_rng(12)
+    shape = (n, n, n)
+    target = rng.choice(np.array([0, 1, 2, 3, 6, 7], np.uint8), size=shape)
+    est = np.where(rng.random(shape) < 0.6, target, rng.choice(np.array([0, 1, 2, 3, 4, 5], np.uint8), size=shape))
+    est = np.where(np.isin(est, (6, 7)), 0, est).astype(np.uint8)
+    mask = rng.random(shape) < 0.65
+    hole = ~mask & (rng.random(shape) < 0.3)
+    est[hole] = 8
+    target[hole] = 8
+    m, cls_iou = ref_metrics.semantic_evaluation(est, target, mask, n_class)
+    e, t = est * mask, target * mask
+    assert set(np.unique(e)) == {0, 1, 2, 3, 4, 5} and set(np.unique(t)) == {0, 1, 2, 3, 6, 7}
+    assert sorted(cls_iou) == [0, 1, 2, 3, 4, 5, 6, 7] and 0 < mask.sum() < mask.size
+    ids = np.array(list(cls_iou), np.int64)
+    return dict(est=est, target=target, mask=mask, n_class=np.array(n_class), mean_acc=np.array(m['Mean Acc'], np.float64),
+                mean_iou=np.array(m['Mean IoU'], np.float64), cls_ids=ids,
+                cls_iou=np.array([cls_iou[k] for k in ids], np.float64))
+
+
 def probe_matmul():
     """Documents the fp32 accumulation order of the reference's two torch.matmul calls here."""
     from oracle import oracle
@@ -499,6 +569,13 @@ def full_size():
 def main():
     if '--probe-matmul' in sys.argv:
         print(probe_matmul())
+        return
+    if '--net-v2' in sys.argv:  # only the FusionNet_v2 fixtures
+        for tag, use_sem in (('sem', True), ('nosem', False)):
+            save_npz_lzma_parts(os.path.join(HERE, 'fusionnet_v2_%s_24x32' % tag), run_fusionnet_v2(24, 32, use_sem))
+        return
+    if '--semantic-evaluation' in sys.argv:  # only the utils/metrics.py semantic_evaluation fixture
+        np.savez_compressed(os.path.join(HERE, 'semantic_evaluation_12.npz'), **run_semantic_evaluation())
         return
     if '--box' in sys.argv:  # only the non-cubic-box fixture of the extract / integrate path
         save_npz_lzma(os.path.join(HERE, 'extract_integrate_box_13x15.npz'), run_extract_integrate_box())
@@ -538,6 +615,9 @@ def main():
     np.savez_compressed(os.path.join(HERE, 'train_v3_nosem_240x320_g256.npz'), **run_training_full_size())
     np.savez_compressed(os.path.join(HERE, 'train_trajectory_v3_nosem_48x64_g64.npz'), **run_training_trajectory())
     np.savez_compressed(os.path.join(HERE, 'train_mode_v3_nosem_48x64_g64.npz'), **run_training_train_mode())
+    for tag, use_sem in (('sem', True), ('nosem', False)):
+        save_npz_lzma_parts(os.path.join(HERE, 'fusionnet_v2_%s_24x32' % tag), run_fusionnet_v2(24, 32, use_sem))
+    np.savez_compressed(os.path.join(HERE, 'semantic_evaluation_12.npz'), **run_semantic_evaluation())
     print('golden vectors written to', HERE)
 
 

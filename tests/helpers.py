@@ -73,13 +73,32 @@ def golden(name):
     return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', name))
 
 
+class _Parts(dict):
+    files = property(lambda self: list(self))
+
+
+def golden_parts(prefix):
+    """The arrays of golden/<prefix>_p0.npz, _p1.npz, ... as one mapping (make_golden.py::save_npz_lzma_parts)."""
+    import glob
+    import os
+    paths = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', prefix + '_p[0-9].npz')))
+    assert paths, prefix
+    out = _Parts()
+    for p in paths:
+        with np.load(p) as z:
+            for k in z.files:
+                assert k not in out, k
+                out[k] = z[k]
+    return out
+
+
 def net_from_golden(g, use_semantics, h, w, version='v3'):
     import torch
     from online_joint_depthfusion_and_semantic_amd import model
     cfg = NS(n_points=9, growth_factor=6, use_semantics=use_semantics, output_scale=1.0, resx=w, resy=h)
     net = getattr(model, 'FusionNet_' + version)(cfg)
     state = {k[len('state_'):]: torch.from_numpy(g[k]) for k in g.files if k.startswith('state_')}
-    net.load_state_dict(state)
+    net.load_state_dict(state, strict=True)
     return net.eval()
 
 

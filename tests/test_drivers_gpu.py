@@ -197,11 +197,12 @@ def test_train_fusion_with_the_backward_pass_beside_the_next_frame_is_the_serial
     bit those of ``train_overlap: False``."""
     h, w, grid = 48, 64, 32
 
-    def run(overlap):
+    def run(overlap, announce=False):
         cfg = _training_defaults(default_config(h, w))
         cfg.SETTINGS.device = str(cuda)
         cfg.SETTINGS.seed = 5
         cfg.SETTINGS.eval_freq = 5
+        cfg.SETTINGS.announce_frames = announce
         if overlap is not None:
             cfg.FUSION_MODEL.train_overlap = overlap
         cfg.TRAINING.optimization.accumulation_steps = 3
@@ -212,6 +213,8 @@ def test_train_fusion_with_the_backward_pass_beside_the_next_frame_is_the_serial
         torch.cuda.synchronize()
         tn = pipe.__dict__['_hip_train']
         assert tn.overlap == (overlap is not False)
+        # SETTINGS.announce_frames: every training frame but the first arrives announced (the stream's poses are finite)
+        assert (pipe.announce_hits, pipe.announce_misses) == ((10, 1) if announce else (0, 11))
         net = pipe._fusion_network
         scene = next(iter(db.scenes_est))
         return (losses, [v.detach().clone() for v in net.state_dict().values()],
@@ -221,3 +224,6 @@ def test_train_fusion_with_the_backward_pass_beside_the_next_frame_is_the_serial
     for x, y in zip(a[1], b[1]):
         assert torch.equal(x, y)
     assert torch.equal(a[2].view(torch.int16), b[2].view(torch.int16)) and torch.equal(a[3].view(torch.int16), b[3].view(torch.int16))
+    c = run(None, announce=True)  # the announced loop (SETTINGS.announce_frames) takes its hit path and is the same loop again
+    assert c[0] == b[0] and all(torch.equal(x, y) for x, y in zip(c[1], b[1]))
+    assert torch.equal(c[2].view(torch.int16), b[2].view(torch.int16)) and torch.equal(c[3].view(torch.int16), b[3].view(torch.int16))

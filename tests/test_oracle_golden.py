@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle
-from helpers import NS, n_mismatch, golden, net_from_golden, oracle_net_est, oracle_fuse, fresh_volumes, make_stream
+from helpers import NS, n_mismatch, golden, golden_parts, net_from_golden, oracle_net_est, oracle_fuse, fresh_volumes, make_stream
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -110,6 +110,49 @@ def test_reference_pipeline_golden(sem):
     f = st.frame(3)
     est = oracle_net_est(net, g['net_fusion_values'], g['net_fusion_weights'], f['tof_depth'], f['semantic_gt'], 30, h, w)
     assert np.abs(est - g['net_est']).max() <= 1e-6
+
+
+@pytest.mark.parametrize('sem', [True, False])
+def test_reference_fusionnet_v2_golden(sem):
+    """The reference's FusionNet_v2 (modules/model.py:164-216), seeded state and inputs, eval mode, 24x32: the package's
+    ``model.FusionNet_v2`` takes that state_dict key for key (strict) and returns its ``net_est``.  Same ATen code on
+    both sides, so the difference is 0 with the same build; the bound is the v3 pin's."""
+    g = golden_parts('fusionnet_v2_%s_24x32' % ('sem' if sem else 'nosem'))
+    h, w = 24, 32
+    net = net_from_golden(g, sem, h, w, version='v2')
+    assert sum(1 for k in g.files if k.startswith('state_')) == len(net.state_dict())
+    est = oracle_net_est(net, g['net_fusion_values'], g['net_fusion_weights'], g['net_depth'], g['net_sem_ids'], 30, h, w)
+    assert g['net_est'].shape == (h * w, 9) and float(np.abs(g['net_est']).max()) > 1e-3
+    err = float(np.abs(est - g['net_est']).max())
+    print('FusionNet_v2 sem=%s: max |d| %.2e vs the reference' % (sem, err))
+    assert err <= 1e-6
+
+
+def _semantic_golden():
+    g = golden('semantic_evaluation_12.npz')
+    want_iou = dict(zip(g['cls_ids'].tolist(), g['cls_iou'].tolist()))
+    return g, int(g['n_class']), float(g['mean_acc']), float(g['mean_iou']), want_iou
+
+
+def test_reference_semantic_evaluation_golden():
+    """utils/metrics.py:69-108 of the reference on a seeded 12^3 case: classes 4, 5 only in the estimate, 6, 7 only in the
+    target, 8 only under the mask, 9-11 nowhere.  ``metrics.semantic_evaluation`` returns the same two values exactly;
+    so do ``volume_ref.confusion``'s counts through ``semantic_metrics_from_counts``."""
+    import volume_ref
+    from online_joint_depthfusion_and_semantic_amd import metrics
+    g, C, mean_acc, mean_iou, want_iou = _semantic_golden()
+    est, target, mask = g['est'], g['target'], g['mask']
+    e, t = est * mask, target * mask
+    assert set(np.unique(e)) - set(np.unique(t)) == {4, 5} and set(np.unique(t)) - set(np.unique(e)) == {6, 7}
+    assert 8 in np.unique(est) and 8 not in np.unique(e) and C == 12 and 0 < int(mask.sum()) < mask.size
+    m, iou = metrics.semantic_evaluation(est, target, mask, C)
+    assert m == {'Mean Acc': mean_acc, 'Mean IoU': mean_iou}
+    assert {int(k): float(v) for k, v in iou.items()} == want_iou and sorted(want_iou) == list(range(8))
+    hist, pe, pg, dropped = volume_ref.confusion(est, target, mask.astype(np.float16), C)
+    assert dropped == 0 and int(hist.sum()) == est.size
+    m2, iou2 = metrics.semantic_metrics_from_counts(hist, pe[:C], pg[:C])
+    assert m2 == {'Mean Acc': mean_acc, 'Mean IoU': mean_iou}
+    assert {int(k): float(v) for k, v in iou2.items()} == want_iou
 
 
 def test_fp16_conversions_exhaustive():

@@ -871,6 +871,113 @@ def test_range_guard_policy_f32_covers_fuse_sequence_and_fuse_many(cuda, entry):
             assert torch.equal(a.view(torch.int16), b.view(torch.int16)), s
 
 
+@pytest.mark.parametrize('launches,mode', [('slots', 'fast'), ('joint', 'fast'), ('slots', 'parity')])
+def test_range_guard_recovery_fuses_exactly_the_skipped_frames(cuda, launches, mode):
+    """guard_policy 'f32' in fuse_many when ONE scene's net trips: three scenes, three steps, and in step 1 the frame of the MIDDLE
+    scene alone leaves the fp16 range (a 4 x 4 patch of masked-out pixels carries a depth of 3e4 and the first convolution is
+    scaled by 100: ordinary frames reach a few hundred).  Whether the step-1 integrate calls of the two other scenes skip
+    depends on where their streams stand when the flag goes up - every scene latches for itself - so the skipped frames need not
+    be the last ones remembered.  The recovery must fuse again exactly the frames whose own record says "skipped":
+
+        skipped in step 1                       f16x3, f32 (fused again), f32
+        enqueued in step 1 and not skipped      f16x3, f16x3, f32
+        refused by the host's poll in step 1    f16x3, f32, f32   (the event was noticed before the frame was enqueued: it is in
+                                                                   no record and runs on the fp32 engine - the first history)
+
+    (a step-2 frame is enqueued behind the event on every stream: it runs on the fp32 engine or is skipped and fused again on it).
+    Both histories come from a 'raise' pipeline whose arithmetic is set by hand, frame by frame, through fuse().  The tripping
+    scene equals the first, every other scene the one its record names: TSDF and weights, bit for bit.  With the earlier rule
+    (the last n remembered frames) a recovery with only the middle scene skipped fused the last scene's frame twice and lost
+    the middle one's (tests/test_guard_recover_host.py shows the rule itself)."""
+    from online_joint_depthfusion_and_semantic_amd import _lib
+    from online_joint_depthfusion_and_semantic_amd.synthetic import SyntheticDataset
+    h, w, grid, S, steps = 48, 64, 64, 3, 3
+    scenes = tuple('room_%d' % k for k in range(S))
+    mid = scenes[1]
+
+    def build(policy):
+        cfg = default_config(h, w, semantics=False, use_semantics=False, integrate_mode=mode)
+        cfg.SETTINGS.device = str(cuda)
+        cfg.FUSION_MODEL.guard_policy = policy
+        cfg.SETTINGS.fuse_many_launches = launches
+        torch.manual_seed(5)
+        pipe = Pipeline(cfg)
+        for m in pipe._fusion_network.modules():
+            if isinstance(m, torch.nn.Conv2d):
+                torch.nn.init.xavier_normal_(m.weight)
+        with torch.no_grad():
+            pipe._fusion_network.block0[0].block[0].weight.mul_(100.0)
+        return cfg, pipe.to(cuda).eval()
+
+    ds = SyntheticDataset(h, w, grid, 8, scenes=scenes)
+
+    def database(cfg):
+        return Database(ds, database_config(cfg))
+
+    def batch(s, i):
+        b = ds.streams[s].batch(i)
+        if (s, i) == (mid, 1):  # the trigger: in this frame's data, outside its mask (no volume ever sees these pixels)
+            b['tof_depth'][0, 5:9, 7:11] = 3.0e4
+            b['mask'][0, 5:9, 7:11] = False
+        return {k: (v.to(cuda) if torch.is_tensor(v) else v) for k, v in b.items()}
+
+    cfg, pipe = build('f32')
+    cfg_r, ref = build('raise')
+    ref._fusion_network.load_state_dict(pipe._fusion_network.state_dict())
+    with torch.no_grad():
+        # precondition: that frame alone trips the guard, every other frame of the test alone does not
+        scratch = database(cfg_r)
+        for i in range(steps):
+            for s in scenes:
+                ref.fuse(batch(s, i), scratch, cuda)
+                if (s, i) == (mid, 1):
+                    with pytest.raises(_lib.OjfError, match='fp16 range'):
+                        ref.check()
+                ref.check()
+        # the two histories per scene (the middle scene has only the first: its step-1 frame cannot pass in f16x3)
+        db_again, db_kept = database(cfg_r), database(cfg_r)
+        for s in scenes:
+            ref.fuse(batch(s, 0), db_again, cuda)
+            ref.fuse(batch(s, 0), db_kept, cuda)
+        for s in scenes:
+            if s != mid:
+                ref.fuse(batch(s, 1), db_kept, cuda)
+        ref.check()
+        cfg_r.FUSION_MODEL.arithmetic = 'f32'
+        for s in scenes:
+            ref.fuse(batch(s, 1), db_again, cuda)
+        for s in scenes:
+            ref.fuse(batch(s, 2), db_again, cuda)
+            if s != mid:
+                ref.fuse(batch(s, 2), db_kept, cuda)
+        ref.check()
+
+        db = database(cfg)
+        with pytest.warns(RuntimeWarning, match='switched to f32'):
+            for i in range(steps):
+                pipe.fuse_many([batch(s, i) for s in scenes], db, cuda)
+            pipe.check()
+    assert pipe.guard_events == 1 and cfg.FUSION_MODEL.arithmetic == 'f32'
+    records = dict(pipe.last_guard_skips)  # the frames remembered when the event was noticed: frame_id -> its call skipped
+    skipped = {fid for fid, skip in records.items() if skip}
+    print('range guard, %s / %s: skipped and fused again: %s; enqueued in front of the event: %s'
+          % (launches, mode, sorted(skipped), sorted(set(records) - skipped)))
+    assert all(int(fid.split('/')[-1]) >= 1 for fid in skipped)  # (step 0 was healthy)
+    # a step-1 frame went through on f16x3 only if it was enqueued, remembered and its own record says "not skipped"; one whose
+    # frame step the host's poll refused (the event was noticed inside step 1) was never enqueued on f16x3: it is in no
+    # record and ran on the fp32 engine, like a skipped one
+    step1 = {s: records.get(ds.streams[s].frame(1)['frame_id'], True) for s in scenes}
+    assert step1[mid] and ds.streams[mid].frame(1)['frame_id'] in skipped
+    for s in scenes:
+        want = db_again if step1[s] else db_kept
+        assert float((db.fusion_weights[s].float() > 0).sum()) > 1000
+        for a, b in zip(_volumes(db, s), _volumes(want, s)):
+            assert torch.equal(a.view(torch.int16), b.view(torch.int16)), (s, step1[s])
+    # (a frame lost or fused twice moves thousands of voxels; the two histories themselves differ by the arithmetic of one frame)
+    print('voxels that tell the two histories of %s apart: %d' % (scenes[0], int(
+        (_volumes(db_again, scenes[0])[0].view(torch.int16) != _volumes(db_kept, scenes[0])[0].view(torch.int16)).sum())))
+
+
 def test_single_frame_and_batched_2d_graphs_share_one_engine(cuda):
     """fuse() (B = 1 graph of the 2-D engine), fuse_many() (B = S graph), fuse() again on ONE pipeline: each captured graph
     addresses its own decoder concat buffers by raw pointer, so neither batch size may evict the other's (the
@@ -982,11 +1089,16 @@ def test_announced_training_frames_change_no_bit(cuda):
         opt = torch.optim.RMSprop(pipe._fusion_network.parameters(), lr=1e-3)
         torch.manual_seed(12)  # the Dropout2d draws
         batches = [_batch(st, i, cuda) for i in range(frames + 1)]
-        outs = []
+        outs, hits = [], []
+        stranger = _batch(st, 0, cuda)
         for i in range(frames):
             if announce:  # frame 3 is announced wrongly (another object): its own count is computed in the call
-                pipe.announce_training_frame(batches[i + 1] if i != 2 else _batch(st, 0, cuda), cuda)
+                pipe.announce_training_frame(batches[i + 1] if i != 2 else stranger, cuda)
             out = pipe.fuse_training(batches[i], db, cuda)
+            hits.append(pipe.announce_hits)
+            # the stranger waits through frame 2 (the documented order: announced one frame step ahead), then it is dropped unused
+            assert any(a[0] is stranger for a in pipe.__dict__.get('_announced', [])) == (announce and i == 2)
+            assert len(pipe.__dict__.get('_announced', [])) <= 1
             loss = (out['tsdf_fused'] - out['tsdf_target']).abs().mean()
             loss.backward()
             outs.append((out['tsdf_est'].detach().clone(), out['tsdf_fused'].detach().clone(), loss.detach().clone()))
@@ -994,6 +1106,12 @@ def test_announced_training_frames_change_no_bit(cuda):
                 opt.step()
                 opt.zero_grad(set_to_none=False)
         torch.cuda.synchronize()
+        # frames 1, 2, 4 and 5 arrive announced; frame 0 never was, and frame 3's announcement was the stranger
+        assert (pipe.announce_hits, pipe.announce_misses) == ((4, 2) if announce else (0, frames))
+        assert hits == ([0, 1, 2, 2, 3, 4] if announce else [0] * frames)
+        pipe.announce_training_frame(batches[frames], cuda)
+        pipe.announce_training_frame(None)
+        assert pipe.__dict__['_announced'] == []
         net = pipe._fusion_network
         return (outs, [p.detach().clone() for p in net.parameters()], [b.detach().clone() for b in net.buffers()],
                 [db.scenes_est[st.scene].volume.clone(), db.fusion_weights[st.scene].clone()])

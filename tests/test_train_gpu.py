@@ -541,6 +541,63 @@ def test_two_frame_sizes_interleaved_keep_their_own_tables(cuda):
             assert float((a - b).abs().max()) <= 2e-5 * max(float(a.abs().max()), 1e-3 * gmax)
 
 
+def test_two_frame_shapes_alive_at_once_keep_their_own_dropout_factors(cuda):
+    """One HipTrainNet in train() mode, Dropout2d active, two executors alive at once (the two smallest frames of
+    train_edge_cases.EXECUTOR_FRAMES; A is the larger one: under batch statistics a 1 x 1 frame passes no gradient through a
+    BatchNorm2d, so its backward pass could not show which factors it read).  From the same seeds
+
+        serial       forward A, backward A, forward B, backward B
+        interleaved  forward A, forward B, backward A, backward B
+
+    draw from the generator in the same order and accumulate the gradients in the same order: outputs, every parameter gradient and
+    the BatchNorm buffers are bit for bit the same.  With one factor buffer per slot instead of per executor, B's forward pass
+    rewrote the factors that A's backward pass reads through ``drop_scale``, and the interleaved gradients differed."""
+    import train_edge_cases as cases
+    (hb, wb), (ha, wa) = sorted(cases.EXECUTOR_FRAMES, key=lambda s: s[0] * s[1])[:2]
+    assert (ha, wa) != (hb, wb) and ha * wa > 1
+
+    def run(interleaved):
+        net = _net('v3', False, ha, wa).to(cuda)
+        for m in net.modules():
+            if isinstance(m, torch.nn.Dropout2d):
+                m.p = 0.2
+        net.train()
+        tn = HipTrainNet(net, inplace_grads=True, overlap=False)
+        case = []
+        for h, w in ((ha, wa), (hb, wb)):
+            x, t = _whole_net_inputs(h, w)
+            case.append(({k: v.to(cuda) for k, v in x.items()}, t.to(cuda)))
+        torch.manual_seed(21)  # the Dropout2d draws
+        loss = lambda est, t: ((est - t) ** 2).mean()
+        if interleaved:
+            ea, eb = tn(case[0][0]), tn(case[1][0])
+            loss(ea, case[0][1]).backward()
+            loss(eb, case[1][1]).backward()
+        else:
+            ea = tn(case[0][0])
+            loss(ea, case[0][1]).backward()
+            eb = tn(case[1][0])
+            loss(eb, case[1][1]).backward()
+        torch.cuda.synchronize()
+        keeps = [tr.keep for tr in tn._trainers.values()]
+        assert len(keeps) == 2 and all(k is not None for k in keeps)
+        for i in (1, 2, 3, 4):  # keep probabilities, draw, factors, mask: one storage each per executor
+            assert keeps[0][i].untyped_storage().data_ptr() != keeps[1][i].untyped_storage().data_ptr()
+        assert not torch.equal(keeps[0][3], keeps[1][3])  # (two draws: otherwise the orders could not differ)
+        grads = [p.grad.detach().clone() for p in net.parameters() if p.grad is not None]
+        assert len(grads) > 50 and sum(int((g != 0).any()) for g in grads) > 50
+        return [ea.detach().clone(), eb.detach().clone()], grads, [b.detach().clone() for b in net.buffers()]
+
+    bits = lambda t: t.view(torch.int32) if t.dtype == torch.float32 else t
+    a, b = run(False), run(True)
+    for x in a[0] + a[1]:
+        assert torch.isfinite(x).all()
+    for part_a, part_b in zip(a, b):
+        assert len(part_a) == len(part_b)
+        for x, y in zip(part_a, part_b):
+            assert torch.equal(bits(x), bits(y))
+
+
 def test_weights_edited_through_data_need_invalidate(cuda):
     """``p.data.mul_()`` bumps no version counter; ``HipTrainNet.invalidate()`` is the documented hook, and an
     ordinary in-place update (optimizer step) is seen without it."""

@@ -74,6 +74,24 @@ def test_confusion_counts_and_semantic_metrics(cuda, shape, n_classes, offset):
     assert got_m == want_m and got_iou.keys() == want_iou.keys() and all(got_iou[k] == want_iou[k] for k in want_iou)
 
 
+@pytest.mark.parametrize('offset', [0, 3])
+def test_confusion_reproduces_the_reference_fixture(cuda, offset):
+    """tests/golden/semantic_evaluation_12.npz: the reference's own utils/metrics.py on a 12^3 case with classes on one
+    side only, a class hidden by the mask and classes that occur nowhere.  The metrics from ojf_volume_confusion's counts
+    are the reference's two returned values, exactly; the counts are volume_ref.confusion's."""
+    from helpers import golden
+    from online_joint_depthfusion_and_semantic_amd import metrics
+    g = golden('semantic_evaluation_12.npz')
+    C = int(g['n_class'])
+    est, gt, w = g['est'].ravel(), g['target'].ravel(), g['mask'].ravel().astype(H16)
+    hist, pe, pg = raw_confusion(cuda, est, gt, w, C, offset)
+    want, want_pe, want_pg, dropped = volume_ref.confusion(est, gt, w, C)
+    assert dropped == 0 and np.array_equal(hist, want) and np.array_equal(pe, want_pe) and np.array_equal(pg, want_pg)
+    m, iou = metrics.semantic_metrics_from_counts(hist, pe[:C], pg[:C])
+    assert m == {'Mean Acc': float(g['mean_acc']), 'Mean IoU': float(g['mean_iou'])}
+    assert {int(k): float(v) for k, v in iou.items()} == dict(zip(g['cls_ids'].tolist(), g['cls_iou'].tolist()))
+
+
 def test_database_evaluate_semantics_on_device(cuda):
     """Database.evaluate_semantics (modules/database.py:311-349) with device-resident volumes == the host path."""
     from online_joint_depthfusion_and_semantic_amd.config import default_config, database_config
