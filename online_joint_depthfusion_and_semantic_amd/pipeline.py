@@ -12,32 +12,23 @@ in between:
 
 The reference's intermediate tensors (int64 indices [N,9,8,3], fp64 weights, NCHW permutes,
 fancy-index slices of valid pixels: pipeline.py:74-171) never exist here.
+
+The class keeps the frame steps.  Three plain objects, created with it, own the state around them: labels2d.LabelFrontEnd (a
+frame's 2-D labels: engine cache, graph captures, look-ahead prefetch), guard_records.GuardRecords (the frames a range-guard
+recovery may have to fuse again) and announce.TrainingAnnouncements (training frames announced ahead, their valid-ray counts).
 """
 import torch
 
 from . import ops
 from . import _lib
 from ._lib import MODE_FAST, MODE_PARITY
+from .announce import TrainingAnnouncements
 from .engine import FusionNetEngine
 from .extractor import Extractor
+from .guard_records import GuardRecords, guard_frames_to_fuse_again, guard_policy  # noqa: F401 (the rule stays importable from here)
 from .integrator import Integrator
+from .labels2d import LabelFrontEnd, side_stream
 from .model import FusionNet_v2, FusionNet_v3
-
-
-def guard_frames_to_fuse_again(ring, records, device_count):
-    """Which remembered frames a range-guard recovery fuses again (FUSION_MODEL.guard_policy 'f32').  ``ring``: the remembered
-    frames in the order they were fused; ``records``: per frame, whether ITS integrate call skipped (the call's own latched
-    decision, Pipeline._guard_note); ``device_count``: the number of skipped integrate calls the device counted since the last
-    report.  Returns the skipped frames, in ring order - they need not be the last ones: with a stream per scene a later slot may
-    have latched "not set" before an earlier slot's net raised the flag.  Raises OjfError when the records and the device
-    disagree (a frame was skipped that nobody remembers, or the other way round): nothing can be fused again reliably then."""
-    if len(records) != len(ring):
-        raise _lib.OjfError('range guard: %d frames are remembered but %d records of their integrate calls' % (len(ring), len(records)))
-    again = [frame for frame, skipped in zip(ring, records) if skipped]
-    if len(again) != int(device_count):
-        raise _lib.OjfError('range guard: the device counted %d skipped frames, the records of the %d remembered frames say %d'
-                            % (int(device_count), len(ring), len(again)))
-    return again
 
 
 class Pipeline(torch.nn.Module):
@@ -87,7 +78,7 @@ class Pipeline(torch.nn.Module):
         # a load_state_dict into the fusion net (any flavour, assign=True included) drops the cached tensor list of the
         # engine-staleness check at once
         def _drop_fingerprint(module, incompatible):
-            self.__dict__.pop('_fp_cache', None)  # (a post hook must return None)
+            self._fp_cache = None  # (a post hook must return None)
         self._fusion_network.register_load_state_dict_post_hook(_drop_fingerprint)
         mode = getattr(config.SETTINGS, 'integrate_mode', 'fast')
         self._integrate_mode = MODE_PARITY if mode == 'parity' else MODE_FAST
@@ -98,8 +89,24 @@ class Pipeline(torch.nn.Module):
         self.profile = False  # True / N: fuse() brackets its three stages with HIP events on every (N-th) frame
         self._frames_fused = 0
         self._marks = []
-        # fuse_training calls that found / did not find their batch announced (announce_training_frame)
-        self.announce_hits = self.announce_misses = 0
+        self.device = torch.device('cpu')  # the device of the last frame step (every one sets it)
+        self._fp_cache = None  # [id(net), its parameters and buffers, age in frames] of _weights_fingerprint
+        self._zero = None  # a device scalar 0.0 for the filtered frame of _frames
+        self._seg_marks = []  # (event in front of the 2-D pass, the frame's first stage event) per profiled frame
+        self._slot_streams = []  # fuse_many: the stream of slot i + 1
+        self._shape = None  # image shape of the last prepared frame (_prepare_frame)
+        self._hip_train = None  # train.HipTrainNet of the fusion net, made by the first fuse_training on a GPU
+        self.guard_events = 0  # range-guard recoveries so far (_guard_recover)
+        self.last_guard_skips = []  # per frame remembered at the last recovery: (frame_id, did its integrate call skip)
+        # plain objects, not sub-modules: the state_dict and children() are the two networks'
+        # (no closure over self: a deep copy of the pipeline gets owners that read the copy's networks and config)
+        self._labels2d = LabelFrontEnd(config, self._modules)
+        self._guard = GuardRecords(config)
+        self._announcements = TrainingAnnouncements()
+
+    # fuse_training calls that found / did not find their batch announced (announce_training_frame)
+    announce_hits = property(lambda self: self._announcements.hits)
+    announce_misses = property(lambda self: self._announcements.misses)
 
     # ---- live stage timing (HIP events on the launch stream; bench.py) ---------------------------
     def _mark(self, first=False):
@@ -139,7 +146,7 @@ class Pipeline(torch.nn.Module):
             for j in range(3):
                 acc[j] += ev[4 * f + j].elapsed_time(ev[4 * f + j + 1])
         out = {'extract': acc[0] / n, 'net': acc[1] / n, 'integrate': acc[2] / n}
-        seg = self.__dict__.get('_seg_marks') or []
+        seg = self._seg_marks
         if seg:  # AdapNet++ prediction of the frame's labels (+ the host work between it and the extract launch)
             out['segmentation'] = sum(a.elapsed_time(b) for a, b in seg) / len(seg)
         return out
@@ -152,7 +159,7 @@ class Pipeline(torch.nn.Module):
                 self._guard_recover()  # (a tripped frame at the end of a scene: nothing after it polled the flag)
             torch.cuda.synchronize(self.device)  # (every slot's stream)
             self._engine.check()
-        elif torch.device(getattr(self, 'device', 'cpu')).type == 'cuda':
+        elif self.device.type == 'cuda':
             # no inference engine yet (training only, or only the 2-D engine ran): the executors share the one flag
             torch.cuda.synchronize(self.device)
             _lib.check(_lib.load().ojf_net_check(_lib.stream_ptr(self.device)), 'ojf_net_check')
@@ -162,10 +169,9 @@ class Pipeline(torch.nn.Module):
         """In-place weight updates (optimizer steps, load_state_dict) bump the tensors' version counters.  Walking
         the module tree costs ~0.3 ms, so the tensor list is cached and re-collected every 64 frames."""
         net = self._fusion_network
-        cache = self.__dict__.get('_fp_cache')
+        cache = self._fp_cache
         if cache is None or cache[0] != id(net) or cache[2] >= 64:
-            cache = [id(net), list(net.parameters()) + list(net.buffers()), 0]
-            self.__dict__['_fp_cache'] = cache
+            cache = self._fp_cache = [id(net), list(net.parameters()) + list(net.buffers()), 0]
         cache[2] += 1
         # version counters see in-place updates (optimizer steps, load_state_dict); storage addresses see
         # ``p.data = ...``; replaced Parameter objects (load_state_dict(assign=True), swapped sub-modules) are seen by
@@ -207,125 +213,6 @@ class Pipeline(torch.nn.Module):
                                                            self._integrate_mode, device)
         return self._workspaces[key]
 
-    # ---- semantics front-end (pipeline.py:42-60, 181-193) --------------------------------------
-    def _segmentation(self, data):
-        inputs = {'image': (data['image'] / 255.0).to(self.device).float()}
-        in_ = self.config.DATA.input
-        if in_ != 'image':
-            inputs[in_] = data[in_].repeat(1, 3, 1, 1).to(self.device).float()
-        net = self._seg_engine(inputs['image'].shape) or self._semantic_2d_network
-        if self.config.SEMANTIC_2D_MODEL.stage == 1:
-            output = net(inputs[in_])
-        else:
-            output = net(inputs['image'], inputs[in_])
-        logits = output if torch.is_tensor(output) else output[0]  # the engine returns the main head only
-        return torch.softmax(logits, dim=1).permute(0, 2, 3, 1)
-
-    def _segment_max(self, data):
-        """``_segmentation(data).max(dim=-1)`` -> (scores, ids).  With the HIP engine the whole chain - image / 255,
-        depth x 3, AdapNet++, softmax, max - is libojf launches (SegEngine.predict); ids come back as uint8."""
-        image = data['image']
-        engine = self._seg_engine(image.shape)
-        if engine is None:
-            return self._segmentation(data).max(dim=-1)
-        in_ = self.config.DATA.input
-        depth = data[in_].to(self.device).float() if in_ != 'image' else None
-        h, w = image.shape[-2:]
-        scores, ids = engine.predict(image.to(self.device).float(), depth)
-        return scores.view(1, h, w), ids.view(1, h, w)
-
-    def _seg_engine(self, shape):
-        """The AdapNet++ convolutions on the SEGCONV HIP kernels (adapnet_engine.SegEngine) when the front-end runs
-        inference on the GPU: ``SEMANTIC_2D_MODEL.engine: hip`` (default) | ``torch`` (module forward, MIOpen).
-        Rebuilt when the parameters change (version counters, checked like the fusion net's)."""
-        net = self._semantic_2d_network
-        if (self.config.SEMANTIC_2D_MODEL.get('engine', 'hip') != 'hip' or net.training or torch.is_grad_enabled()
-                or torch.device(self.device).type != 'cuda' or shape[0] != 1):
-            return None
-        if shape[-2] % 16 or shape[-1] % 16:
-            if not self.__dict__.get('_warned_seg_fallback'):
-                import warnings
-                self.__dict__['_warned_seg_fallback'] = True
-                warnings.warn('SEMANTIC_2D_MODEL.engine = hip needs frame sides that are multiples of 16 (the 1/16-resolution '
-                              'stage of AdapNet++): %dx%d frames run on the torch module forward instead' % (shape[-2], shape[-1]),
-                              RuntimeWarning)
-            return None
-        cache = self.__dict__.get('_seg_cache')
-        if cache is None or cache['net'] != id(net) or cache['age'] >= 64:
-            tensors = list(net.parameters()) + list(net.buffers())
-            cache = {'net': id(net), 'tensors': tensors, 'age': 0, 'key': None, 'engine': None} if cache is None or cache['net'] != id(net) \
-                else dict(cache, tensors=tensors, age=0)
-            self.__dict__['_seg_cache'] = cache
-        cache['age'] += 1
-        key = (len(cache['tensors']), sum(t._version for t in cache['tensors']), str(self.device))
-        if cache['engine'] is None or cache['key'] != key:
-            from .adapnet_engine import SegEngine
-            cache['engine'], cache['key'] = SegEngine(net), key
-        return cache['engine']
-
-    def _segmentation_graph(self, data):
-        """Inference-time replay of ``_segmentation(...).max(-1)``: captured once per frame shape (and engine) into a
-        device graph.  320x240: torch module 772 launches, 9.1 ms eager / 4.5 ms replayed; SEGCONV engine 215 launches,
-        2.6 ms eager / 2.3 ms replayed.  Parameters are read in place, so ``load_state_dict`` /
-        optimizer steps are seen; ``SEMANTIC_2D_MODEL.graph: False`` or a failed capture falls back to eager."""
-        image = data['image']
-        in_ = self.config.DATA.input
-        depth = data[in_] if in_ != 'image' else None
-        with torch.no_grad():
-            engine = self._seg_engine(image.shape)  # a rebuilt engine owns new weight buffers: recapture
-        key = (tuple(image.shape), str(self.device), id(self._semantic_2d_network), id(engine))
-        st = self.__dict__.get('_seg_graph')
-        if st is None or st['key'] != key:
-            st = {'key': key, 'graph': None}
-            self.__dict__['_seg_graph'] = st
-            try:
-                st['image'] = torch.zeros(image.shape, dtype=image.dtype, device=self.device)
-                st['depth'] = torch.zeros(depth.shape, dtype=depth.dtype, device=self.device) if depth is not None else None
-                batch = {'image': st['image']}
-                if depth is not None:
-                    batch[in_] = st['depth']
-                side = torch.cuda.Stream(device=self.device)
-                side.wait_stream(torch.cuda.current_stream(self.device))
-                with torch.cuda.stream(side):  # library workspaces and autotuning must be settled before the capture
-                    for _ in range(3):
-                        self._segment_max(batch)
-                torch.cuda.current_stream(self.device).wait_stream(side)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    st['scores'], st['ids'] = self._segment_max(batch)
-                st['graph'] = graph
-            except Exception:  # capture is an optimisation only
-                st['graph'] = None
-        if st['graph'] is None:
-            return self._segment_max(data)
-        st['image'].copy_(image, non_blocking=True)
-        if depth is not None:
-            st['depth'].copy_(depth.reshape(st['depth'].shape), non_blocking=True)
-        st['graph'].replay()
-        return st['scores'], st['ids']
-
-    def _frame_semantics(self, batch):
-        if not self.config.DATA.semantics:
-            return None, None
-        strategy = self.config.DATA.semantic_strategy
-        if strategy == 'predict':
-            with torch.no_grad():
-                use_graph = (self.config.SEMANTIC_2D_MODEL.get('graph', True) and not self._semantic_2d_network.training
-                             and torch.device(self.device).type == 'cuda')
-                if use_graph:
-                    scores, sem_ids = self._segmentation_graph(batch)
-                else:
-                    scores, sem_ids = self._segment_max(batch)
-        elif strategy == 'gt':
-            sem_ids = batch['semantic_gt']
-            scores = torch.ones_like(sem_ids, dtype=torch.float32)
-        else:
-            raise ValueError('Valid values for DATA.semantic_strategy are "gt" or "predict".')
-        h, w = sem_ids.shape[-2:]
-        sem_ids = sem_ids.to(self.device).to(torch.uint8).reshape(h * w).contiguous()
-        scores = scores.to(self.device).float().reshape(h * w).contiguous()
-        return sem_ids, scores
-
     def fuse_sequence(self, batches, database, device, prefetch=None):
         """``for b in batches: fuse(b, database, device)`` for CONSECUTIVE frames (of one scene, or any mix of scenes in stream
         order).  The frame steps stay strictly in order - frame t+1 is extracted from the volume frame t was integrated into -
@@ -343,13 +230,15 @@ class Pipeline(torch.nn.Module):
         if self._tvl1 and prefetch:
             raise ValueError('Pipeline.fuse_sequence: FUSION_MODEL.name "tvl1" does not support the look-ahead (prefetch)')
         self.device = torch.device(device)
-        sems = self._take_prefetched(batches)
+        labels = self._labels2d
+        sems = labels.take_prefetched(batches, self.device)
         if sems is None:
-            sems = self._frame_semantics_many(batches)
-        if prefetch and self._batched_2d_pass_applies(prefetch):
-            if sems and sems[0][0] is not None and not self.__dict__.get('_prefetch', {}).get('taken'):
+            sems = labels.frame_semantics_many(batches, self.device)
+        if prefetch and labels.batched_pass_applies(prefetch):
+            if sems and sems[0][0] is not None and not (labels.prefetch or {}).get('taken'):
                 sems = [(i.clone(), sc.clone()) for i, sc in sems]  # (this chunk's labels sit in the graph's output buffers, which the prefetched pass overwrites)
-            self._prefetch_semantics(prefetch)
+            eng, est = self._engine, self._est
+            labels.prefetch_semantics(prefetch, self.device, eng, (lambda: eng.forward(est)) if eng is not None else None)
         if self._classical:
             return self._fuse_classical(batches, sems, database)
         fp = self._weights_fingerprint()
@@ -374,180 +263,8 @@ class Pipeline(torch.nn.Module):
                 raise
             self._guard_recover(err)
             return self._fuse_frame(batch, database, 0, sem)  # (fp32 engine: a new fingerprint)
-        self._guard_remember(batch, database)
+        self._guard.remember(batch, database)
         return sem_ids
-
-    def _batched_2d_pass_applies(self, batches):
-        cfg = self.config
-        return bool(cfg.DATA.semantics and cfg.DATA.semantic_strategy == 'predict' and len(batches) > 1
-                    and not self._semantic_2d_network.training and cfg.SEMANTIC_2D_MODEL.get('stage', 2) != 1)
-
-    def _side_stream(self, others):
-        """A torch stream whose kernels really run beside those of ``others``: the runtime backs all streams by a small
-        round-robin pool of hardware queues, and two streams on one queue take turns (measured: the look-ahead pass beside
-        the frame steps 933 frames/s on two queues, 775 on one).  Up to eight candidates are tried (ojf_streams_overlap, a
-        set-up cost of ~0.5 ms each); the rejected ones stay referenced until the choice is made, so that the next candidate
-        is another pool member."""
-        lib = _lib.load()
-        rejected, best = [], None
-        for _ in range(8):
-            cand = torch.cuda.Stream(device=self.device)
-            if all(lib.ojf_streams_overlap(o if isinstance(o, int) else o.cuda_stream, cand.cuda_stream) == 1 for o in others):
-                return cand
-            best = best or cand
-            rejected.append(cand)
-        return best
-
-    def _measured_side_stream(self, cur, frames):
-        """The look-ahead stream by measurement: which hardware queue a new stream gets, and whose packets it then waits
-        behind, is the runtime's business (a stream that passes ojf_streams_overlap against every stream we know of still ran
-        the pass 20 % slower than its neighbour in the pool: 780 against 940 frames/s at four frames per chunk).  Six candidate
-        streams each replay the batched 2-D pass beside ``frames`` forward passes of the fusion net on the caller's stream
-        (the executor recomputes its last frame's estimate: no volume is touched); the fastest is kept.  ~30 ms, once."""
-        st = self.__dict__.get('_seg_graph_many')
-        eng, est = getattr(self, '_engine', None), getattr(self, '_est', None)
-        if not st or st.get('graph') is None or eng is None or est is None:
-            return None
-        best, best_ms, cands = None, None, []
-        with torch.no_grad():
-            for _ in range(6):
-                cand = torch.cuda.Stream(device=self.device)
-                cands.append(cand)  # (kept alive: the next candidate is another member of the pool)
-                ms = []
-                for _rep in range(3):
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(cur)
-                    cand.wait_stream(cur)
-                    with torch.cuda.stream(cand):
-                        st['graph'].replay()
-                    for _f in range(frames):
-                        eng.forward(est)
-                    cur.wait_stream(cand)
-                    e1.record(cur)
-                    e1.synchronize()
-                    ms.append(e0.elapsed_time(e1))
-                t = min(ms[1:])
-                if best is None or t < best_ms:
-                    best, best_ms = cand, t
-        return best
-
-    def _net_side_streams(self):
-        """Raw handles of the fusion net's own side streams (the second head of the two-head net runs on one): the look-ahead
-        pass must not share a hardware queue with them either (measured: 775 frames/s when it does, 930-1070 when not)."""
-        eng = getattr(self, '_engine', None)
-        try:
-            return eng.side_streams() if eng is not None and hasattr(eng, 'side_streams') else []
-        except Exception:
-            return []
-
-    def _prefetch_semantics(self, batches):
-        """The batched 2-D pass of ``batches`` on the side stream; the labels land in one of two persistent result slots
-        (the graph's own output buffers belong to the next replay).  Slot k % 2 was last read by the frame steps of the
-        chunk two calls ago: they are in front of the side stream's wait on the caller's stream."""
-        if not self._batched_2d_pass_applies(batches):
-            return
-        cur = torch.cuda.current_stream(self.device)
-        pf = self.__dict__.get('_prefetch')
-        # 'measured' (_measured_side_stream, round 5) | 'priority' (below) | 'probe': the first stream that passes ojf_streams_overlap
-        how = self.config.SETTINGS.get('lookahead_stream', 'measured')
-        if pf is None:
-            net_streams = self._net_side_streams()
-            if how == 'priority':
-                # a stream of ANOTHER priority class: the runtime keeps one pool of hardware queues per priority, so this stream never
-                # shares a queue with the caller's (normal-priority) stream or the net's side streams - by construction, not by probing
-                side = torch.cuda.Stream(device=self.device, priority=-1)
-            else:
-                side = self._side_stream([cur] + net_streams)
-            pf = self.__dict__['_prefetch'] = {'stream': side, 'n': 0, 'slots': [None, None], 'ready': None, 'taken': False, 'measured': how != 'measured',
-                                                'net_seen': bool(net_streams) or getattr(self, '_engine', None) is not None}
-        elif not pf.get('measured') and getattr(self, '_engine', None) is not None and self.__dict__.get('_seg_graph_many', {}).get('graph') is not None:
-            # (once, when both networks' launch sequences exist: the stream is chosen by what it does to the real work)
-            old = pf['stream']
-            pf['stream'] = self._measured_side_stream(cur, len(batches)) or old
-            pf['stream'].wait_stream(old)
-            pf['measured'] = True
-        side = pf['stream']
-        side.wait_stream(cur)
-        with torch.cuda.stream(side), torch.no_grad():
-            sems = self._frame_semantics_many(batches)
-            if sems[0][0] is None:
-                return
-            k = pf['n'] % 2
-            slot = pf['slots'][k]
-            if slot is None or len(slot) != len(sems) or slot[0][0].shape != sems[0][0].shape:
-                side.synchronize(); cur.synchronize()  # (first use / another chunk shape: allocate the slot once, outside any overlap)
-                slot = pf['slots'][k] = [(torch.empty_like(i), torch.empty_like(sc)) for i, sc in sems]
-            for (di, dsc), (i, sc) in zip(slot, sems):
-                di.copy_(i, non_blocking=True)
-                dsc.copy_(sc, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(side)
-        pf['n'] += 1
-        # the announced batch OBJECTS are held (and compared with `is`): an id() of a dict the caller has dropped can be handed to a
-        # new dict, and the stale labels of other frames would be fused silently
-        pf['ready'] = {'batches': list(batches), 'sems': slot, 'event': ev}
-
-    def _take_prefetched(self, batches):
-        pf = self.__dict__.get('_prefetch')
-        if pf:
-            pf['taken'] = False
-        if not pf or not pf['ready']:
-            return None
-        ready, pf['ready'] = pf['ready'], None
-        cur = torch.cuda.current_stream(self.device)
-        cur.wait_event(ready['event'])  # (also orders this call's own 2-D pass, if the chunk is another one, behind the side stream's use of the graph buffers)
-        pf['taken'] = len(ready['batches']) == len(batches) and all(a is b for a, b in zip(ready['batches'], batches))
-        pf['hits'] = pf.get('hits', 0) + int(pf['taken'])
-        return ready['sems'] if pf['taken'] else None
-
-    def _frame_semantics_many(self, batches):
-        """``[_frame_semantics(b) for b in batches]``; with ``semantic_strategy: predict`` on the HIP engine the S frames go
-        through the 2-D network as ONE batched pass (SegEngine.predict_many: every layer's weights fetched once for all
-        frames), replayed from a device graph per (S, frame shape)."""
-        cfg = self.config
-        if (not cfg.DATA.semantics or cfg.DATA.semantic_strategy != 'predict' or len(batches) == 1
-                or self._semantic_2d_network.training or cfg.SEMANTIC_2D_MODEL.get('stage', 2) == 1):
-            return [self._frame_semantics(b) for b in batches]
-        with torch.no_grad():
-            engine = self._seg_engine(batches[0]['image'].shape)
-            if engine is None:
-                return [self._frame_semantics(b) for b in batches]
-            in_ = cfg.DATA.input
-            images = [b['image'].to(self.device).float() for b in batches]
-            depths = [b[in_].to(self.device).float() for b in batches] if in_ != 'image' else None
-            S = len(batches)
-            h, w = images[0].shape[-2:]
-            key = (S, tuple(images[0].shape), None if depths is None else tuple(depths[0].shape), str(self.device), id(engine))
-            st = self.__dict__.get('_seg_graph_many')
-            if st is None or st['key'] != key:
-                st = self.__dict__['_seg_graph_many'] = {'key': key, 'graph': None}
-                if cfg.SEMANTIC_2D_MODEL.get('graph', True):
-                    try:
-                        st['images'] = [torch.zeros_like(im) for im in images]
-                        st['depths'] = [torch.zeros_like(d) for d in depths] if depths is not None else None
-                        side = torch.cuda.Stream(device=self.device)
-                        side.wait_stream(torch.cuda.current_stream(self.device))
-                        with torch.cuda.stream(side):
-                            for _ in range(2):
-                                engine.predict_many(st['images'], st['depths'])
-                        torch.cuda.current_stream(self.device).wait_stream(side)
-                        graph = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(graph):
-                            st['scores'], st['ids'] = engine.predict_many(st['images'], st['depths'])
-                        st['graph'] = graph
-                    except Exception:  # capture is an optimisation only
-                        st['graph'] = None
-            if st['graph'] is None:
-                scores, ids = engine.predict_many(images, depths)
-            else:
-                for dst, src in zip(st['images'], images):
-                    dst.copy_(src, non_blocking=True)
-                if depths is not None:
-                    for dst, src in zip(st['depths'], depths):
-                        dst.copy_(src.reshape(dst.shape), non_blocking=True)
-                st['graph'].replay()
-                scores, ids = st['scores'], st['ids']
-            return [(ids[i].contiguous(), scores[i].contiguous()) for i in range(S)]
 
     def _frames(self, batch, filtered=True):
         """(frame, filtered frame) of pipeline.py:194-199; with ``filtered=False`` the second item is the bool mask
@@ -562,9 +279,9 @@ class Pipeline(torch.nn.Module):
             if mask.dtype != torch.bool:
                 mask = mask != 0
             return frame[0], mask[0].contiguous()
-        zero = self.__dict__.get('_zero')
+        zero = self._zero
         if zero is None or zero.device != frame.device:
-            zero = self.__dict__['_zero'] = torch.zeros((), dtype=torch.float32, device=frame.device)
+            zero = self._zero = torch.zeros((), dtype=torch.float32, device=frame.device)
         filtered = torch.where(mask, frame, zero)  # pipeline.py:196; one launch (a python scalar costs a fill kernel)
         return frame[0], filtered[0]
 
@@ -604,37 +321,8 @@ class Pipeline(torch.nn.Module):
     #                      so) and fuses the skipped frames again, in order: the stream comes out as if the net had run in
     #                      fp32 from the event on.  The batches of the last <= 48 frames stay alive for that (an event
     #                      every 16 frames bounds how far the host may run ahead of the device).
-    _GUARD_EVERY, _GUARD_KEEP = 16, 48
-
     def _guard_policy(self):
-        if self.config.FUSION_MODEL.get('arithmetic', 'f16x3') != 'f16x3':
-            return 'raise'
-        return self.config.FUSION_MODEL.get('guard_policy', 'raise')
-
-    def _guard_note(self, slot, workspace):
-        """guard_policy 'f32': keeps, per slot, a copy of the decision the integrate call just enqueued on this stream will have
-        taken (ops.IntegrateWorkspace.guard_latch: the slot's workspace is reused by the slot's next call).  The healthy path's
-        whole cost: 4 bytes, device to device, per frame; nothing is read before a recovery."""
-        if self._guard_policy() == 'f32':
-            self.__dict__.setdefault('_guard_latches', {})[slot] = workspace.guard_latch()
-
-    def _guard_remember(self, batch, database, slot=0):
-        if self._guard_policy() != 'f32':  # (a frame fused behind a recovery, on the fp32 engine: there is nothing to recover to)
-            return
-        ring = self.__dict__.setdefault('_guard_ring', [])
-        marks = self.__dict__.setdefault('_guard_marks', [])
-        ring.append((batch, database, self.__dict__.get('_guard_latches', {}).pop(slot, None)))
-        if len(ring) % self._GUARD_EVERY == 0:
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(self.device))
-            marks.append([len(ring), ev])
-        if len(ring) > self._GUARD_KEEP:
-            upto, ev = marks.pop(0)
-            ev.synchronize()  # (long done unless the host is > 32 frames ahead of the device)
-            if not _lib.load().ojf_guard_poll():  # the frames in front of that event were fused with the guard silent
-                del ring[:upto]
-                for m in marks:
-                    m[0] -= upto
+        return guard_policy(self.config)
 
     def _guard_recover(self, err=None):
         """guard_policy 'f32': if the guard fired - report + clear the event, switch the arithmetic, fuse the skipped frames
@@ -649,19 +337,11 @@ class Pipeline(torch.nn.Module):
                 raise err
             return False
         lib.ojf_net_check(_lib.stream_ptr(self.device))  # (reports what `flag` said and clears it)
-        ring = self.__dict__.get('_guard_ring', [])
         n = skipped.value
-        # (every stream that fused a remembered frame has been joined to this one, which ojf_guard_status has drained: one read)
-        latches = [r[2] for r in ring]
-        if any(l is None for l in latches):
-            raise _lib.OjfError('range guard: a remembered frame has no record of its integrate call')
-        records = torch.stack(latches).cpu().ne(0).any(dim=1).tolist() if latches else []
-        redo = guard_frames_to_fuse_again([r[:2] for r in ring], records, n)
         # per remembered frame, in order: (frame_id, did its integrate call skip) - which frames the recovery below fuses again
-        self.last_guard_skips = [(r[0]['frame_id'][0], s) for r, s in zip(ring, records)]
-        self.__dict__['_guard_ring'], self.__dict__['_guard_marks'], self.__dict__['_guard_latches'] = [], [], {}
+        redo, self.last_guard_skips = self._guard.take(n)
         self.config.FUSION_MODEL.arithmetic = 'f32'
-        self.guard_events = self.__dict__.get('guard_events', 0) + 1
+        self.guard_events += 1
         warnings.warn('split-fp16 range guard fired: FUSION_MODEL.arithmetic switched to f32 for this network, '
                       '%d skipped frame(s) fused again' % n, RuntimeWarning)
         for b, db in redo:
@@ -736,7 +416,7 @@ class Pipeline(torch.nn.Module):
         self._refuse_tripped_guard('Pipeline.fuse')
         profiled = slot == 0 and semantics is None
         seg0 = self._mark_segmentation() if profiled else None
-        sem_ids, scores = self._frame_semantics(batch) if semantics is None else semantics
+        sem_ids, scores = self._labels2d.frame_semantics(batch, self.device) if semantics is None else semantics
         scene_id, volume, frame, mask, Ki, E, h, w = self._prepare_frame(batch, database)
         tsdf, weights = volume['current'], volume['weights']
 
@@ -746,7 +426,7 @@ class Pipeline(torch.nn.Module):
         mark = self._mark if profiled else (lambda first=False: None)
         mark(first=True)
         if seg0 is not None and self._marks:
-            self.__dict__.setdefault('_seg_marks', []).append((seg0, self._marks[-1]))
+            self._seg_marks.append((seg0, self._marks[-1]))
         use_sem = self.config.FUSION_MODEL.use_semantics
         if eng.fused_input:
             # geometry-only net: the extractor writes the net's input planes itself (one launch less, no sample planes)
@@ -769,7 +449,7 @@ class Pipeline(torch.nn.Module):
                       sem_ids=sem_ids if sem else None, sem_scores=scores if sem else None,
                       id_vol=volume['ids_est'] if sem else None, score_vol=volume['scores'] if sem else None,
                       mode=self._integrate_mode, mask=mask)  # filtered frame of pipeline.py:196 formed in the kernels
-        self._guard_note(slot, ws)
+        self._guard.note(slot, ws)
         mark()
         self._commit_frame(database, scene_id, volume)
         return sem_ids
@@ -841,7 +521,7 @@ class Pipeline(torch.nn.Module):
             del run[:]
 
         for b, s in zip(batches, sems):
-            sem_ids, scores = self._frame_semantics(b) if s is None else s
+            sem_ids, scores = self._labels2d.frame_semantics(b, self.device) if s is None else s
             scene_id, _, frame, mask = self._prepare_frame(b, None)[:4]
             key = (scene_id, tuple(frame.shape))
             if key != run_key or len(run) == _lib.PROJECTIVE_MAX_VIEWS:
@@ -901,11 +581,11 @@ class Pipeline(torch.nn.Module):
                 self._fuse_many_frames(batches[i:i + _lib.MAX_SCENES], database, device)
             return
         main = torch.cuda.current_stream(self.device)
-        sems = self._frame_semantics_many(batches)  # (None, None) without semantics; predict: ONE batched pass, this stream
+        sems = self._labels2d.frame_semantics_many(batches, self.device)  # (None, None) without semantics; predict: ONE batched pass, this stream
         fp = self._weights_fingerprint()
-        streams = self.__dict__.setdefault('_slot_streams', [])
+        streams = self._slot_streams
         while len(streams) < len(batches) - 1:
-            streams.append(self._side_stream([main] + streams))  # (a stream that runs beside the caller's and the other slots')
+            streams.append(side_stream(self.device, [main] + streams))  # (a stream that runs beside the caller's and the other slots')
         enqueued = 0
         try:
             # 'auto' (default): the joint launches for two scenes, per-slot launches from three on - measured on one box (round 6,
@@ -935,7 +615,7 @@ class Pipeline(torch.nn.Module):
             # guard_policy 'f32': the frames of this call that were enqueued behind the event are among the skipped ones
             # (remember them first); the one the poll refused and those after it follow, one at a time on the fp32 engine
             for i, b in enumerate(batches[:enqueued]):
-                self._guard_remember(b, database, i)
+                self._guard.remember(b, database, i)
             self._guard_recover(err)
             for b, sem in zip(batches[enqueued:], sems[enqueued:]):
                 self._fuse_guarded(b, database, sem, None, True)
@@ -944,7 +624,7 @@ class Pipeline(torch.nn.Module):
             main.wait_stream(st)
         if recover:
             for i, b in enumerate(batches):
-                self._guard_remember(b, database, i)  # (scene i ran on slot i: its own record)
+                self._guard.remember(b, database, i)  # (scene i ran on slot i: its own record)
 
     def _fuse_many_joint(self, batches, database, sems, fp, main, streams):
         """fuse_many's frame steps with the gather and the scatter of ALL scenes as single launches (round 6):
@@ -990,7 +670,7 @@ class Pipeline(torch.nn.Module):
         self._mark()
         ops.integrate_many([p['scatter'] for p in prep], n_points=P, n_tail=n_tail, trunc=self.config.DATA.init_value)
         for i, p in enumerate(prep):  # (every scene of the launch latches for itself)
-            self._guard_note(i, p['scatter']['workspace'])
+            self._guard.note(i, p['scatter']['workspace'])
         self._mark()
         self._frames_fused += len(prep) - 1  # (the first mark counted one)
         for p in prep:
@@ -999,11 +679,11 @@ class Pipeline(torch.nn.Module):
     def _training_forward(self, inputs):
         """The net forward of pipeline.py:322 with a graph for ``loss.backward()``: on the libojf training kernels
         (train.HipTrainNet: ``FUSION_MODEL.train_engine: hip``, default on a GPU) or on torch autograd (``torch``)."""
-        if self.config.FUSION_MODEL.get('train_engine', 'hip') == 'hip' and torch.device(self.device).type == 'cuda':
-            tn = self.__dict__.get('_hip_train')
+        if self.config.FUSION_MODEL.get('train_engine', 'hip') == 'hip' and self.device.type == 'cuda':
+            tn = self._hip_train
             if tn is None or tn.net is not self._fusion_network:
                 from .train import HipTrainNet
-                tn = self.__dict__['_hip_train'] = HipTrainNet(self._fusion_network, graph=self.config.FUSION_MODEL.get('train_graph', False),
+                tn = self._hip_train = HipTrainNet(self._fusion_network, graph=self.config.FUSION_MODEL.get('train_graph', False),
                                                                inplace_grads=True, arithmetic=self.config.FUSION_MODEL.get('train_arithmetic', 'f16x3'),
                                                                backward_arithmetic=self.config.FUSION_MODEL.get('train_arithmetic_bwd', None),
                                                                replay=self.config.FUSION_MODEL.get('train_replay', None),
@@ -1017,7 +697,7 @@ class Pipeline(torch.nn.Module):
         fusion net's gradients or writes its parameters (train_fusion.py:182-189: clip_grad_norm_, optimizer.step(), zero_grad()).  With
         ``FUSION_MODEL.train_overlap`` the backward pass of a frame runs on a stream of its own beside the next frame's forward stage and
         this context puts its body on that stream; without it (the default) the context does nothing."""
-        tn = self.__dict__.get('_hip_train')
+        tn = self._hip_train
         if tn is not None:
             return tn.gradients()
         import contextlib
@@ -1027,7 +707,7 @@ class Pipeline(torch.nn.Module):
         """``fn()`` behind the backward passes enqueued so far - the function form of ``with pipeline.gradients(): ...`` that a host thread
         of the pipeline's own can run (``FUSION_MODEL.train_overlap_thread``, default off: measured neutral): the caller does not wait
         for the backward pass's launch loop.  ``join=False`` only for an ``fn`` that writes no parameter (train.HipTrainNet.gradient_work)."""
-        tn = self.__dict__.get('_hip_train')
+        tn = self._hip_train
         if tn is not None:
             return tn.gradient_work(fn, join=join)
         fn()
@@ -1035,47 +715,16 @@ class Pipeline(torch.nn.Module):
     def join_gradients(self):
         """The current stream waits for the gradient stream (before checkpoints, validation, host reads of gradients or freshly stepped
         weights); a no-op without ``FUSION_MODEL.train_overlap``.  The next ``fuse_training`` joins by itself when a weight changed."""
-        tn = self.__dict__.get('_hip_train')
+        tn = self._hip_train
         if tn is not None:
             tn.join_gradients()
-
-    def _async_count(self, mask_flat):
-        """Number of set elements of a device bool vector, on its way to the host: (pinned int32 buffer, event)."""
-        if not mask_flat.is_cuda:
-            return int(mask_flat.sum())
-        slots = self.__dict__.setdefault('_count_slots', [])
-        at = self.__dict__.get('_count_at', 0)
-        # A ring of four.  A frame step that was not announced reads its slot inside the same call.  An announcement's slot is read
-        # by the fuse_training call after next at the latest (_take_announced drops it then); with an announcement and a miss in
-        # every frame the requests in between are: the miss of the frame step in front of it, the next announcement, and - when
-        # it is dropped instead of read - the miss of its own frame step.  That is at most three newer requests while a value is
-        # still wanted, so the slot that the fourth reuses has been read or given up.
-        if len(slots) < 4:
-            slots.append((torch.empty(1, dtype=torch.int32).pin_memory(), torch.cuda.Event()))
-        buf, ev = slots[at % len(slots)]
-        self.__dict__['_count_at'] = at + 1
-        buf.copy_(mask_flat.sum(dtype=torch.int32).reshape(1), non_blocking=True)
-        ev.record(torch.cuda.current_stream(mask_flat.device))
-        return buf, ev
-
-    def _valid_index(self, mask_flat, count):
-        """``mask.nonzero()[:, 0]`` without draining the stream: the size comes from _async_count."""
-        if isinstance(count, int):
-            return mask_flat.nonzero()[:, 0]
-        buf, ev = count
-        ev.synchronize()
-        nv = int(buf[0])
-        try:
-            return torch.nonzero_static(mask_flat, size=nv)[:, 0]
-        except (RuntimeError, NotImplementedError):  # builds without the device kernel: the blocking form
-            return mask_flat.nonzero()[:, 0]
 
     # ---- training frame step (pipeline.py:251-363) -----------------------------------------------
     def announce_training_frame(self, batch, device=None):
         """Tells the pipeline which batch the ``fuse_training`` call AFTER the coming one will bring (the same object; call order
         announce(i + 1), fuse_training(i) - announcing the very next call's batch works too).  Up to two announcements are held,
         matched by object identity and consumed by the first ``fuse_training`` that brings the object; ``None`` clears them
-        (``_take_announced``).  The part of that frame
+        (announce.TrainingAnnouncements).  The part of that frame
         step that depends on the batch alone - the filtered frame of pipeline.py:196 and the number of valid rays, the one value
         the host must read to shape ``tsdf_fused`` / ``tsdf_target`` [1, Nv, 9] - is enqueued NOW, in front of the current
         frame's work, so that its answer is on the host long before the next call asks for it.  Without the announcement the count
@@ -1085,45 +734,18 @@ class Pipeline(torch.nn.Module):
         4.8-5.5 ms).  With it the host may run up to one frame ahead.  Optional and bit-neutral: the same launches, earlier.  The
         reference has no counterpart (its ``nonzero`` drains the queue in the middle of every frame, pipeline.py:125-131)."""
         if batch is None:
-            self.__dict__['_announced'] = []
-            return
-        self.device = torch.device(device if device is not None else getattr(self, 'device', 'cpu'))
-        frame, filtered = self._frames(batch)
-        valid_mask = filtered.reshape(frame.numel()) != 0
-        held = self.__dict__.setdefault('_announced', [])
-        # [batch, frame, filtered, valid_mask, count, fuse_training calls of OTHER batches it has seen]
-        held.append([batch, frame, filtered, valid_mask, self._async_count(valid_mask), 0])
-        del held[:-2]  # (the one waiting for the frame step in between, and this one)
-
-    def _take_announced(self, batch):
-        """The announcement of ``batch`` (the same object, on this call's device) or None, for ``fuse_training``.  The documented
-        order is announce(i + 1), fuse_training(i): an announcement outlives ONE frame step of another batch and is dropped by the
-        second, as is one made for another device.  ``announce_hits`` / ``announce_misses`` count the calls either way."""
-        hit, keep = None, []
-        # ('cuda' and 'cuda:<current>' are one device: a frame tensor's device always carries its index)
-        dev = torch.empty(0, device=self.device).device
-        for a in self.__dict__.get('_announced') or []:
-            if a[1].device != dev:
-                continue
-            if hit is None and a[0] is batch:
-                hit = a
-            elif a[5] == 0:
-                a[5] = 1
-                keep.append(a)
-        self.__dict__['_announced'] = keep
-        if hit is None:
-            self.announce_misses += 1
-        else:
-            self.announce_hits += 1
-        return hit
+            return self._announcements.announce(None)
+        if device is not None:
+            self.device = torch.device(device)
+        self._announcements.announce(batch, *self._frames(batch))
 
     def fuse_training(self, batch, database, device):
         if self._classical:
             raise RuntimeError('Pipeline.fuse_training: FUSION_MODEL.name "tsdf" is classical TSDF averaging - there is no '
                                'network to train (use "v2" or "v3")')
         self.device = torch.device(device)
-        sem_ids, scores = self._frame_semantics(batch)
-        ann = self._take_announced(batch)
+        sem_ids, scores = self._labels2d.frame_semantics(batch, self.device)
+        ann = self._announcements.take(batch, self.device)
         if ann is not None:
             frames, valid_mask, count = tuple(ann[1:3]), ann[3], ann[4]  # (enqueued a frame ago: the count is on the host by now)
         else:
@@ -1140,7 +762,7 @@ class Pipeline(torch.nn.Module):
         # the middle of every frame and the device idled while Python enqueued the loss: 2.7 of 10.4 ms per 320x240 frame.)
         if valid_mask is None:
             valid_mask = filtered.reshape(n) != 0
-            count = self._async_count(valid_mask)
+            count = self._announcements.async_count(valid_mask)
 
         # sample planes [P, n] are NCHW [1, P, h, w] as they stand: no permute / contiguous copies in front of the net
         cur = ops.extract(frame, Ki, E, volume['origin'], volume['resolution'], tsdf, weights, n_points=P, planes=True)
@@ -1158,7 +780,7 @@ class Pipeline(torch.nn.Module):
             if 'fp16 range' in str(err) and self.device.type == 'cuda':
                 _lib.load().ojf_net_check(_lib.stream_ptr(self.device))
             raise
-        valid = self._valid_index(valid_mask, count)
+        valid = self._announcements.valid_index(valid_mask, count)
 
         # pipeline.py:104-135 in the plane layout, one launch each way; the [1, n, P] tensor of the API is a transposed view
         init = self.config.DATA.init_value

@@ -104,36 +104,36 @@ def test_pipeline_uses_the_engine_and_follows_weight_updates(cuda):
     lively(pipe._semantic_2d_network, 3)
     batch = {'image': torch.randn(1, 3, h, w, device=cuda) * 50 + 120, cfg.DATA.input: torch.rand(1, 1, h, w, device=cuda) * 3}
     with torch.no_grad():
-        hip = pipe._segmentation(batch)
-        assert pipe._seg_cache['engine'] is not None
-        first = pipe._seg_cache['engine']
+        hip = pipe._labels2d.segmentation(batch, cuda)
+        assert pipe._labels2d.seg_cache['engine'] is not None
+        first = pipe._labels2d.seg_cache['engine']
         cfg.SEMANTIC_2D_MODEL.engine = 'torch'
-        ref = pipe._segmentation(batch)
+        ref = pipe._labels2d.segmentation(batch, cuda)
         assert (hip - ref).abs().max().item() < 2e-4 and (hip.argmax(-1) == ref.argmax(-1)).float().mean().item() > 0.999
         cfg.SEMANTIC_2D_MODEL.engine = 'hip'
         for p in pipe._semantic_2d_network.decoder.parameters():
             p.mul_(1.5)  # in-place update: version counters move, the engine is rebuilt
-        ref2 = pipe._segmentation(dict(batch))
+        ref2 = pipe._labels2d.segmentation(dict(batch), cuda)
         cfg.SEMANTIC_2D_MODEL.engine = 'torch'
-        want2 = pipe._segmentation(batch)
+        want2 = pipe._labels2d.segmentation(batch, cuda)
         cfg.SEMANTIC_2D_MODEL.engine = 'hip'
-        assert pipe._seg_cache['engine'] is not first
+        assert pipe._labels2d.seg_cache['engine'] is not first
         assert (ref2 - want2).abs().max().item() < 2e-4 and (ref2 - hip).abs().max().item() > 1e-3
         # graph replay of the engine == eager engine, before and after another update
         for _ in range(2):
-            s, i = pipe._segmentation_graph(batch)
-            assert pipe._seg_graph['graph'] is not None
-            es, ei = pipe._segment_max(batch)  # the eager chain of the same libojf launches (SegEngine.predict)
+            s, i = pipe._labels2d.segmentation_graph(batch, cuda)
+            assert pipe._labels2d.seg_graph['graph'] is not None
+            es, ei = pipe._labels2d.segment_max(batch, cuda)  # the eager chain of the same libojf launches (SegEngine.predict)
             assert torch.equal(s, es) and torch.equal(i, ei)  # same kernels, fixed summation order
             # torch's image / 255 (a multiplication by 1/255 on the GPU, a true division here and on the reference's CPU
             # path), softmax and max around the same engine: one input ulp through 50 layers of a lively net
-            ts, ti = pipe._segmentation(batch).max(dim=-1)
+            ts, ti = pipe._labels2d.segmentation(batch, cuda).max(dim=-1)
             assert torch.allclose(s, ts, rtol=0, atol=2e-3) and float((i.long() == ti).float().mean()) > 0.995
             for p in pipe._semantic_2d_network.decoder.parameters():
                 p.mul_(0.9)
     with pytest.raises(Exception):  # training mode never routes through the inference engine silently
         pipe._semantic_2d_network.train()
-        assert pipe._seg_engine((1, 3, h, w)) is None
+        assert pipe._labels2d.seg_engine((1, 3, h, w), cuda) is None
         raise RuntimeError('ok')
 
 

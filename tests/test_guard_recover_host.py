@@ -1,12 +1,12 @@
 """CPU: which remembered frames a range-guard recovery (FUSION_MODEL.guard_policy 'f32') fuses again -
-pipeline.guard_frames_to_fuse_again on hand-made rings.  The rule it replaces was "the last n of the ring"."""
+guard_records.guard_frames_to_fuse_again on hand-made rings.  The rule it replaces was "the last n of the ring"."""
 import os
 import re
 
 import pytest
 
 from online_joint_depthfusion_and_semantic_amd import _lib, ops
-from online_joint_depthfusion_and_semantic_amd.pipeline import guard_frames_to_fuse_again as select
+from online_joint_depthfusion_and_semantic_amd.guard_records import guard_frames_to_fuse_again as select
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 

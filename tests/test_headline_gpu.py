@@ -412,7 +412,7 @@ def test_fuse_predict_strategy_at_B_matches_reference_golden(cuda, engine):
     with torch.no_grad():
         for i in range(2):
             b = {k: (v.to(cuda) if torch.is_tensor(v) else v) for k, v in st.batch(i).items()}
-            ids, scores = pipe._frame_semantics(b)
+            ids, scores = pipe._labels2d.frame_semantics(b, cuda)
             scores, ids = scores.reshape(h, w).cpu().numpy(), ids.reshape(h, w).cpu().numpy()
             clear = g['f%d_seg_margin' % i].astype(np.float32) > 1e-4
             flips = int((ids != g['f%d_seg_ids' % i]).sum())
@@ -492,8 +492,8 @@ def test_batched_2d_pass_at_B_matches_reference_golden(cuda, B):
             filler += 1
     flips_total = 0
     with torch.no_grad():
-        sems = pipe._frame_semantics_many(chunk)
-        assert pipe.__dict__['_seg_graph_many']['graph'] is not None  # the batched pass, captured and replayed
+        sems = pipe._labels2d.frame_semantics_many(chunk, cuda)
+        assert pipe._labels2d.seg_graph_many['graph'] is not None  # the batched pass, captured and replayed
         for i, p in enumerate(pos):
             ids, scores = sems[p]
             scores, ids = scores.reshape(h, w).cpu().numpy(), ids.reshape(h, w).cpu().numpy()

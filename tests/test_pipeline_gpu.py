@@ -264,7 +264,7 @@ def test_fuse_with_predicted_semantics(cuda):
 
 
 def test_segmentation_graph_replay_equals_eager(cuda):
-    """The device-graph replay of the AdapNet++ front end (Pipeline._segmentation_graph) returns what the eager
+    """The device-graph replay of the AdapNet++ front end (labels2d.LabelFrontEnd.segmentation_graph) returns what the eager
     call returns (to rounding), frame after frame and after an in-place weight update."""
     h, w, grid = 64, 96, 32
     cfg = default_config(h, w, semantics=True, use_semantics=True, n_classes=12)
@@ -279,9 +279,9 @@ def test_segmentation_graph_replay_equals_eager(cuda):
         for i in range(3):
             b = _batch(st, i, cuda)
             b['image'] = torch.randn(1, 3, h, w, device=cuda) * 50 + 120
-            want_s, want_i = pipe._segmentation(b).max(dim=-1)
-            got_s, got_i = pipe._segmentation_graph(b)
-            assert pipe._seg_graph['graph'] is not None  # the capture worked: this is the replay path
+            want_s, want_i = pipe._labels2d.segmentation(b, cuda).max(dim=-1)
+            got_s, got_i = pipe._labels2d.segmentation_graph(b, cuda)
+            assert pipe._labels2d.seg_graph['graph'] is not None  # the capture worked: this is the replay path
             # same operators; the convolution library may pick another algorithm between calls, so scores agree to
             # rounding and an arg-max can flip only where two classes tie to that precision
             assert torch.allclose(got_s, want_s, atol=1e-5, rtol=0), i
@@ -320,7 +320,7 @@ def test_fuse_predict_strategy_matches_reference_golden(cuda, engine):
     with torch.no_grad():
         for i in range(2):
             b = _batch(st, i, cuda)
-            ids, scores = pipe._frame_semantics(b)
+            ids, scores = pipe._labels2d.frame_semantics(b, cuda)
             scores, ids = scores.reshape(h, w).cpu().numpy(), ids.reshape(h, w).cpu().numpy()
             margin = g['f%d_seg_margin' % i]
             clear = margin > 1e-4
@@ -603,7 +603,7 @@ def test_fuse_many_with_predicted_semantics(cuda):
                 one.fuse(batch(ds_b, s, i), db_b, cuda)
         many.check()
         one.check()
-    assert many.__dict__['_seg_graph_many']['graph'] is not None  # the batched pass was captured and replayed
+    assert many._labels2d.seg_graph_many['graph'] is not None  # the batched pass was captured and replayed
     for s in scenes:
         assert torch.equal(db_a.scenes_est[s].volume.view(torch.int16), db_b.scenes_est[s].volume.view(torch.int16))
         assert torch.equal(db_a.fusion_weights[s].view(torch.int16), db_b.fusion_weights[s].view(torch.int16))
@@ -741,10 +741,11 @@ def test_fuse_sequence_without_a_2d_network(cuda, sem):
 
 
 def test_streams_overlap_probe(cuda):
-    """ojf_streams_overlap (set-up helper behind Pipeline._side_stream): a stream never runs beside itself; two streams give
-    0 or 1 (the runtime's queue mapping decides); _side_stream returns a stream that passed the probe when one of its eight
+    """ojf_streams_overlap (set-up helper behind labels2d.side_stream): a stream never runs beside itself; two streams give
+    0 or 1 (the runtime's queue mapping decides); side_stream returns a stream that passed the probe when one of its eight
     candidates does."""
     from online_joint_depthfusion_and_semantic_amd import _lib
+    from online_joint_depthfusion_and_semantic_amd.labels2d import side_stream
     lib = _lib.load()
     a, b = torch.cuda.Stream(device=cuda), torch.cuda.Stream(device=cuda)
     assert lib.ojf_streams_overlap(a.cuda_stream, a.cuda_stream) == 0
@@ -754,7 +755,7 @@ def test_streams_overlap_probe(cuda):
     pipe = Pipeline(cfg).to(cuda).eval()
     pipe.device = torch.device(cuda)
     main = torch.cuda.current_stream(cuda)
-    side = pipe._side_stream([main])
+    side = side_stream(cuda, [main])
     assert isinstance(side, torch.cuda.Stream) and side.cuda_stream != main.cuda_stream
 
 
@@ -807,7 +808,7 @@ def test_fuse_sequence_prefetch_of_a_dropped_chunk_is_never_taken(cuda):
             gc.collect()
             other = [_batch(st_a, i, cuda) for i in range(8, 12)]  # new dicts, other frames, maybe the old addresses
             pre.fuse_sequence(other, db_a, cuda)
-            assert pre.__dict__['_prefetch'].get('hits', 0) == 0
+            assert pre._labels2d.prefetch.get('hits', 0) == 0
             plain.fuse_sequence([_batch(st_b, i, cuda) for i in range(0, 4)], db_b, cuda)
             plain.fuse_sequence([_batch(st_b, i, cuda) for i in range(8, 12)], db_b, cuda)
         pre.check()
@@ -819,7 +820,7 @@ def test_fuse_sequence_prefetch_of_a_dropped_chunk_is_never_taken(cuda):
         pre.fuse_sequence(first, db_a, cuda, prefetch=nxt)
         pre.fuse_sequence(nxt, db_a, cuda)
         pre.check()
-    assert pre.__dict__['_prefetch']['hits'] == 1
+    assert pre._labels2d.prefetch['hits'] == 1
 
 
 @pytest.mark.parametrize('entry', ['fuse_sequence', 'fuse_many', 'fuse_many_joint'])
@@ -1012,8 +1013,8 @@ def test_single_frame_and_batched_2d_graphs_share_one_engine(cuda):
                 single.fuse(batch(ds_b, s, i), db_b, cuda)
         single.check()
         b = batch(ds_a, scenes[0], 7)
-        ids_m, sc_m = mixed._frame_semantics(b)
-        ids_s, sc_s = single._frame_semantics(b)
+        ids_m, sc_m = mixed._labels2d.frame_semantics(b, cuda)
+        ids_s, sc_s = single._labels2d.frame_semantics(b, cuda)
         assert torch.isfinite(sc_m).all() and torch.equal(ids_m, ids_s) and torch.equal(sc_m, sc_s)
     for s in scenes:
         # geometry does not see the labels: bit for bit; labels: the batched pass's rounding at near-ties only
@@ -1067,7 +1068,7 @@ def test_segmentation_on_odd_frame_sizes_says_why(cuda):
     with torch.no_grad():
         with pytest.warns(RuntimeWarning, match='multiples of 16'), pytest.raises(RuntimeError):
             pipe.fuse(_batch(st, 0, cuda), db, cuda)
-    assert pipe.__dict__.get('_warned_seg_fallback') is True
+    assert pipe._labels2d.warned_seg_fallback is True
 
 
 def test_announced_training_frames_change_no_bit(cuda):
@@ -1097,8 +1098,8 @@ def test_announced_training_frames_change_no_bit(cuda):
             out = pipe.fuse_training(batches[i], db, cuda)
             hits.append(pipe.announce_hits)
             # the stranger waits through frame 2 (the documented order: announced one frame step ahead), then it is dropped unused
-            assert any(a[0] is stranger for a in pipe.__dict__.get('_announced', [])) == (announce and i == 2)
-            assert len(pipe.__dict__.get('_announced', [])) <= 1
+            assert any(a[0] is stranger for a in pipe._announcements.held) == (announce and i == 2)
+            assert len(pipe._announcements.held) <= 1
             loss = (out['tsdf_fused'] - out['tsdf_target']).abs().mean()
             loss.backward()
             outs.append((out['tsdf_est'].detach().clone(), out['tsdf_fused'].detach().clone(), loss.detach().clone()))
@@ -1111,7 +1112,7 @@ def test_announced_training_frames_change_no_bit(cuda):
         assert hits == ([0, 1, 2, 2, 3, 4] if announce else [0] * frames)
         pipe.announce_training_frame(batches[frames], cuda)
         pipe.announce_training_frame(None)
-        assert pipe.__dict__['_announced'] == []
+        assert pipe._announcements.held == []
         net = pipe._fusion_network
         return (outs, [p.detach().clone() for p in net.parameters()], [b.detach().clone() for b in net.buffers()],
                 [db.scenes_est[st.scene].volume.clone(), db.fusion_weights[st.scene].clone()])

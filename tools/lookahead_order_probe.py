@@ -9,7 +9,7 @@ def la(L, tag):
     n_la = (60 + L - 1) // L * L
     case = bench.Case(c, dev, 0, 3 * n_la + 4 * L)
     r = bench.run_lookahead(case, n_la, 2 * L, sync, L, 3)
-    pf = case.pipe.__dict__.get('_prefetch'); lib = bench._lib.load() if hasattr(bench, '_lib') else __import__('online_joint_depthfusion_and_semantic_amd._lib', fromlist=['x']).load()
+    pf = case.pipe._labels2d.prefetch; lib = bench._lib.load() if hasattr(bench, '_lib') else __import__('online_joint_depthfusion_and_semantic_amd._lib', fromlist=['x']).load()
     main = torch.cuda.current_stream(dev)
     print(tag, 'L', L, round(r['value'], 1), 'prefetched %d taken %d side stream %x main %x overlap %d' % (pf['n'], pf.get('hits', 0), pf['stream'].cuda_stream, main.cuda_stream, lib.ojf_streams_overlap(main.cuda_stream, pf['stream'].cuda_stream)), flush=True)
     del case; torch.cuda.empty_cache()

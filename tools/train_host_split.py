@@ -51,7 +51,7 @@ host = sum(T[k] for k in keys[:-1]) / m * 1e3
 print('training frame step, one frame at a time on an empty queue (%d frames):' % m)
 for k in keys: print('  %-78s %.3f ms/frame' % (k, T[k] / m * 1e3))
 print('  host enqueue total %.3f ms/frame; + drain %.3f = %.3f ms/frame serial' % (host, T[keys[-1]] / m * 1e3, host + T[keys[-1]] / m * 1e3))
-tn = pipe.__dict__.get('_hip_train')
+tn = pipe._hip_train
 if tn is not None and tn._trainers:
     tr = next(iter(tn._trainers.values()))
     print('  executor launches: forward %d, backward %d' % (tr.fwd_launches, tr.bwd_launches))

@@ -71,7 +71,7 @@ def main():
     th = time.perf_counter() - t0
     torch.cuda.synchronize()
     t = time.perf_counter() - t0
-    tn = case.pipe.__dict__['_hip_train']
+    tn = case.pipe._hip_train
     print('overlap %s thread %s: %.3f ms per frame (host loop %.3f)' % (tn.overlap, tn.overlap_thread, 1e3 * t / n, 1e3 * th / n))
     for k, v in acc.items():
         print('  %-50s %.3f ms/frame' % (k, 1e3 * v / n))
