@@ -637,6 +637,41 @@ int ojf_track_associate(const float *depth_dev, const uint8_t *mask_dev, int h, 
                         double *pose_dev, double *sums_dev, float *jr_dev, uint8_t *reason_dev, int *status_dev,
                         ojf_stream_t stream);
 
+/* ---- TRACK RGBD (ojf_track with a photometric term against the model's colour; no counterpart in the reference) -------
+ * ojf_track_rgbd: ojf_track's arguments, meaning and outputs, plus image_dev u8[h*w*4] the live colour image (RGBA bytes
+ *   as ojf_fuse_color takes them, the fourth ignored), model_color_host: a host array of `levels` device pointers to the
+ *   level's ojf_color_render image u8[h_l*w_l*4] at the level's model depth (alpha 0: no colour there), photo_weight
+ *   (lambda, metres per intensity level, finite, >= 0; 0 adds no photometric row: ojf_track's bits), photo_thresh
+ *   (intensity levels, >= 0: a photometric residual beyond it is cut) and grad_depth_limit (m, > 0: a model intensity
+ *   gradient counts only where the model depth of the four axis neighbours is within it of the centre's).  Intensity is
+ *   (77 R + 150 G + 29 B) / 256.  A pixel whose geometric reason is 0, 2 or 7 also gets a photometric row
+ *   lambda * (J_I, r_I), r_I = I_model(bilinear at its projection) - I_live; the inlier count counts a pixel with either row
+ *   once.  workspace_dev: >= ojf_track_rgbd_workspace_bytes(h, w, levels) bytes; with N = sum of h_l*w_l and
+ *   P = N*4 rounded up to 256, it holds the depth pyramid f32[N] at 0, the live intensity pyramid f32[N] at P and the
+ *   model maps f32[N][4] = (I_m, gx, gy, valid) at 2P, level after level.  Enqueues 1 + 2*sum(iterations) kernels on
+ *   `stream` and never waits.  The exact fp32 / fp64 definition is in csrc/ojf_track_rgbd.hip.
+ * ojf_track_rgbd_associate: the counterpart of ojf_track_associate (the workspace sized for level + 1 levels; the model
+ *   map is written for `level` only): beside jr_dev / reason_dev it exports photo_jr_dev (or NULL) f32[h_l*w_l][7] =
+ *   (J_I, r_I) unscaled (0 unless the photometric reason is 0) and photo_reason_dev (or NULL) u8[h_l*w_l]: 0 row added,
+ *   1 / 3 / 4 / 5 / 6 as the geometric codes, 8 a bilinear corner is not valid, 9 residual beyond photo_thresh, 10 the
+ *   photometric term is off (photo_weight 0).  For tests and diagnostics. */
+size_t ojf_track_rgbd_workspace_bytes(int h, int w, int levels);
+int ojf_track_rgbd(const float *depth_dev, const uint8_t *mask_dev, const uint8_t *image_dev, int h, int w, int levels,
+                   const double *K_host, const float *Kinv_host, const float *const *model_depth_host,
+                   const float *const *model_normals_host, const uint8_t *const *model_color_host,
+                   const double *E_ref_host, const double *E_init_host, const int *iterations_host, double dist_thresh,
+                   double angle_thresh_deg, double pyramid_delta, double min_inlier_fraction, double photo_weight,
+                   double photo_thresh, double grad_depth_limit, void *workspace_dev, size_t workspace_bytes,
+                   double *pose_dev, double *stats_dev, int *status_dev, ojf_stream_t stream);
+int ojf_track_rgbd_associate(const float *depth_dev, const uint8_t *mask_dev, const uint8_t *image_dev, int h, int w,
+                             int level, const double *K_host, const float *Kinv_host, const float *model_depth_dev,
+                             const float *model_normals_dev, const uint8_t *model_color_dev, const double *E_ref_host,
+                             const double *E_pose_host, double dist_thresh, double angle_thresh_deg, double pyramid_delta,
+                             double min_inlier_fraction, double photo_weight, double photo_thresh, double grad_depth_limit,
+                             void *workspace_dev, size_t workspace_bytes, double *pose_dev, double *sums_dev,
+                             float *jr_dev, uint8_t *reason_dev, float *photo_jr_dev, uint8_t *photo_reason_dev,
+                             int *status_dev, ojf_stream_t stream);
+
 /* ---- PROJECTIVE (classical voxel-projective TSDF fusion, no network; no counterpart in the reference) ----------------
  * ojf_fuse_projective: fuses n depth views (1 <= n <= OJF_PROJECTIVE_MAX_VIEWS, one h x w for all) into the fp16 volumes
  *   tsdf_dev / weights_dev [X,Y,Z] in place, Curless-Levoy / KinectFusion style: every voxel centre (origin +

@@ -178,6 +178,17 @@ SIGNATURES = {
     # workspace, workspace_bytes, pose, sums, jr, reason, status, stream
     'ojf_track_associate': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _vp, _sz, _vp, _vp, _vp,
                                  _vp, _vp, _vp]),
+    'ojf_track_rgbd_workspace_bytes': (_sz, [_i, _i, _i]),
+    # depth, mask, image, h, w, levels, K, Kinv, model depth[], model normals[], model colour[], E_ref, E_init, iterations,
+    # dist, angle, delta, min_inlier_fraction, photo_weight, photo_thresh, grad_depth_limit, workspace, workspace_bytes,
+    # pose, stats, status, stream
+    'ojf_track_rgbd': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _d, _d, _d,
+                            _vp, _sz, _vp, _vp, _vp, _vp]),
+    # depth, mask, image, h, w, level, K, Kinv, model depth, model normals, model colour, E_ref, E_pose, dist, angle, delta,
+    # min_inlier_fraction, photo_weight, photo_thresh, grad_depth_limit, workspace, workspace_bytes, pose, sums, jr, reason,
+    # photo jr, photo reason, status, stream
+    'ojf_track_rgbd_associate': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _d, _d,
+                                      _d, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # tsdf, weights, ids, scores, X, Y, Z, origin, resolution, n, K, E, depth, mask, labels, label scores, h, w, trunc,
     # max_weight, near, carve, stream
     'ojf_fuse_projective': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _i, _vp]),

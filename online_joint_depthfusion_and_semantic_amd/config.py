@@ -60,7 +60,7 @@ def default_config(h=240, w=320, semantics=False, use_semantics=None, n_classes=
                          'depth_filter': None},
         'SEMANTIC_2D_MODEL': {'stage': 2, 'n_classes': n_classes},
         'TRAINING': {'optimization': {'accumulation_steps': 8, 'clipping': True}},
-        'TESTING': {'outlier_filter_val': 2, 'track_invalid_poses': False},
+        'TESTING': {'outlier_filter_val': 2, 'track_invalid_poses': False, 'track_with_color': False},
         'DATA': {'semantics': 'class{}'.format(n_classes) if semantics else None,
                  'semantic_strategy': 'gt', 'semantic_grid': bool(semantics), 'input': depth_key,
                  'target': 'depth_gt', 'resx': w, 'resy': h, 'init_value': init_value, 'pad': 0},

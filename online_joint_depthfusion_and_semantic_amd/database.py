@@ -405,17 +405,25 @@ class Database(torch.utils.data.Dataset):
                                                intrinsics=intrinsics, extrinsics=extrinsics, depth=out['depth'])
         return out
 
-    def track(self, scene_id, depth, intrinsics, extrinsics, reference_extrinsics=None, filter=None, **kw):
+    def track(self, scene_id, depth, intrinsics, extrinsics, reference_extrinsics=None, filter=None, image=None, **kw):
         """Camera pose of a depth frame against the estimated volume of a scene (tracking.py, frame-to-model ICP):
         tracking starts at ``extrinsics`` and the model is ray-cast at ``reference_extrinsics`` (default: the same pose);
         ``kw`` goes to ``tracking.track_frame`` (mask, levels, iterations, thresholds).  Unobserved voxels are transparent.
         ``filter``: a dict of ``frames.prepare_depth`` options - the frame and its mask go through it first (None: as they are).
+        ``image``: the frame's colour image (u8 [h,w,3|4] or float [3,h,w] on the 0..255 scale) - tracking then also compares
+        it with the scene's colour volume (``tracking.track_frame_rgbd``, which ``kw`` goes to: photo_weight, photo_thresh,
+        grad_depth_limit); a scene without a colour volume (``integrate_color``) is a ValueError.
         Returns {'extrinsics' f64 [4,4], 'ok', 'status', 'stats'}.  Works on resident and on host (to_numpy) state."""
         from . import tracking
         tsdf = self._device_volume(self.scenes_est[scene_id].volume, torch.float16)
         w = self._device_volume(self.fusion_weights[scene_id], torch.float16)
+        cvol = self._color_volume(scene_id, 'track') if image is not None else None
         if filter is not None:
             depth, kw['mask'] = _filtered(_to_dev(depth, tsdf.device), _to_dev(kw.get('mask'), tsdf.device), intrinsics, filter)
+        if image is not None:
+            return tracking.track_frame_rgbd(tsdf, w, cvol, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]),
+                                             image=image, depth=depth, intrinsics=intrinsics, extrinsics=extrinsics,
+                                             reference_extrinsics=reference_extrinsics, **kw)
         return tracking.track_frame(tsdf, w, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]),
                                     depth=depth, intrinsics=intrinsics, extrinsics=extrinsics,
                                     reference_extrinsics=reference_extrinsics, **kw)

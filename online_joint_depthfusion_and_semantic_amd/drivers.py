@@ -217,7 +217,9 @@ def _tracked_batch(batch, database, config, last_pose, log):
     E0 = last_pose[scene]
     depth = batch[config.DATA.input][0]
     mask = batch['mask'][0] if 'mask' in batch else None
-    res = database.track(scene, depth, batch['intrinsics'][0], E0, reference_extrinsics=E0, mask=mask)
+    # TESTING.track_with_color: the batch's colour image joins the tracking (the scene must have a colour volume)
+    image = batch['image'][0] if config.TESTING.get('track_with_color', False) else None
+    res = database.track(scene, depth, batch['intrinsics'][0], E0, reference_extrinsics=E0, mask=mask, image=image)
     if not res['ok']:
         log('track_invalid_poses: {} skipped: tracking failed (status {})'.format(frame_id, res['status']))
         return None
