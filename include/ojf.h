@@ -1152,6 +1152,44 @@ int ojf_depth_prepare(const float *depth_dev /* f32[n,h,w] */, const uint8_t *ma
                       float edge_abs, float edge_rel, float near, float far, float cos_min, float *depth_out_dev,
                       uint8_t *valid_out_dev /* or NULL */, float *normals_out_dev /* f32[n,h,w,3] or NULL */, ojf_stream_t stream);
 
+/* ---- RELOC (keyframe relocalisation by randomised ferns: a code per frame, a device store of keyframe codes and poses, the
+ * nearest-keyframe search; definition: csrc/ojf_reloc.hip; the reference takes every pose from its dataset) ---
+ * A frame's code: the frame is cut into cells of `cell` x `cell` pixels (1..64; CH = h / cell rows of CW = w / cell cells,
+ *   trailing rows and columns ignored, CH * CW <= 1024); a cell's channel 0 is the mean of the depths of its valid pixels
+ *   (mask != 0, finite, 0 < d < 64) quantised to 1/1024 m, valid when at least half of the pixels are, and channels 1..3 the
+ *   means of the R, G, B bytes of image_dev (u8 [n,h,w,4], color.pack_image; without an image 0).  Fern m of n_ferns (a
+ *   multiple of 8 in 8..4096) makes 4 bits "value(cell, channel) > threshold" from entries [m][0..3] of fern_cell_dev i32,
+ *   fern_channel_dev u8 (0..3) and fern_threshold_dev f32 (device memory; a bit of channel 0 also needs a valid cell); its
+ *   nibble sits in word m / 8 at bits 4 * (m % 8): n_ferns / 8 u32 words per frame.  Two codes differ by the number of
+ *   ferns whose nibbles differ.
+ * A store is device memory the caller owns: db_codes_dev u32 [capacity][n_ferns / 8], db_poses_dev f64 [capacity][12],
+ *   db_count_dev i32 [1] (set it to 0 before the first insert).  The count is read and written on the device only.
+ * ojf_reloc_encode: codes_dev u32 [n][n_ferns / 8] of n frames, and the code image f32 [n][4][CH][CW] if asked for (an
+ *   invalid cell holds 0).  One launch, one workgroup per frame.
+ * ojf_reloc_query: for each of n codes the k (1..16) smallest keys (u64) differ << 32 | keyframe over the first count
+ *   keyframes, ascending (equal codes: smallest keyframe first); places beyond count hold all-ones.  One launch, or two and
+ *   a stream-ordered scratch allocation for a capacity above 256.
+ * ojf_reloc_insert: the n frames in call order - best_dev[i] = the smallest key over the store as it stands (all-ones when
+ *   empty); the frame is wanted when force != 0, or the store is empty, or best's count > min_differ; added_dev[i] = 0 not
+ *   wanted, 2 wanted but count == capacity (nothing is written), 1 added: code and pose copied to slot count, count + 1.
+ *   One launch of one workgroup.
+ * No float atomics, no workgroup waits for another, never waits; the same bits on every run and for every split of the
+ *   frames into calls.  Refused before any HIP call: a null pointer other than mask_dev, image_dev, code_image_dev; n, h,
+ *   w < 1 or n * h * w >= 2^31; cell outside 1..64 or larger than the frame, more than 1024 cells; n_ferns no multiple of 8
+ *   in 8..4096; capacity outside 1..2^24; k outside 1..16; n > 65535 queries; min_differ outside 0..n_ferns; a pointer off
+ *   the grid of its element type, fern_cell_dev / fern_threshold_dev off the 16-byte grid, fern_channel_dev off the 4-byte
+ *   grid. */
+int ojf_reloc_encode(const float *depth_dev /* f32[n,h,w] */, const uint8_t *mask_dev /* u8[n,h,w] or NULL */,
+                     const uint8_t *image_dev /* u8[n,h,w,4] or NULL */, int n, int h, int w, int cell, int n_ferns,
+                     const int32_t *fern_cell_dev /* i32[M][4] */, const uint8_t *fern_channel_dev /* u8[M][4] */,
+                     const float *fern_threshold_dev /* f32[M][4] */, uint32_t *codes_dev /* u32[n][M/8] */,
+                     float *code_image_dev /* NULL or f32[n][4][CH][CW] */, ojf_stream_t stream);
+int ojf_reloc_query(const uint32_t *codes_dev /* u32[n][M/8] */, int n, int n_ferns, const uint32_t *db_codes_dev,
+                    const int32_t *db_count_dev, int capacity, int k, uint64_t *keys_dev /* u64[n][k] */, ojf_stream_t stream);
+int ojf_reloc_insert(const uint32_t *codes_dev /* u32[n][M/8] */, const double *poses_dev /* f64[n][12] */, int n, int n_ferns,
+                     int min_differ, int force, uint32_t *db_codes_dev, double *db_poses_dev, int32_t *db_count_dev, int capacity,
+                     uint64_t *best_dev /* u64[n] */, int32_t *added_dev /* i32[n] */, ojf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

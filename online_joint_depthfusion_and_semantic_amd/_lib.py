@@ -269,6 +269,12 @@ SIGNATURES = {
     # depth, mask, n, h, w, K, radius, spatial, range0, range2, edge_abs, edge_rel, near, far, cos_min, depth out, valid out,
     # normals out, stream
     'ojf_depth_prepare': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _f, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
+    # depth, mask, image, n, h, w, cell, n_ferns, fern cells, fern channels, fern thresholds, codes, code image, stream
+    'ojf_reloc_encode': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # codes, n, n_ferns, store codes, store count, capacity, k, keys, stream
+    'ojf_reloc_query': (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    # codes, poses, n, n_ferns, min_differ, force, store codes, store poses, store count, capacity, best, added, stream
+    'ojf_reloc_insert': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
 }
 
 _LIB = None

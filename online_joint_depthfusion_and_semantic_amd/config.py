@@ -60,7 +60,10 @@ def default_config(h=240, w=320, semantics=False, use_semantics=None, n_classes=
                          'depth_filter': None},
         'SEMANTIC_2D_MODEL': {'stage': 2, 'n_classes': n_classes},
         'TRAINING': {'optimization': {'accumulation_steps': 8, 'clipping': True}},
-        'TESTING': {'outlier_filter_val': 2, 'track_invalid_poses': False, 'track_with_color': False},
+        'TESTING': {'outlier_filter_val': 2, 'track_invalid_poses': False, 'track_with_color': False,
+                    # with track_invalid_poses: fused frames are harvested as keyframes and a pose-less frame the tracker cannot
+                    # place is relocalised from them (relocalize.py); 'relocalizer': keywords of relocalize.Relocalizer
+                    'relocalize': False},
         'DATA': {'semantics': 'class{}'.format(n_classes) if semantics else None,
                  'semantic_strategy': 'gt', 'semantic_grid': bool(semantics), 'input': depth_key,
                  'target': 'depth_gt', 'resx': w, 'resy': h, 'init_value': init_value, 'pad': 0},
@@ -74,4 +77,5 @@ def database_config(config):
     d.implementation = config.SETTINGS.implementation
     d.transform = None
     d.n_classes = config.SEMANTIC_2D_MODEL.n_classes if config.DATA.semantics else None
+    d.relocalizer = dict(config.get('TESTING', {}).get('relocalizer', None) or {})
     return d

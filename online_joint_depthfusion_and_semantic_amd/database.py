@@ -77,6 +77,9 @@ class Database(torch.utils.data.Dataset):
         self._tvl1_changed = set()  # scenes whose histograms took views since their solver last ran
         self._label_tv_solvers = {}  # scene -> label_tv.Solver: the workspace of regularize_labels, kept for the next call
         self.tracked_poses = {}  # frame_id -> f64 [4,4] camera-to-world: frames fused with a tracked pose (drivers.test_fusion)
+        self.relocalizers = {}  # scene -> relocalize.Relocalizer: the keyframes of add_keyframe, made on first use
+        self.relocalizer_options = dict(config.get('relocalizer', None) or {})  # Relocalizer keywords (TESTING.relocalizer)
+        self.relocalized = []  # frame ids fused with a pose that came from a keyframe (drivers.test_fusion)
 
         for s in dataset.scenes:
             self.scenes.append(s)
@@ -178,6 +181,7 @@ class Database(torch.utils.data.Dataset):
         being re-allocated on the host and uploaded."""
         for s in ([scene_id] if scene_id else self.scenes):
             self.state[s] = False
+            self.relocalizers.pop(s, None)  # (keyframes of a volume that is gone)
             c = self.colors.get(s)
             if _is_dev(c):
                 ops.volume_fill(c, 0.0)
@@ -221,6 +225,7 @@ class Database(torch.utils.data.Dataset):
         self.depth_hists.pop(scene_id, None)
         self._tvl1_solvers.pop(scene_id, None)
         self._label_tv_solvers.pop(scene_id, None)
+        self.relocalizers.pop(scene_id, None)
         if self.semantics:
             self.ids_est[scene_id] = None
             self.scores[scene_id] = None
@@ -427,6 +432,46 @@ class Database(torch.utils.data.Dataset):
         return tracking.track_frame(tsdf, w, origin=self.origin[scene_id], resolution=float(self.resolution[scene_id]),
                                     depth=depth, intrinsics=intrinsics, extrinsics=extrinsics,
                                     reference_extrinsics=reference_extrinsics, **kw)
+
+    def _relocalizer(self, scene_id, depth):
+        """The scene's ``relocalize.Relocalizer``, made on first use for the size of ``depth`` [..,h,w] from
+        ``relocalizer_options``."""
+        from . import relocalize
+        r = self.relocalizers.get(scene_id)
+        if r is None:
+            h, w = (int(x) for x in depth.shape[-2:])
+            r = relocalize.Relocalizer(h, w, device=self.device, **self.relocalizer_options)
+            self.relocalizers[scene_id] = r
+        return r
+
+    def add_keyframe(self, scene_id, depth, extrinsics, mask=None, image=None, filter=None, force=False):
+        """Offer one or more frames with their camera-to-world poses to the scene's keyframe store (relocalize.py): a
+        frame is kept when it differs enough from every keyframe (``relocalizer_options['min_dissimilarity']``), or when
+        ``force``.  depth [h,w] / [n,h,w], mask and image (read only by a colour table) of the same frames; ``filter`` as
+        for ``track`` (a filter with max_angle needs intrinsics and is refused here).  Returns device tensors {'added',
+        'best'} without synchronising; the volumes are not touched."""
+        dev = lambda x: _to_dev(x, self.device)  # noqa: E731
+        depth, mask = dev(depth), dev(mask)
+        if filter is not None:
+            depth, mask = _filtered(depth, mask, None, filter)
+        return self._relocalizer(scene_id, depth).add(depth, extrinsics, mask=mask, image=dev(image), force=force)
+
+    def relocalize(self, scene_id, depth, intrinsics, mask=None, image=None, filter=None, k=4, **kw):
+        """The pose of a frame without one, against the estimated volume of a scene: the ``k`` nearest keyframes of the
+        scene's store are the starts of ``track`` (relocalize.relocalize_frame, which ``kw`` goes to: max_dissimilarity and
+        the tracker's keywords).  ``image`` joins the tracking when the scene has a colour volume, and the code when the
+        store's table is a colour table.  Returns ``track``'s dict plus 'candidate' and 'candidates'; {'ok': False, 'status':
+        4} when no keyframe gave a pose - a scene without keyframes included.  Works on resident and on host state."""
+        from . import relocalize
+        tsdf = self._device_volume(self.scenes_est[scene_id].volume, torch.float16)
+        w = self._device_volume(self.fusion_weights[scene_id], torch.float16)
+        depth, mask = _to_dev(depth, tsdf.device), _to_dev(mask, tsdf.device)
+        if filter is not None:
+            depth, mask = _filtered(depth, mask, intrinsics, filter)
+        cvol = self._color_volume(scene_id, 'relocalize') if image is not None and self.colors.get(scene_id) is not None else None
+        return relocalize.relocalize_frame(tsdf, w, self._relocalizer(scene_id, depth), origin=self.origin[scene_id],
+                                           resolution=float(self.resolution[scene_id]), depth=depth, intrinsics=intrinsics, mask=mask,
+                                           image=image, colors=cvol, k=k, **kw)
 
     def integrate_depth(self, scene_id, depth, intrinsics, extrinsics, mask=None, labels=None, label_scores=None, filter=None, **kw):
         """Fuse one or more depth maps into the resident volumes of a scene by classical projective TSDF averaging

@@ -128,6 +128,10 @@ def test_fusion(config, dataset, device, rank=0, world=1, state_dict=None, log=p
     # TESTING.track_invalid_poses: a frame without a finite pose is tracked against its scene's volume (tracking.py) from the
     # last pose fused into that scene, and fused with the tracked pose; off (the default), such frames are skipped
     track = bool(config.TESTING.get('track_invalid_poses', False))
+    # TESTING.relocalize (read with track_invalid_poses only): every frame that is fused is offered to its scene's keyframe
+    # store (relocalize.py), and a pose-less frame with no earlier pose in its scene, or whose tracking from the last pose
+    # fails, gets its pose from the nearest keyframes instead of being skipped
+    reloc = track and bool(config.TESTING.get('relocalize', False))
     last_pose = {}  # scene -> f64 [4,4] of the last frame fused into it (only kept when tracking)
     with torch.no_grad():
         chunk, ahead = [], None  # `ahead`: the chunk in front of `chunk`, fused once `chunk` is complete (its 2-D pass then runs beside ahead's frame steps)
@@ -141,12 +145,15 @@ def test_fusion(config, dataset, device, rank=0, world=1, state_dict=None, log=p
                 if chunk:
                     pipeline.fuse_sequence(chunk, database, device)
                     chunk = []
-                batch = _tracked_batch(batch, database, config, last_pose, log)
+                batch = _tracked_batch(batch, database, config, last_pose, log, reloc)
                 if batch is None:
                     continue
             if track:
                 E = batch['extrinsics'][0].to(torch.float64).reshape(-1, 4)
                 last_pose[batch['frame_id'][0].split('/')[0]] = np.concatenate([E[:3].numpy(), [[0.0, 0.0, 0.0, 1.0]]])
+            if reloc:
+                database.add_keyframe(batch['frame_id'][0].split('/')[0], batch[config.DATA.input][0], E[:3],
+                                      mask=batch['mask'][0] if 'mask' in batch else None, image=_reloc_image(batch, config))
             if lookahead <= 1:
                 pipeline.fuse(_host_pose_batch(batch, device), database, device)
                 continue
@@ -206,20 +213,39 @@ def test_fusion(config, dataset, device, rank=0, world=1, state_dict=None, log=p
     return results, per_scene, database
 
 
-def _tracked_batch(batch, database, config, last_pose, log):
+def _reloc_image(batch, config):
+    """The batch's colour image where the keyframe codes read it (TESTING.relocalizer.color), else None."""
+    return batch['image'][0] if (config.TESTING.get('relocalizer', None) or {}).get('color', False) else None
+
+
+def _tracked_batch(batch, database, config, last_pose, log, reloc=False):
     """``batch`` with the pose tracked against its scene's volume from the scene's last fused pose, recorded in
-    ``database.tracked_poses``; None (and a log line) when the scene has no earlier pose or tracking fails."""
+    ``database.tracked_poses``; None (and a log line) when the scene has no earlier pose or tracking fails.  ``reloc``: in
+    those two cases the pose is sought from the scene's keyframes first (``Database.relocalize``; the frame is then listed in
+    ``database.relocalized`` as well), and the frame is skipped only if that fails too."""
     frame_id = batch['frame_id'][0]
     scene = frame_id.split('/')[0]
-    if scene not in last_pose:
+    if scene not in last_pose and not reloc:
         log('track_invalid_poses: {} skipped: no earlier pose in scene {}'.format(frame_id, scene))
         return None
-    E0 = last_pose[scene]
     depth = batch[config.DATA.input][0]
     mask = batch['mask'][0] if 'mask' in batch else None
     # TESTING.track_with_color: the batch's colour image joins the tracking (the scene must have a colour volume)
     image = batch['image'][0] if config.TESTING.get('track_with_color', False) else None
-    res = database.track(scene, depth, batch['intrinsics'][0], E0, reference_extrinsics=E0, mask=mask, image=image)
+    res = None
+    if scene in last_pose:
+        E0 = last_pose[scene]
+        res = database.track(scene, depth, batch['intrinsics'][0], E0, reference_extrinsics=E0, mask=mask, image=image)
+    if (res is None or not res['ok']) and reloc:
+        found = database.relocalize(scene, depth, batch['intrinsics'][0], mask=mask,
+                                    image=image if image is not None else _reloc_image(batch, config))
+        if not found['ok']:
+            log('track_invalid_poses: {} skipped: {}, relocalisation failed (status {})'.format(
+                frame_id, 'no earlier pose in scene {}'.format(scene) if res is None else 'tracking failed (status {})'.format(res['status']),
+                found['status']))
+            return None
+        database.relocalized.append(frame_id)
+        res = found
     if not res['ok']:
         log('track_invalid_poses: {} skipped: tracking failed (status {})'.format(frame_id, res['status']))
         return None
