@@ -45,7 +45,9 @@
 // iteration one associate and one solve: 1 + 2·sum(iterations).  Kernel boundaries order the iterations; the host never
 // waits.  No atomics, no inline assembly; every output is written once: the same bits on every run.
 // The terms, the block sums and the solve kernel of (b) and (c) are in ojf_gauss_newton.h, which ojf_register.hip shares.
-#include "ojf_gauss_newton.h"
+// The code of (a) and (b) up to the row (J, r), the host checks and the launch loop are in ojf_track_front.h, which
+// ojf_track_rgbd.hip shares; here are the pyramid kernel and the associate kernel that leaves a pixel at its first failed test.
+#include "ojf_track_front.h"
 
 namespace ojf {
 
@@ -61,71 +63,19 @@ struct PyramidArgs {
     double init[12];
 };
 
-__device__ __forceinline__ float level0(const PyramidArgs &A, int r, int c)
-{
-    const size_t i = (size_t)r * A.w + c;
-    const float d = A.depth[i];
-    const bool ok = isfinite(d) && d > 0.0f && (!A.mask || A.mask[i] != 0);
-    return ok ? d : 0.0f;
-}
-
-__device__ __forceinline__ float block_value(const float v[4], float delta)
-{
-    float dmin = INFINITY;
-    bool any = false;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (v[k] != 0.0f) {
-            dmin = fminf(dmin, v[k]);
-            any = true;
-        }
-    }
-    if (!any) return 0.0f;
-    float s = 0.0f;
-    int n = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (v[k] != 0.0f && (v[k] - dmin) <= delta) {
-            s = s + v[k];
-            ++n;
-        }
-    }
-    return s / (float)n;
-}
-
-template <int LV>
-__device__ float pyr_value(const PyramidArgs &A, int r, int c)
-{
-    if constexpr (LV == 0) {
-        return level0(A, r, c);
-    } else {
-        const float v[4] = {pyr_value<LV - 1>(A, 2 * r, 2 * c), pyr_value<LV - 1>(A, 2 * r, 2 * c + 1),
-                            pyr_value<LV - 1>(A, 2 * r + 1, 2 * c), pyr_value<LV - 1>(A, 2 * r + 1, 2 * c + 1)};
-        return block_value(v, A.delta);
-    }
-}
-
 __global__ __launch_bounds__(kTrackThreads) void track_pyramid_kernel(PyramidArgs A)
 {
     const int g = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (g == 0 && A.pose) {
-        for (int i = 0; i < 12; ++i) A.pose[i] = A.init[i];
-        A.status[0] = 0;
-        A.status[1] = -1;
-    }
+    if (g == 0 && A.pose) write_initial_state(A.pose, A.status, A.init);
     if (g >= A.off[A.levels]) return;
     int l = 0;
     while (l + 1 < A.levels && g >= A.off[l + 1]) ++l;
     const int wl = A.w >> l;
     const int pix = g - A.off[l];
     const int r = pix / wl, c = pix % wl;
+    const DepthSource S = {A.depth, A.mask, A.w, A.delta};
     float v;
-    switch (l) {
-    case 0: v = pyr_value<0>(A, r, c); break;
-    case 1: v = pyr_value<1>(A, r, c); break;
-    case 2: v = pyr_value<2>(A, r, c); break;
-    default: v = pyr_value<3>(A, r, c); break;
-    }
+    with_level(l, [&](auto lv) { v = depth_pyramid_value<decltype(lv)::value>(S, r, c); });
     A.pyr[g] = v;
 }
 
@@ -138,86 +88,35 @@ struct AssocArgs {
     double *rows;             // [blocks, 29]
     float *jr;                // [h_l*w_l, 7] or NULL
     uint8_t *reason;          // [h_l*w_l] or NULL
-    int h, w, npix;
-    float Ki[9];
-    float fx, fy, cx, cy;
-    float Rr[9], tr[3];
-    float dist2, cos_thr;
+    LevelCamera cam;
 };
 
-__device__ __forceinline__ void ray_dc(const float Ki[9], int r, int c, float dc[3])
-{
-    const float cf = (float)c, rf = (float)r;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) dc[i] = Ki[3 * i] * cf + Ki[3 * i + 1] * rf + Ki[3 * i + 2];
-}
-
-__device__ __forceinline__ void vertex(const AssocArgs &A, int r, int c, float D, float V[3])
-{
-    float dc[3];
-    ray_dc(A.Ki, r, c, dc);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) V[i] = D * dc[i];
-}
-
-// reason code of pixel `pix`; for an inlier also J[6] and the residual
+// reason code of pixel `pix`, the first test of (b) that fails; for an inlier also J[6] and the residual
 __device__ int associate_pixel(const AssocArgs &A, const float R[9], const float t[3], int pix, float J[6], float &res)
 {
-    const int r = pix / A.w, c = pix % A.w;
+    const LevelCamera &C = A.cam;
+    const int r = pix / C.w, c = pix % C.w;
     const float D = A.D[pix];
     if (D == 0.0f) return 1;
-    if (r + 1 >= A.h || c + 1 >= A.w) return 2;
-    const float Dd = A.D[pix + A.w], Dr = A.D[pix + 1];
+    if (r + 1 >= C.h || c + 1 >= C.w) return 2;
+    const float Dd = A.D[pix + C.w], Dr = A.D[pix + 1];
     if (Dd == 0.0f || Dr == 0.0f) return 2;
-    float v[3], vd[3], vr[3];
-    vertex(A, r, c, D, v);
-    vertex(A, r + 1, c, Dd, vd);
-    vertex(A, r, c + 1, Dr, vr);
-    float a[3], b[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        a[i] = vd[i] - v[i];
-        b[i] = vr[i] - v[i];
-    }
-    const float x[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
-    const float xx = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
-    if (!(xx > 0.0f) || !isfinite(xx)) return 2;
-    const float xl = sqrtf(xx);
-    const float n[3] = {x[0] / xl, x[1] / xl, x[2] / xl};
-    float p[3], nw[3], e[3], q[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        p[i] = R[3 * i] * v[0] + R[3 * i + 1] * v[1] + R[3 * i + 2] * v[2] + t[i];
-        nw[i] = R[3 * i] * n[0] + R[3 * i + 1] * n[1] + R[3 * i + 2] * n[2];
-        e[i] = p[i] - A.tr[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) q[i] = A.Rr[i] * e[0] + A.Rr[3 + i] * e[1] + A.Rr[6 + i] * e[2];
-    if (!(q[2] > 0.0f)) return 3;
-    const float ux = A.fx * (q[0] / q[2]) + A.cx, uy = A.fy * (q[1] / q[2]) + A.cy;
-    const float fc = floorf(ux + 0.5f), fr = floorf(uy + 0.5f);
-    if (!(fc >= 0.0f && fc < (float)A.w && fr >= 0.0f && fr < (float)A.h)) return 4;
-    const int mc_ = (int)fc, mr = (int)fr;
-    const int mp = mr * A.w + mc_;
+    float v[3], n[3];
+    vertex(C, r, c, D, v);
+    if (!live_normal(C, r, c, v, Dd, Dr, n)) return 2;
+    float p[3], nw[3], q[3];
+    pose_transform(C, R, t, v, n, p, nw, q);
+    float ux, uy, fc, fr;
+    if (const int stop = project(C, q, ux, uy, fc, fr)) return stop;
+    const int mc = (int)fc, mr = (int)fr;
+    const int mp = mr * C.w + mc;
     const float dm = A.mdepth[mp];
     if (dm == 0.0f) return 5;
-    float mv[3], m[3], g[3];
-    vertex(A, mr, mc_, dm, mv);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        m[i] = A.Rr[3 * i] * mv[0] + A.Rr[3 * i + 1] * mv[1] + A.Rr[3 * i + 2] * mv[2] + A.tr[i];
-        g[i] = p[i] - m[i];
-    }
-    if (g[0] * g[0] + g[1] * g[1] + g[2] * g[2] > A.dist2) return 6;
+    float g[3];
+    if (!model_gap(C, p, mr, mc, dm, g)) return 6;
     const float nm[3] = {A.mnormal[3 * (size_t)mp], A.mnormal[3 * (size_t)mp + 1], A.mnormal[3 * (size_t)mp + 2]};
-    if (nw[0] * nm[0] + nw[1] * nm[1] + nw[2] * nm[2] < A.cos_thr) return 7;
-    res = nm[0] * g[0] + nm[1] * g[1] + nm[2] * g[2];
-    J[0] = p[1] * nm[2] - p[2] * nm[1];
-    J[1] = p[2] * nm[0] - p[0] * nm[2];
-    J[2] = p[0] * nm[1] - p[1] * nm[0];
-    J[3] = nm[0];
-    J[4] = nm[1];
-    J[5] = nm[2];
+    if (!normals_agree(C, nw, nm)) return 7;
+    plane_row(p, nm, g, J, res);
     return 0;
 }
 
@@ -225,60 +124,31 @@ __global__ __launch_bounds__(kTrackThreads) void track_associate_kernel(AssocArg
 {
     if (A.status[0] != 0) return;  // a failed step froze the pose: nothing more to do (uniform over the grid)
     float R[9], t[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) R[3 * i + k] = (float)A.pose[4 * i + k];
-        t[i] = (float)A.pose[4 * i + 3];
-    }
+    load_pose_f32(A.pose, R, t);
     double acc[kTrackTerms];
 #pragma unroll
     for (int e = 0; e < kTrackTerms; ++e) acc[e] = 0.0;
+    // rolled: the measured times (DESIGN.md sections 9 and 25) are this form's; left alone the compiler makes four copies of
+    // the body (2.2x the code), which were not measured
+#pragma unroll 1
     for (int k = 0; k < kTrackPixPerThread; ++k) {
         const int pix = (int)blockIdx.x * kTrackPixPerBlock + k * kTrackThreads + (int)threadIdx.x;
-        if (pix >= A.npix) break;
+        if (pix >= A.cam.npix) break;
         float J[6] = {0, 0, 0, 0, 0, 0}, res = 0.0f;
         const int why = associate_pixel(A, R, t, pix, J, res);
-        if (A.reason) A.reason[pix] = (uint8_t)why;
-        if (A.jr) {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) A.jr[7 * (size_t)pix + i] = why ? 0.0f : J[i];
-            A.jr[7 * (size_t)pix + 6] = why ? 0.0f : res;
-        }
+        export_row(A.reason, A.jr, pix, why, J, res);
         if (why) continue;
         add_terms(acc, J, res);
     }
     block_terms_to_row(acc, A.rows + (size_t)blockIdx.x * kTrackTerms);
 }
 
-static int level_blocks(int h, int w, int l) { return (((h >> l) * (w >> l)) + kTrackPixPerBlock - 1) / kTrackPixPerBlock; }
-
-static size_t pyramid_bytes(int h, int w, int levels)
-{
-    size_t n = 0;
-    for (int l = 0; l < levels; ++l) n += (size_t)(h >> l) * (size_t)(w >> l);
-    return align256(n * sizeof(float));
-}
-
-static size_t workspace_bytes(int h, int w, int levels)
-{
-    return pyramid_bytes(h, w, levels) + align256((size_t)level_blocks(h, w, 0) * kTrackTerms * sizeof(double)) + 256;
-}
-
-static int check_shape(const char *who, int h, int w, int levels)
-{
-    if (levels < 1 || levels > OJF_TRACK_MAX_LEVELS) return fail(std::string(who) + ": levels must be 1..OJF_TRACK_MAX_LEVELS");
-    if (h <= 0 || w <= 0 || (int64_t)h * w > 0x3fffffffLL) return fail(std::string(who) + ": bad image size");
-    if ((h >> (levels - 1)) < 8 || (w >> (levels - 1)) < 8)
-        return fail(std::string(who) + ": every level must be at least 8 x 8 pixels");
-    return 0;
-}
+// depth pyramid | block rows | 256 bytes (the probe's stats row)
+static size_t workspace_bytes(int h, int w, int levels) { return pyramid_bytes(h, w, levels) + rows_bytes(h, w); }
 
 static int check_thresholds(const char *who, double dist, double angle, double delta, double frac)
 {
-    if (!(dist > 0.0) || !isfinite(dist) || !(angle > 0.0) || !(angle <= 180.0) || !(delta >= 0.0) || !isfinite(delta) ||
-        !(frac >= 0.0) || !(frac <= 1.0))
-        return fail(std::string(who) + ": thresholds out of range");
+    if (!thresholds_in_range(dist, angle, delta, frac)) return fail(std::string(who) + ": thresholds out of range");
     return 0;
 }
 
@@ -304,19 +174,7 @@ static void fill_assoc(AssocArgs &A, const PyramidArgs &P, int l, const double *
     A.D = P.pyr + P.off[l];
     A.mdepth = mdepth; A.mnormal = mnormal; A.pose = pose; A.status = status; A.rows = rows;
     A.jr = nullptr; A.reason = nullptr;
-    A.h = P.h >> l; A.w = P.w >> l; A.npix = A.h * A.w;
-    for (int i = 0; i < 9; ++i) A.Ki[i] = Ki[i];
-    const double s = (double)(1 << l);
-    A.fx = (float)(K[0] / s);
-    A.fy = (float)(K[4] / s);
-    A.cx = (float)((K[2] + 0.5) / s - 0.5);
-    A.cy = (float)((K[5] + 0.5) / s - 0.5);
-    for (int i = 0; i < 3; ++i) {
-        for (int k = 0; k < 3; ++k) A.Rr[3 * i + k] = (float)Eref[4 * i + k];
-        A.tr[i] = (float)Eref[4 * i + 3];
-    }
-    A.dist2 = (float)(dist * dist);
-    A.cos_thr = (float)cos(angle * M_PI / 180.0);
+    fill_camera(A.cam, P.h, P.w, l, K, Ki, Eref, dist, angle);
 }
 
 static int launch_pyramid(const PyramidArgs &P, hipStream_t s)
@@ -327,11 +185,11 @@ static int launch_pyramid(const PyramidArgs &P, hipStream_t s)
     return 0;
 }
 
-static int launch_step(const AssocArgs &A, const SolveArgs &S, hipStream_t s)
+static int launch_associate(const AssocArgs &A, int blocks, hipStream_t s)
 {
-    hipLaunchKernelGGL(track_associate_kernel, dim3(S.nblocks), dim3(kTrackThreads), 0, s, A);
+    hipLaunchKernelGGL(track_associate_kernel, dim3(blocks), dim3(kTrackThreads), 0, s, A);
     OJF_HIP(hipGetLastError());
-    return launch_solve(S, s);
+    return 0;
 }
 
 }  // namespace ojf
@@ -339,8 +197,7 @@ static int launch_step(const AssocArgs &A, const SolveArgs &S, hipStream_t s)
 OJF_API size_t ojf_track_workspace_bytes(int h, int w, int levels)
 {
     using namespace ojf;
-    if (levels < 1 || levels > OJF_TRACK_MAX_LEVELS || h <= 0 || w <= 0 || (int64_t)h * w > 0x3fffffffLL) return 0;
-    return workspace_bytes(h, w, levels);
+    return sizable(h, w, levels) ? workspace_bytes(h, w, levels) : 0;
 }
 
 OJF_API int ojf_track(const float *depth_dev, const uint8_t *mask_dev, int h, int w, int levels, const double *K_host,
@@ -354,34 +211,20 @@ OJF_API int ojf_track(const float *depth_dev, const uint8_t *mask_dev, int h, in
         !iterations_host || !workspace_dev || !pose_dev || !stats_dev || !status_dev)
         return fail("ojf_track: null pointer argument");
     if (int rc = check_shape("ojf_track", h, w, levels)) return rc;
-    int total = 0;
-    for (int l = 0; l < levels; ++l) {
-        if (!model_depth_host[l] || !model_normals_host[l]) return fail("ojf_track: null pointer argument (model maps)");
-        if (iterations_host[l] < 0) return fail("ojf_track: negative iteration count");
-        total += iterations_host[l];
-        if (total > OJF_TRACK_MAX_ITERATIONS) return fail("ojf_track: more than OJF_TRACK_MAX_ITERATIONS iterations");
-    }
+    if (int rc = check_schedule("ojf_track", levels, iterations_host, model_depth_host, model_normals_host)) return rc;
     if (int rc = check_thresholds("ojf_track", dist_thresh, angle_thresh_deg, pyramid_delta, min_inlier_fraction)) return rc;
     if (workspace_bytes_ < workspace_bytes(h, w, levels)) return fail("ojf_track: workspace too small");
     const hipStream_t s = as_stream(stream);
     PyramidArgs P;
     fill_pyramid(P, depth_dev, mask_dev, workspace_dev, h, w, levels, pyramid_delta, pose_dev, status_dev, E_init_host);
     double *rows = (double *)((char *)workspace_dev + pyramid_bytes(h, w, levels));
-    if (int rc = launch_pyramid(P, s)) return rc;
-    int iter = 0;
-    for (int l = levels - 1; l >= 0; --l) {
-        AssocArgs A;
-        fill_assoc(A, P, l, K_host, Kinv_host + 9 * l, model_depth_host[l], model_normals_host[l], E_ref_host,
+    AssocArgs A[OJF_TRACK_MAX_LEVELS];
+    for (int l = 0; l < levels; ++l)
+        fill_assoc(A[l], P, l, K_host, Kinv_host + 9 * l, model_depth_host[l], model_normals_host[l], E_ref_host,
                    dist_thresh, angle_thresh_deg, pose_dev, status_dev, rows);
-        SolveArgs S;
-        fill_solve(S, rows, level_blocks(h, w, l), pose_dev, status_dev, stats_dev, nullptr, 0,
-                   min_inlier_fraction * (double)A.npix, E_init_host);
-        for (int k = 0; k < iterations_host[l]; ++k) {
-            S.iter = iter++;
-            if (int rc = launch_step(A, S, s)) return rc;
-        }
-    }
-    return 0;
+    if (int rc = launch_pyramid(P, s)) return rc;
+    return run_steps(h, w, levels, iterations_host, min_inlier_fraction, rows, pose_dev, status_dev, stats_dev, nullptr,
+                     E_init_host, s, [&](int l, int blocks) { return launch_associate(A[l], blocks, s); });
 }
 
 OJF_API int ojf_track_associate(const float *depth_dev, const uint8_t *mask_dev, int h, int w, int level,
@@ -410,9 +253,9 @@ OJF_API int ojf_track_associate(const float *depth_dev, const uint8_t *mask_dev,
                angle_thresh_deg, pose_dev, status_dev, rows);
     A.jr = jr_dev;
     A.reason = reason_dev;
-    SolveArgs S;
-    fill_solve(S, rows, level_blocks(h, w, level), pose_dev, status_dev, stats, sums_dev, 0,
-               min_inlier_fraction * (double)A.npix, E_pose_host);
+    int one_step[OJF_TRACK_MAX_LEVELS] = {};
+    one_step[level] = 1;
     if (int rc = launch_pyramid(P, s)) return rc;
-    return launch_step(A, S, s);
+    return run_steps(h, w, level + 1, one_step, min_inlier_fraction, rows, pose_dev, status_dev, stats, sums_dev, E_pose_host,
+                     s, [&](int, int blocks) { return launch_associate(A, blocks, s); });
 }

@@ -6,7 +6,10 @@
 //
 // Normative definition.  Rounding, "a + b + c", the levels, the level intrinsics fx_l .. cy_l, Ki, dc(r, c), the depth
 // pyramid (a), the association (b) with its reason codes 1..7, J and r, the 29 terms, the block sums and the solve (c) are
-// ojf_track.hip's: the same inputs give the same bits.  What is added:
+// ojf_track.hip's, and so is their code: (a), the stages of (b), the row export, the host checks and the launch loop are in
+// ojf_track_front.h, the terms and (c) in ojf_gauss_newton.h; the associate kernel here calls the stages in its own order
+// (every pixel with depth is projected; the model loads are issued together).  The same inputs give the same bits.  What is
+// added, and all that namespace rgbd holds:
 // (d) Intensity of an RGBA byte quadruple: I = (float)(77·R + 150·G + 29·B) / 256.0f (the integer is at most 65280: the
 //   conversion and the division are exact).  Live pyramid: I_0 from the live image (its fourth byte is ignored);
 //   I_{l+1}(r, c) = (((a + b) + c) + d)·0.25f over (I_l(2r,2c), I_l(2r,2c+1), I_l(2r+1,2c), I_l(2r+1,2c+1)).  It does not
@@ -33,7 +36,7 @@
 // Launches: one prepare (both pyramids, the model maps of every level, P = E_init, status {0, -1}), then per level from L-1
 // down to 0 and per iteration one associate and one shared solve: 1 + 2·sum(iterations).  The host never waits.  No atomics,
 // no inline assembly; every output is written once: the same bits on every run.
-#include "ojf_gauss_newton.h"
+#include "ojf_track_front.h"
 
 namespace ojf {
 namespace rgbd {
@@ -63,50 +66,6 @@ __device__ __forceinline__ float intensity_of(uint32_t rgba)
     return (float)v / 256.0f;
 }
 
-__device__ __forceinline__ float depth0(const PrepArgs &A, int r, int c)
-{
-    const size_t i = (size_t)r * A.w + c;
-    const float d = A.depth[i];
-    const bool ok = isfinite(d) && d > 0.0f && (!A.mask || A.mask[i] != 0);
-    return ok ? d : 0.0f;
-}
-
-__device__ __forceinline__ float depth_block(const float v[4], float delta)
-{
-    float dmin = INFINITY;
-    bool any = false;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (v[k] != 0.0f) {
-            dmin = fminf(dmin, v[k]);
-            any = true;
-        }
-    }
-    if (!any) return 0.0f;
-    float s = 0.0f;
-    int n = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (v[k] != 0.0f && (v[k] - dmin) <= delta) {
-            s = s + v[k];
-            ++n;
-        }
-    }
-    return s / (float)n;
-}
-
-template <int LV>
-__device__ float depth_value(const PrepArgs &A, int r, int c)
-{
-    if constexpr (LV == 0) {
-        return depth0(A, r, c);
-    } else {
-        const float v[4] = {depth_value<LV - 1>(A, 2 * r, 2 * c), depth_value<LV - 1>(A, 2 * r, 2 * c + 1),
-                            depth_value<LV - 1>(A, 2 * r + 1, 2 * c), depth_value<LV - 1>(A, 2 * r + 1, 2 * c + 1)};
-        return depth_block(v, A.delta);
-    }
-}
-
 template <int LV>
 __device__ float intensity_value(const PrepArgs &A, int r, int c)
 {
@@ -127,11 +86,7 @@ __global__ __launch_bounds__(kTileW *kTileH) void track_rgbd_prepare_kernel(Prep
     __shared__ float sI[kTileH + 2][kTileW + 2];
     __shared__ float sD[kTileH + 2][kTileW + 2];
     const int t = (int)threadIdx.x;
-    if (blockIdx.x == 0 && t == 0) {
-        for (int i = 0; i < 12; ++i) A.pose[i] = A.init[i];
-        A.status[0] = 0;
-        A.status[1] = -1;
-    }
+    if (blockIdx.x == 0 && t == 0) write_initial_state(A.pose, A.status, A.init);
     int l = 0;
     while (l + 1 < A.levels && (int)blockIdx.x >= A.tile0[l + 1]) ++l;
     const int hl = A.h >> l, wl = A.w >> l;
@@ -160,13 +115,12 @@ __global__ __launch_bounds__(kTileW *kTileH) void track_rgbd_prepare_kernel(Prep
     const int r = r0 + lr, c = c0 + lc;
     if (r >= hl || c >= wl) return;
     const size_t g = (size_t)A.off[l] + (size_t)r * wl + c;
+    const DepthSource S = {A.depth, A.mask, A.w, A.delta};
     float d, I;
-    switch (l) {
-    case 0: d = depth_value<0>(A, r, c); I = intensity_value<0>(A, r, c); break;
-    case 1: d = depth_value<1>(A, r, c); I = intensity_value<1>(A, r, c); break;
-    case 2: d = depth_value<2>(A, r, c); I = intensity_value<2>(A, r, c); break;
-    default: d = depth_value<3>(A, r, c); I = intensity_value<3>(A, r, c); break;
-    }
+    with_level(l, [&](auto lv) {
+        d = depth_pyramid_value<decltype(lv)::value>(S, r, c);
+        I = intensity_value<decltype(lv)::value>(A, r, c);
+    });
     A.dpyr[g] = d;
     A.ipyr[g] = I;
     if (!mcolor) return;
@@ -196,28 +150,9 @@ struct AssocArgs {
     double *rows;             // [blocks, 29]
     float *jr, *pjr;          // [h_l*w_l, 7] or NULL: the geometric and the (unscaled) photometric row
     uint8_t *reason, *preason;  // [h_l*w_l] or NULL
-    int h, w, npix;
-    float Ki[9];
-    float fx, fy, cx, cy;
-    float Rr[9], tr[3];
-    float dist2, cos_thr;
+    LevelCamera cam;
     float lambda, photo_thr;
 };
-
-__device__ __forceinline__ void ray_dc(const float Ki[9], int r, int c, float dc[3])
-{
-    const float cf = (float)c, rf = (float)r;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) dc[i] = Ki[3 * i] * cf + Ki[3 * i + 1] * rf + Ki[3 * i + 2];
-}
-
-__device__ __forceinline__ void vertex(const AssocArgs &A, int r, int c, float D, float V[3])
-{
-    float dc[3];
-    ray_dc(A.Ki, r, c, dc);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) V[i] = D * dc[i];
-}
 
 __device__ __forceinline__ float lerp2(float v00, float v01, float v10, float v11, float ax, float ay)
 {
@@ -231,11 +166,12 @@ __device__ void associate_pixel(const AssocArgs &A, const float R[9], const floa
                                 float &res, int &pwhy, float pJ[6], float &pres)
 {
     const bool photo = A.lambda != 0.0f;
-    const int r = pix / A.w, c = pix % A.w;
-    const bool edge = r + 1 >= A.h || c + 1 >= A.w;
+    const LevelCamera &C = A.cam;
+    const int r = pix / C.w, c = pix % C.w;
+    const bool edge = r + 1 >= C.h || c + 1 >= C.w;
     // the live loads, together
     const float D = A.D[pix];
-    const float Dd = edge ? 0.0f : A.D[pix + A.w], Dr = edge ? 0.0f : A.D[pix + 1];
+    const float Dd = edge ? 0.0f : A.D[pix + C.w], Dr = edge ? 0.0f : A.D[pix + 1];
     const float Il = A.I[pix];
     if (D == 0.0f) {
         why = 1;
@@ -243,62 +179,26 @@ __device__ void associate_pixel(const AssocArgs &A, const float R[9], const floa
         return;
     }
     float v[3];
-    vertex(A, r, c, D, v);
-    bool normal_ok = Dd != 0.0f && Dr != 0.0f;
+    vertex(C, r, c, D, v);
     float n[3] = {0.0f, 0.0f, 0.0f};
-    if (normal_ok) {
-        float vd[3], vr[3], a[3], b[3];
-        vertex(A, r + 1, c, Dd, vd);
-        vertex(A, r, c + 1, Dr, vr);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            a[i] = vd[i] - v[i];
-            b[i] = vr[i] - v[i];
-        }
-        const float x[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
-        const float xx = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
-        if (!(xx > 0.0f) || !isfinite(xx)) {
-            normal_ok = false;
-        } else {
-            const float xl = sqrtf(xx);
-            n[0] = x[0] / xl;
-            n[1] = x[1] / xl;
-            n[2] = x[2] / xl;
-        }
-    }
-    float p[3], nw[3], e[3], q[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        p[i] = R[3 * i] * v[0] + R[3 * i + 1] * v[1] + R[3 * i + 2] * v[2] + t[i];
-        nw[i] = R[3 * i] * n[0] + R[3 * i + 1] * n[1] + R[3 * i + 2] * n[2];
-        e[i] = p[i] - A.tr[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) q[i] = A.Rr[i] * e[0] + A.Rr[3 + i] * e[1] + A.Rr[6 + i] * e[2];
-    int stop = 0;
+    const bool normal_ok = Dd != 0.0f && Dr != 0.0f && live_normal(C, r, c, v, Dd, Dr, n);
+    float p[3], nw[3], q[3];
+    pose_transform(C, R, t, v, n, p, nw, q);
     float ux = 0.0f, uy = 0.0f, fc = 0.0f, fr = 0.0f;
-    if (!(q[2] > 0.0f)) {
-        stop = 3;
-    } else {
-        ux = A.fx * (q[0] / q[2]) + A.cx;
-        uy = A.fy * (q[1] / q[2]) + A.cy;
-        fc = floorf(ux + 0.5f);
-        fr = floorf(uy + 0.5f);
-        if (!(fc >= 0.0f && fc < (float)A.w && fr >= 0.0f && fr < (float)A.h)) stop = 4;
-    }
+    int stop = project(C, q, ux, uy, fc, fr);
     if (stop) {
         why = normal_ok ? stop : 2;
         pwhy = photo ? stop : 10;
         return;
     }
     // the model loads, together: depth, normal and the four records of the bilinear fetch hang on (ux, uy) alone
-    const int mc_ = (int)fc, mr = (int)fr;
-    const int mp = mr * A.w + mc_;
+    const int mc = (int)fc, mr = (int)fr;
+    const int mp = mr * C.w + mc;
     const float x0f = floorf(ux), y0f = floorf(uy);  // in [-1, w_l - 1] and [-1, h_l - 1] here
-    const bool inside = x0f >= 0.0f && x0f <= (float)(A.w - 2) && y0f >= 0.0f && y0f <= (float)(A.h - 2);
+    const bool inside = x0f >= 0.0f && x0f <= (float)(C.w - 2) && y0f >= 0.0f && y0f <= (float)(C.h - 2);
     const int x0 = inside ? (int)x0f : 0, y0 = inside ? (int)y0f : 0;
-    const int i00 = y0 * A.w + x0;
-    const int right = A.w > 1 ? 1 : 0, down = A.h > 1 ? A.w : 0;
+    const int i00 = y0 * C.w + x0;
+    const int right = C.w > 1 ? 1 : 0, down = C.h > 1 ? C.w : 0;
     const float dm = A.mdepth[mp];
     const float nm[3] = {A.mnormal[3 * (size_t)mp], A.mnormal[3 * (size_t)mp + 1], A.mnormal[3 * (size_t)mp + 2]};
     float4 c00 = {0, 0, 0, 0}, c01 = c00, c10 = c00, c11 = c00;
@@ -308,33 +208,18 @@ __device__ void associate_pixel(const AssocArgs &A, const float R[9], const floa
         c10 = A.mmap[i00 + down];
         c11 = A.mmap[i00 + down + right];
     }
+    float g[3];
     if (dm == 0.0f) {
         stop = 5;
+    } else if (!model_gap(C, p, mr, mc, dm, g)) {
+        stop = 6;
+    } else if (!normal_ok) {
+        why = 2;
+    } else if (!normals_agree(C, nw, nm)) {
+        why = 7;
     } else {
-        float mv[3], m[3];
-        vertex(A, mr, mc_, dm, mv);
-        float g[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            m[i] = A.Rr[3 * i] * mv[0] + A.Rr[3 * i + 1] * mv[1] + A.Rr[3 * i + 2] * mv[2] + A.tr[i];
-            g[i] = p[i] - m[i];
-        }
-        if (g[0] * g[0] + g[1] * g[1] + g[2] * g[2] > A.dist2) {
-            stop = 6;
-        } else if (!normal_ok) {
-            why = 2;
-        } else if (nw[0] * nm[0] + nw[1] * nm[1] + nw[2] * nm[2] < A.cos_thr) {
-            why = 7;
-        } else {
-            why = 0;
-            res = nm[0] * g[0] + nm[1] * g[1] + nm[2] * g[2];
-            J[0] = p[1] * nm[2] - p[2] * nm[1];
-            J[1] = p[2] * nm[0] - p[0] * nm[2];
-            J[2] = p[0] * nm[1] - p[1] * nm[0];
-            J[3] = nm[0];
-            J[4] = nm[1];
-            J[5] = nm[2];
-        }
+        why = 0;
+        plane_row(p, nm, g, J, res);
     }
     if (stop) {
         why = normal_ok ? stop : 2;
@@ -358,11 +243,11 @@ __device__ void associate_pixel(const AssocArgs &A, const float R[9], const floa
         pwhy = 9;
         return;
     }
-    const float a0 = A.fx * gx, a1 = A.fy * gy;
+    const float a0 = C.fx * gx, a1 = C.fy * gy;
     const float gc[3] = {a0 / q[2], a1 / q[2], -((a0 * q[0] + a1 * q[1]) / (q[2] * q[2]))};
     float a[3];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) a[i] = A.Rr[3 * i] * gc[0] + A.Rr[3 * i + 1] * gc[1] + A.Rr[3 * i + 2] * gc[2];
+    for (int i = 0; i < 3; ++i) a[i] = C.Rr[3 * i] * gc[0] + C.Rr[3 * i + 1] * gc[1] + C.Rr[3 * i + 2] * gc[2];
     pwhy = 0;
     pres = rI;
     pJ[0] = p[1] * a[2] - p[2] * a[1];
@@ -377,33 +262,18 @@ __global__ __launch_bounds__(kTrackThreads) void track_rgbd_associate_kernel(Ass
 {
     if (A.status[0] != 0) return;  // a failed step froze the pose: nothing more to do (uniform over the grid)
     float R[9], t[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) R[3 * i + k] = (float)A.pose[4 * i + k];
-        t[i] = (float)A.pose[4 * i + 3];
-    }
+    load_pose_f32(A.pose, R, t);
     double acc[kTrackTerms];
 #pragma unroll
     for (int e = 0; e < kTrackTerms; ++e) acc[e] = 0.0;
     for (int k = 0; k < kTrackPixPerThread; ++k) {
         const int pix = (int)blockIdx.x * kTrackPixPerBlock + k * kTrackThreads + (int)threadIdx.x;
-        if (pix >= A.npix) break;
+        if (pix >= A.cam.npix) break;
         float J[6] = {0, 0, 0, 0, 0, 0}, res = 0.0f, pJ[6] = {0, 0, 0, 0, 0, 0}, pres = 0.0f;
         int why = 0, pwhy = 0;
         associate_pixel(A, R, t, pix, why, J, res, pwhy, pJ, pres);
-        if (A.reason) A.reason[pix] = (uint8_t)why;
-        if (A.preason) A.preason[pix] = (uint8_t)pwhy;
-        if (A.jr) {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) A.jr[7 * (size_t)pix + i] = why ? 0.0f : J[i];
-            A.jr[7 * (size_t)pix + 6] = why ? 0.0f : res;
-        }
-        if (A.pjr) {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) A.pjr[7 * (size_t)pix + i] = pwhy ? 0.0f : pJ[i];
-            A.pjr[7 * (size_t)pix + 6] = pwhy ? 0.0f : pres;
-        }
+        export_row(A.reason, A.jr, pix, why, J, res);
+        export_row(A.preason, A.pjr, pix, pwhy, pJ, pres);
         if (!why) add_terms(acc, J, res);
         if (!pwhy) {
             float sJ[6];
@@ -416,23 +286,12 @@ __global__ __launch_bounds__(kTrackThreads) void track_rgbd_associate_kernel(Ass
     block_terms_to_row(acc, A.rows + (size_t)blockIdx.x * kTrackTerms);
 }
 
-static int level_blocks(int h, int w, int l) { return (((h >> l) * (w >> l)) + kTrackPixPerBlock - 1) / kTrackPixPerBlock; }
-
-static size_t total_pixels(int h, int w, int levels)
-{
-    size_t n = 0;
-    for (int l = 0; l < levels; ++l) n += (size_t)(h >> l) * (size_t)(w >> l);
-    return n;
-}
-
-static size_t pyramid_bytes(int h, int w, int levels) { return align256(total_pixels(h, w, levels) * sizeof(float)); }
 static size_t maps_bytes(int h, int w, int levels) { return align256(total_pixels(h, w, levels) * sizeof(float4)); }
 
 // depth pyramid | intensity pyramid | model maps | block rows | 256 bytes (the probe's stats row)
 static size_t workspace_bytes(int h, int w, int levels)
 {
-    return 2 * pyramid_bytes(h, w, levels) + maps_bytes(h, w, levels) +
-           align256((size_t)level_blocks(h, w, 0) * kTrackTerms * sizeof(double)) + 256;
+    return 2 * pyramid_bytes(h, w, levels) + maps_bytes(h, w, levels) + rows_bytes(h, w);
 }
 
 static double *rows_of(void *ws, int h, int w, int levels)
@@ -440,20 +299,10 @@ static double *rows_of(void *ws, int h, int w, int levels)
     return (double *)((char *)ws + 2 * pyramid_bytes(h, w, levels) + maps_bytes(h, w, levels));
 }
 
-static int check_shape(const char *who, int h, int w, int levels)
-{
-    if (levels < 1 || levels > OJF_TRACK_MAX_LEVELS) return fail(std::string(who) + ": levels must be 1..OJF_TRACK_MAX_LEVELS");
-    if (h <= 0 || w <= 0 || (int64_t)h * w > 0x3fffffffLL) return fail(std::string(who) + ": bad image size");
-    if ((h >> (levels - 1)) < 8 || (w >> (levels - 1)) < 8)
-        return fail(std::string(who) + ": every level must be at least 8 x 8 pixels");
-    return 0;
-}
-
 static int check_thresholds(const char *who, double dist, double angle, double delta, double frac, double weight,
                             double photo, double grad)
 {
-    if (!(dist > 0.0) || !isfinite(dist) || !(angle > 0.0) || !(angle <= 180.0) || !(delta >= 0.0) || !isfinite(delta) ||
-        !(frac >= 0.0) || !(frac <= 1.0) || !(photo >= 0.0) || !isfinite(photo) || !(grad > 0.0) || !isfinite(grad))
+    if (!thresholds_in_range(dist, angle, delta, frac) || !(photo >= 0.0) || !isfinite(photo) || !(grad > 0.0) || !isfinite(grad))
         return fail(std::string(who) + ": thresholds out of range");
     if (!(weight >= 0.0) || !isfinite(weight)) return fail(std::string(who) + ": photo_weight must be finite and >= 0");
     return 0;
@@ -492,19 +341,7 @@ static void fill_assoc(AssocArgs &A, const PrepArgs &P, int l, const double *K, 
     A.mmap = P.maps + P.off[l];
     A.mdepth = mdepth; A.mnormal = mnormal; A.pose = pose; A.status = status; A.rows = rows;
     A.jr = A.pjr = nullptr; A.reason = A.preason = nullptr;
-    A.h = P.h >> l; A.w = P.w >> l; A.npix = A.h * A.w;
-    for (int i = 0; i < 9; ++i) A.Ki[i] = Ki[i];
-    const double s = (double)(1 << l);
-    A.fx = (float)(K[0] / s);
-    A.fy = (float)(K[4] / s);
-    A.cx = (float)((K[2] + 0.5) / s - 0.5);
-    A.cy = (float)((K[5] + 0.5) / s - 0.5);
-    for (int i = 0; i < 3; ++i) {
-        for (int k = 0; k < 3; ++k) A.Rr[3 * i + k] = (float)Eref[4 * i + k];
-        A.tr[i] = (float)Eref[4 * i + 3];
-    }
-    A.dist2 = (float)(dist * dist);
-    A.cos_thr = (float)cos(angle * M_PI / 180.0);
+    fill_camera(A.cam, P.h, P.w, l, K, Ki, Eref, dist, angle);
     A.lambda = (float)weight;
     A.photo_thr = (float)photo;
 }
@@ -516,11 +353,11 @@ static int launch_prepare(const PrepArgs &P, hipStream_t s)
     return 0;
 }
 
-static int launch_step(const AssocArgs &A, const SolveArgs &S, hipStream_t s)
+static int launch_associate(const AssocArgs &A, int blocks, hipStream_t s)
 {
-    hipLaunchKernelGGL(track_rgbd_associate_kernel, dim3(S.nblocks), dim3(kTrackThreads), 0, s, A);
+    hipLaunchKernelGGL(track_rgbd_associate_kernel, dim3(blocks), dim3(kTrackThreads), 0, s, A);
     OJF_HIP(hipGetLastError());
-    return launch_solve(S, s);
+    return 0;
 }
 
 }  // namespace rgbd
@@ -529,8 +366,7 @@ static int launch_step(const AssocArgs &A, const SolveArgs &S, hipStream_t s)
 OJF_API size_t ojf_track_rgbd_workspace_bytes(int h, int w, int levels)
 {
     using namespace ojf;
-    if (levels < 1 || levels > OJF_TRACK_MAX_LEVELS || h <= 0 || w <= 0 || (int64_t)h * w > 0x3fffffffLL) return 0;
-    return rgbd::workspace_bytes(h, w, levels);
+    return sizable(h, w, levels) ? rgbd::workspace_bytes(h, w, levels) : 0;
 }
 
 OJF_API int ojf_track_rgbd(const float *depth_dev, const uint8_t *mask_dev, const uint8_t *image_dev, int h, int w,
@@ -547,43 +383,29 @@ OJF_API int ojf_track_rgbd(const float *depth_dev, const uint8_t *mask_dev, cons
     if (!depth_dev || !image_dev || !K_host || !Kinv_host || !model_depth_host || !model_normals_host || !model_color_host ||
         !E_ref_host || !E_init_host || !iterations_host || !workspace_dev || !pose_dev || !stats_dev || !status_dev)
         return fail("ojf_track_rgbd: null pointer argument");
-    if (int rc = rgbd::check_shape("ojf_track_rgbd", h, w, levels)) return rc;
-    int total = 0;
-    for (int l = 0; l < levels; ++l) {
-        if (!model_depth_host[l] || !model_normals_host[l] || !model_color_host[l])
-            return fail("ojf_track_rgbd: null pointer argument (model maps)");
-        if (iterations_host[l] < 0) return fail("ojf_track_rgbd: negative iteration count");
-        total += iterations_host[l];
-        if (total > OJF_TRACK_MAX_ITERATIONS) return fail("ojf_track_rgbd: more than OJF_TRACK_MAX_ITERATIONS iterations");
-    }
-    if (int rc = rgbd::check_thresholds("ojf_track_rgbd", dist_thresh, angle_thresh_deg, pyramid_delta, min_inlier_fraction,
-                                        photo_weight, photo_thresh, grad_depth_limit))
+    if (int rc = check_shape("ojf_track_rgbd", h, w, levels)) return rc;
+    if (int rc = check_schedule("ojf_track_rgbd", levels, iterations_host, model_depth_host, model_normals_host,
+                                model_color_host))
         return rc;
-    if (workspace_bytes_ < rgbd::workspace_bytes(h, w, levels)) return fail("ojf_track_rgbd: workspace too small");
+    if (int rc = check_thresholds("ojf_track_rgbd", dist_thresh, angle_thresh_deg, pyramid_delta, min_inlier_fraction,
+                                  photo_weight, photo_thresh, grad_depth_limit))
+        return rc;
+    if (workspace_bytes_ < workspace_bytes(h, w, levels)) return fail("ojf_track_rgbd: workspace too small");
     const hipStream_t s = as_stream(stream);
     PrepArgs P;
     fill_prepare(P, depth_dev, mask_dev, image_dev, workspace_dev, h, w, levels, pyramid_delta, grad_depth_limit, pose_dev,
                  status_dev, E_init_host);
+    double *rows = rows_of(workspace_dev, h, w, levels);
+    AssocArgs A[OJF_TRACK_MAX_LEVELS];
     for (int l = 0; l < levels; ++l) {
         P.mdepth[l] = model_depth_host[l];
         P.mcolor[l] = (const uint32_t *)model_color_host[l];
+        fill_assoc(A[l], P, l, K_host, Kinv_host + 9 * l, model_depth_host[l], model_normals_host[l], E_ref_host, dist_thresh,
+                   angle_thresh_deg, photo_weight, photo_thresh, pose_dev, status_dev, rows);
     }
-    double *rows = rows_of(workspace_dev, h, w, levels);
     if (int rc = launch_prepare(P, s)) return rc;
-    int iter = 0;
-    for (int l = levels - 1; l >= 0; --l) {
-        rgbd::AssocArgs A;
-        rgbd::fill_assoc(A, P, l, K_host, Kinv_host + 9 * l, model_depth_host[l], model_normals_host[l], E_ref_host,
-                         dist_thresh, angle_thresh_deg, photo_weight, photo_thresh, pose_dev, status_dev, rows);
-        SolveArgs S;
-        fill_solve(S, rows, rgbd::level_blocks(h, w, l), pose_dev, status_dev, stats_dev, nullptr, 0,
-                   min_inlier_fraction * (double)A.npix, E_init_host);
-        for (int k = 0; k < iterations_host[l]; ++k) {
-            S.iter = iter++;
-            if (int rc = rgbd::launch_step(A, S, s)) return rc;
-        }
-    }
-    return 0;
+    return run_steps(h, w, levels, iterations_host, min_inlier_fraction, rows, pose_dev, status_dev, stats_dev, nullptr,
+                     E_init_host, s, [&](int l, int blocks) { return launch_associate(A[l], blocks, s); });
 }
 
 OJF_API int ojf_track_rgbd_associate(const float *depth_dev, const uint8_t *mask_dev, const uint8_t *image_dev, int h, int w,
@@ -603,11 +425,11 @@ OJF_API int ojf_track_rgbd_associate(const float *depth_dev, const uint8_t *mask
         return fail("ojf_track_rgbd_associate: null pointer argument");
     if (level < 0) return fail("ojf_track_rgbd_associate: levels must be 1..OJF_TRACK_MAX_LEVELS");
     const int levels = level + 1;
-    if (int rc = rgbd::check_shape("ojf_track_rgbd_associate", h, w, levels)) return rc;
-    if (int rc = rgbd::check_thresholds("ojf_track_rgbd_associate", dist_thresh, angle_thresh_deg, pyramid_delta,
-                                        min_inlier_fraction, photo_weight, photo_thresh, grad_depth_limit))
+    if (int rc = check_shape("ojf_track_rgbd_associate", h, w, levels)) return rc;
+    if (int rc = check_thresholds("ojf_track_rgbd_associate", dist_thresh, angle_thresh_deg, pyramid_delta,
+                                  min_inlier_fraction, photo_weight, photo_thresh, grad_depth_limit))
         return rc;
-    if (workspace_bytes_ < rgbd::workspace_bytes(h, w, levels)) return fail("ojf_track_rgbd_associate: workspace too small");
+    if (workspace_bytes_ < workspace_bytes(h, w, levels)) return fail("ojf_track_rgbd_associate: workspace too small");
     const hipStream_t s = as_stream(stream);
     PrepArgs P;
     fill_prepare(P, depth_dev, mask_dev, image_dev, workspace_dev, h, w, levels, pyramid_delta, grad_depth_limit, pose_dev,
@@ -615,17 +437,17 @@ OJF_API int ojf_track_rgbd_associate(const float *depth_dev, const uint8_t *mask
     P.mdepth[level] = model_depth_dev;
     P.mcolor[level] = (const uint32_t *)model_color_dev;
     double *rows = rows_of(workspace_dev, h, w, levels);
-    double *stats = (double *)((char *)workspace_dev + rgbd::workspace_bytes(h, w, levels) - 256);  // the stats row goes to the scratch tail
-    rgbd::AssocArgs A;
-    rgbd::fill_assoc(A, P, level, K_host, Kinv_host, model_depth_dev, model_normals_dev, E_ref_host, dist_thresh,
-                     angle_thresh_deg, photo_weight, photo_thresh, pose_dev, status_dev, rows);
+    double *stats = (double *)((char *)workspace_dev + workspace_bytes(h, w, levels) - 256);  // the stats row goes to the scratch tail
+    AssocArgs A;
+    fill_assoc(A, P, level, K_host, Kinv_host, model_depth_dev, model_normals_dev, E_ref_host, dist_thresh, angle_thresh_deg,
+               photo_weight, photo_thresh, pose_dev, status_dev, rows);
     A.jr = jr_dev;
     A.reason = reason_dev;
     A.pjr = photo_jr_dev;
     A.preason = photo_reason_dev;
-    SolveArgs S;
-    fill_solve(S, rows, rgbd::level_blocks(h, w, level), pose_dev, status_dev, stats, sums_dev, 0,
-               min_inlier_fraction * (double)A.npix, E_pose_host);
+    int one_step[OJF_TRACK_MAX_LEVELS] = {};
+    one_step[level] = 1;
     if (int rc = launch_prepare(P, s)) return rc;
-    return rgbd::launch_step(A, S, s);
+    return run_steps(h, w, levels, one_step, min_inlier_fraction, rows, pose_dev, status_dev, stats, sums_dev, E_pose_host, s,
+                     [&](int, int blocks) { return launch_associate(A, blocks, s); });
 }

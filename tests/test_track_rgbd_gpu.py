@@ -15,6 +15,7 @@ from online_joint_depthfusion_and_semantic_amd.ops import camera_arrays
 from online_joint_depthfusion_and_semantic_amd.render import render_views
 from online_joint_depthfusion_and_semantic_amd.tracking import level_intrinsics, pose12, track_frame, track_frame_rgbd
 from render_ref import plane_case
+from test_track_gpu import _associate
 import color_ref
 import track_ref
 import track_rgbd_ref as ref
@@ -160,6 +161,31 @@ def test_one_step_is_the_restatement(cuda, h, w, levels):
     out = _step(cuda, dev, case, 0, case['pose'], weight=0.0)
     a = _check_step(out, case, 0, case['pose'], '%dx%d, photo_weight 0' % (h, w), weight=0.0)
     assert (a['preason'] == 10).all() and out['sums'][28] == (a['reason'] == 0).sum()
+
+
+@pytest.mark.parametrize('h,w,levels', [(25, 41, 1), (67, 93, 3)])
+def test_one_step_at_photo_weight_0_is_ojf_track_associate(cuda, h, w, levels):
+    """The front half the two trackers share (csrc/ojf_track_front.h), seen at step level: from the same pose,
+    ojf_track_associate and ojf_track_rgbd_associate at photo_weight 0 leave the same bits in everything both export, at
+    every level.  1025 pixels (a block of one pixel) and odd halves with cut tiles; at level 0 the inputs reach every
+    geometric reason (track_ref.associate counts 26, 532, 395, 14, 46, 2, 2, 8 of reasons 0..7 at 25x41 and 238, 3027,
+    2373, 88, 356, 9, 21, 119 at 67x93; the coarser levels of 67x93 lack some)."""
+    case = ref.hostile_case(h, w, levels)
+    dev = _upload(cuda, case)
+    for l in range(levels):
+        what = '%dx%d level %d' % (h, w, l)
+        both = _step(cuda, dev, case, l, case['pose'], weight=0.0)
+        depth_only = _associate(cuda, case['depth'], case['mask'], l, case['K'], case['Kinv'][l], dev['mdepth'][l],
+                                dev['mnormal'][l], case['E_ref'], case['pose'])
+        for k in range(l + 1):
+            _same_bits(both['dpyr'][k], depth_only['pyr'][k], '%s: depth pyramid level %d' % (what, k))
+        for k in ('J', 'r', 'reason', 'sums', 'pose', 'status'):
+            _same_bits(both[k], depth_only[k], '%s: %s' % (what, k))
+        assert (both['preason'] == 10).all(), what
+        counts = np.bincount(depth_only['reason'].reshape(-1), minlength=8)
+        print(what, 'geometric', counts.tolist())
+        if l == 0:
+            assert len(counts) == 8 and (counts > 0).all(), (what, counts)
 
 
 # ---- the whole call
