@@ -241,6 +241,27 @@ int ojf_entry_gemm(const float *weight_host, const float *bias_host, int c_in_ph
                    int c4_in, int npix, float *out_dev, int og_store, int split_groups, int act_n, void *colsums_dev, int form,
                    int max_blocks, ojf_stream_t stream);
 
+/* Test entry point: one launch of the fused VortexPooling tail in split-fp16 arithmetic (vortex_tail_kernel), on caller-supplied branch
+ * planes and raw fp32 layers, which the call packs as the net does; it runs the launch and synchronises `stream`.
+ *   t_b = ReLU(w1[b] v_b + b1[b]), y = bf + sum_b wf[:, b*c_out .. (b+1)*c_out) t_b     (b < 4)
+ * w1_host [4][c_out][c], b1_host [4][c_out], wf_host [c_out][4*c_out], bf_host [c_out]; c <= 32 branch channels, 113 <= c_out <= 128.
+ * v_dev: planes [4 branches][c4 groups][npix] float4 (4*c4 >= c, c4 <= 8), 16-byte aligned; the float4 in front of v_dev must be readable
+ * and zero (what lanes outside the frame read).  y is never written; what rides along is:
+ * kind 1, the next VortexPooling's entry GEMM: next_w_host [4*cs][c_out], next_b_host [4*cs], next_dims_host = {cs}; out_dev: planes, groups
+ *   < og_store (<= cs) of the 5 * 4 computed are written, ReLU on channels < act_n, groups < split_groups as split planes; colsums_dev
+ *   (int64 fix[16][256], then uint32 bad[256], see ojf_entry_gemm) gets the channel sums of y added.  rows_stride, rows_n, scale: unused.
+ * kind 19, the prediction head: next_dims_host = the 12 channel counts of its 11 pointwise layers (next_dims_host[0] = c_out; in tiles of
+ *   16 after rounding up to 4: 8-6-6-5-5-4-4-3-3-2-2-1), next_w_host the layers [c_l+1][c_l] back to back, next_b_host their biases back to
+ *   back; LeakyReLU(0.01) between them, out_dev[p * rows_stride + o] = tanh(last layer) * scale for o < rows_n.  og_store, split_groups,
+ *   act_n, colsums_dev: unused.
+ * form: 1 = the kernel the net launches (branch b + 1's planes requested during branch b, DPP channel sums), 0 = planes requested at
+ * each branch's head and __shfl_xor channel sums; both give the same bits.
+ * A pre-activation beyond the fp16 range raises the process-wide range guard (ojf_net_check). */
+int ojf_vortex_tail(int kind, const float *w1_host, const float *b1_host, const float *wf_host, const float *bf_host, int c, int c_out,
+                    const float *next_w_host, const float *next_b_host, const int *next_dims_host, const float *v_dev, int c4, int npix,
+                    float *out_dev, int og_store, int split_groups, int act_n, void *colsums_dev, int rows_stride, int rows_n,
+                    float scale, int form, ojf_stream_t stream);
+
 /* ---- SEGCONV: convolutions of the 2-D semantic front-end (AdapNet++) ---------------------------
  * One prepacked layer = nn.Conv2d (groups 1, square kernel <= 7, any stride / dilation / zero padding) with what
  * follows it in modules/adapnet.py folded in: eval-mode BatchNorm as scale_host[c_out] (multiplied into the weights)

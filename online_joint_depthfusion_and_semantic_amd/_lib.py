@@ -112,6 +112,9 @@ SIGNATURES = {
     'ojf_pool_pyramid': (_i, [_vp] * 10 + [_i] * 4 + [_vp] * 5 + [_i, _i, _vp, _i, _vp]),
     # weight, bias, c_in_phys, cs, in, in_split, c4_in, npix, out, og_store, split_groups, act_n, colsums, form, max_blocks, stream
     'ojf_entry_gemm': (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp]),
+    # kind, w1, b1, wf, bf, c, c_out, next_w, next_b, next_dims, v, c4, npix, out, og_store, split_groups, act_n, colsums, rows_stride,
+    # rows_n, scale, form, stream
+    'ojf_vortex_tail': (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _f, _i, _vp]),
     'ojf_conv2d': (_i, [_vp, _i, _i, _vp, _i, _i, _c.POINTER(ConvLayer), _i, _i, _i, _vp]),
     'ojf_volume_fill_f16': (_i, [_vp, _sz, _f, _vp]),
     'ojf_volume_fill_u8': (_i, [_vp, _sz, _c.c_uint8, _vp]),

@@ -966,11 +966,12 @@ __device__ __forceinline__ const f32x4 *vec_commit(VecStage &vs, int n)
 // `pre` carries the weights of this layer's first part on entry (already fetched from HBM/L2 while the
 // previous part computed) and the next layer's first part on exit: global latency never sits between two
 // compute phases, only the two barriers around the LDS refill do.
-template <int ARITH, int MT, int NTIN, int NTOUT, int MODE, int NEXT_FIRST, int NA, int NB>
+struct ChainNoHook { __device__ __forceinline__ void operator()() const {} };
+template <int ARITH, int MT, int NTIN, int NTOUT, int MODE, int NEXT_FIRST, int NA, int NB, class HOOK = ChainNoHook>
 __device__ __forceinline__ void chain_layer(const f32x4 (&in)[MT][NA], f32x4 (&out)[MT][NB], f32x4 *wlds, const f32x4 *wg,
                                             const ChainArgs &a, const int (&p)[MT], int lane,
                                             f32x4 (&pre)[kChainPre], int &buf, VecStage &vs, const VecNext nx = VecNext(),
-                                            const f32x4 *next_src = nullptr, int commit_extra = 0)
+                                            const f32x4 *next_src = nullptr, int commit_extra = 0, HOOK hook = HOOK())
 {
     static_assert(NTIN <= NA && NTOUT <= NB, "register arrays too small for this layer");
     // this layer's epilogue vectors (issued one layer ago) go to LDS now; an accumulating layer may carry the vectors of
@@ -1012,6 +1013,7 @@ __device__ __forceinline__ void chain_layer(const f32x4 (&in)[MT][NA], f32x4 (&o
             buf ^= 1;
             dma_part(nsrc, wlds + buf * chain_cap(ARITH), nsize, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane);
             if (part == 0) vec_issue(vs, nx);
+            if (part == 0) hook();  // (requests of the caller's that are to travel behind the layer's first barrier)
         } else {
             __syncthreads();  // readers of the previous part are done
 #pragma unroll
@@ -1022,6 +1024,7 @@ __device__ __forceinline__ void chain_layer(const f32x4 (&in)[MT][NA], f32x4 (&o
             for (int k = 0; k < kChainPre; ++k)
                 if ((int)threadIdx.x + kChainThreads * k < nsize) pre[k] = nsrc[threadIdx.x + kChainThreads * k];
             if (part == 0) vec_issue(vs, nx);
+            if (part == 0) hook();  // (requests of the caller's that are to travel behind the layer's first barrier)
         }
         if constexpr (MODE != kChainAccumulate) {
 #pragma unroll
@@ -1121,6 +1124,25 @@ __device__ __forceinline__ void chain_layer(const f32x4 (&in)[MT][NA], f32x4 (&o
     }
 }
 
+#ifdef OJF_TAIL_STAMPS  // profiling build only (tools/tail_stamps.py): phase stamps of the fused tails' blocks, thread 0
+// [launch kind: 0 = tail + entry layer (or alone), 1 = tail + head][block][slot]: clock64 at 0 block start; for branch b at 1 + 3b inputs
+// landed (the profiling build's own vmcnt(0) in front of the closing 1x1: the wave's planes AND its chunks of the weight part), 2 + 3b closing
+// 1x1 done, 3 + 3b accumulation done; 13 final epilogue done, 14 channel sums done (tail + entry), 15 fused entry layer / head done; 100-MHz
+// wall clock at 16 block start, 17 block end; 18 = block index + 1; 100-MHz wall clock at 20 + l: layer l < 11 of the prediction head done (chain_run).  The stamps
+// of the LAST launch of each kind remain.
+constexpr int kTailStampBlocks = 8192, kTailStampSlots = 32;
+__device__ unsigned long long g_tail_stamps[2][kTailStampBlocks][kTailStampSlots];
+#define TAIL_STAMP(kind, i, v)                                                                                                 \
+    do {                                                                                                                       \
+        if (threadIdx.x == 0 && blockIdx.x < (unsigned)kTailStampBlocks)                                                       \
+            g_tail_stamps[kind][blockIdx.x][i] = (i) == 18 ? (unsigned long long)(v) : ((i) >= 16 ? wall_clock64() : clock64()); \
+    } while (0)
+#define TAIL_STAMP_LANDED() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")  // "inputs landed" has to wait for them
+#else
+#define TAIL_STAMP(kind, i, v) do { } while (0)
+#define TAIL_STAMP_LANDED() do { } while (0)
+#endif
+
 // layer l reads `x` and writes `y`; the recursion swaps the two arrays for layer l+1
 template <int ARITH, int MT, int NTIN, int NTOUT>
 __device__ __forceinline__ void chain_run(f32x4 (&x)[MT][8], f32x4 (&y)[MT][8], f32x4 *wlds, const f32x4 *wg,
@@ -1128,6 +1150,7 @@ __device__ __forceinline__ void chain_run(f32x4 (&x)[MT][8], f32x4 (&y)[MT][8], 
                                           f32x4 (&pre)[kChainPre], int &buf, VecStage &vs)
 {
     chain_layer<ARITH, MT, NTIN, NTOUT, kChainLastRows, 0>(x, y, wlds, wg, a, p, lane, pre, buf, vs);
+    TAIL_STAMP(1, 30, 0);  // (chain_run serves the tails' prediction head only: 11 layers, this one the last)
 }
 
 template <int ARITH, int MT, int NTIN, int NTOUT, int NTNEXT, int... REST>
@@ -1141,6 +1164,7 @@ __device__ __forceinline__ void chain_run(f32x4 (&x)[MT][8], f32x4 (&y)[MT][8], 
     nx.na = chain_bias_stride(ARITH, NTNEXT) / 4;
     chain_layer<ARITH, MT, NTIN, NTOUT, kChainLeaky, chain_first_size(ARITH, NTOUT, NTNEXT)>(x, y, wlds, wg, a, p, lane, pre,
                                                                                              buf, vs, nx);
+    TAIL_STAMP(1, 29 - (int)sizeof...(REST), 0);  // layer 9 - sizeof...(REST) of the head's 11
     chain_run<ARITH, MT, NTOUT, NTNEXT, REST...>(y, x, wlds, wg + (size_t)chain_layer_size(ARITH, NTIN, NTOUT),
                                                  bias + chain_bias_stride(ARITH, NTOUT), a, p, lane, pre, buf, vs);
 }
@@ -1497,11 +1521,38 @@ __device__ __forceinline__ void head_run(f32x4 (&x)[MT][8], f32x4 (&y)[MT][8], f
 constexpr int head_first_ntout(int kind) { return kind == 19 ? 6 : 7; }
 constexpr int head_first_size(int arith, int kind) { return chain_first_size(arith, 8, kind == 19 ? 6 : 7); }
 
+// When a block asks for its branch inputs.  They are cold (written by the grouped 3x3 launch just before, on other XCDs), and every
+// chain_layer part begins with a full vmcnt wait and a barrier, so a request at a branch's head is a global round trip the block sits
+// out at once - four per block.  kTailNext: branch b + 1's planes are requested behind the first barrier of branch b's closing 1x1 and
+// land under that branch's parts (8 more VGPRs, still three blocks per CU), and the butterfly of the fused entry layer's channel sums
+// runs on DPP moves.  kTailAtBranch: the requests at each branch's head and the __shfl_xor butterfly - the same arithmetic and the same
+// bits, kept for ojf_vortex_tail's form 0 (tests) and the profiling build.  Where the time of a block goes in either form, and the form
+// with all four branches requested at block start that was not kept: profiles/vortex_tail_block_life.txt.
+constexpr int kTailAtBranch = 0, kTailNext = 1;
+
+// the planes of branch b for this wave's pixels (lanes outside the frame or the branch's groups read the zero float4 in front of the planes)
+template <int MT, int NV>
+__device__ __forceinline__ void tail_load_branch(f32x4 (&vin)[MT][NV], const TailArgs &a, int b, const int (&p)[MT], int g)
+{
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int S = 0; S < NV; ++S) {
+            const int G = 4 * S + g;
+            const bool ok = p[m] < a.npix && G < a.c4;
+            vin[m][S] = a.v[b][ok ? G * a.npix + p[m] : -1];
+        }
+}
+
 // CHAIN = 0: write the VortexPooling result planes.  CHAIN = 19 / 20: feed it straight into the prediction head
 // (same accumulator -> operand identity) and write est rows; the 114-channel tensor between them never exists.
-template <int ARITH, int MT, int NV, int NO, int CHAIN = 0>
+template <int ARITH, int MT, int NV, int NO, int CHAIN = 0, int FORM = kTailNext>
 __global__ __launch_bounds__(kChainThreads, kChainBlocks) void vortex_tail_kernel(const TailArgs a)
 {
+    [[maybe_unused]] constexpr int kStampKind = CHAIN > kTailEntry ? 1 : 0;
+    TAIL_STAMP(kStampKind, 16, 0);
+    TAIL_STAMP(kStampKind, 0, 0);
+    TAIL_STAMP(kStampKind, 18, blockIdx.x + 1);
     static_assert(CHAIN == 0 || NO == 8, "the fused prediction head / entry layer expects 8 input tiles");
     __shared__ f32x4 wlds[chain_dma(ARITH) ? 2 * kChainDmaHalf : kChainLdsFloat4];
     __shared__ f32x4 vec_lds[2 * kVecF4];
@@ -1544,17 +1595,13 @@ __global__ __launch_bounds__(kChainThreads, kChainBlocks) void vortex_tail_kerne
     constexpr size_t per_branch = (size_t)chain_layer_size(ARITH, NV, NO) + chain_layer_size(ARITH, NO, NO);
     f32x4 t[MT][NO];
     const f32x4 *vfin = vec_lds;
+    f32x4 vin[4][MT][NV];
+    if constexpr (FORM == kTailNext) tail_load_branch(vin[0], a, 0, p, g);
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-        f32x4 vin[MT][NV];
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int S = 0; S < NV; ++S) {
-                const int G = 4 * S + g;
-                const bool ok = p[m] < a.npix && G < a.c4;
-                vin[m][S] = a.v[b][ok ? G * a.npix + p[m] : -1];
-            }
+        if constexpr (FORM == kTailAtBranch) tail_load_branch(vin[b], a, b, p, g);
+        TAIL_STAMP_LANDED();
+        TAIL_STAMP(kStampKind, 1 + 3 * b, 0);
         const f32x4 *w1 = a.w + b * per_branch, *wf = w1 + (size_t)chain_layer_size(ARITH, NV, NO);
         VecNext nx;  // what travels during this branch's closing 1x1
         if (b < 3) {
@@ -1563,7 +1610,15 @@ __global__ __launch_bounds__(kChainThreads, kChainBlocks) void vortex_tail_kerne
             nx.a = a.bias_final; nx.na = NO * 4;
             if constexpr (ARITH == OJF_ARITH_F16X3) { nx.b = a.rinv_final; nx.nb = NO * 4; }
         }
-        chain_layer<ARITH, MT, NV, NO, kChainRelu, chain_first_size(ARITH, NO, NO)>(vin, t, wlds, w1, ca, p, lane, pre, buf, vs, nx);
+        // kTailNext: the next branch's planes are requested behind this layer's first barrier (chain_layer's hook); none after the last
+        constexpr int kLast = 3;
+        const int bn = b < kLast ? b + 1 : kLast;
+        auto next_planes = [&]() {
+            if (FORM == kTailNext && b < kLast) tail_load_branch(vin[bn], a, bn, p, g);
+        };
+        chain_layer<ARITH, MT, NV, NO, kChainRelu, chain_first_size(ARITH, NO, NO)>(vin[b], t, wlds, w1, ca, p, lane, pre, buf, vs, nx,
+                                                                                    nullptr, 0, next_planes);
+        TAIL_STAMP(kStampKind, 2 + 3 * b, 0);
         if (b < 3) {
             chain_layer<ARITH, MT, NO, NO, kChainAccumulate, chain_first_size(ARITH, NV, NO)>(t, y, wlds, wf, ca, p, lane, pre, buf, vs);
         } else {
@@ -1575,6 +1630,7 @@ __global__ __launch_bounds__(kChainThreads, kChainBlocks) void vortex_tail_kerne
                         CHAIN == kTailEntry ? chain_first_size(ARITH, 8, 5) : (CHAIN ? head_first_size(ARITH, CHAIN) : 0)>(
                 t, y, wlds, wf, ca, p, lane, pre, buf, vs, nf, CHAIN == kTailEntry ? a.entry_w : a.chain_w, kVecFin);
         }
+        TAIL_STAMP(kStampKind, 3 + 3 * b, 0);
     }
     float gmax = 0.0f;
 #pragma unroll
@@ -1592,14 +1648,19 @@ __global__ __launch_bounds__(kChainThreads, kChainBlocks) void vortex_tail_kerne
     }
     if constexpr (ARITH == OJF_ARITH_F16X3)
         if (gmax > 65504.0f && a.ovf) guard_raise(a.ovf, 1);
+    TAIL_STAMP(kStampKind, 13, 0);
     if constexpr (CHAIN == kTailEntry) {
-        block_colsum<MT, NO>(y, p, a.npix, red, a.colsum, lane, wave, a.colsum_off);
+        // (the butterfly by DPP moves: 128 ds_bpermute per wave through the LDS crossbar otherwise, see entry1x1_persistent_kernel)
+        block_colsum<MT, NO, FORM != kTailAtBranch>(y, p, a.npix, red, a.colsum, lane, wave, a.colsum_off);
+        TAIL_STAMP(kStampKind, 14, 0);
         ca.out_planes = a.entry_out; ca.out_g0 = 0; ca.og_store = a.entry_og; ca.act_n = a.entry_act_n; ca.split_groups = a.entry_split;
         chain_layer<ARITH, MT, 8, 5, kChainEntry, 0>(y, t, wlds, a.entry_w, ca, p, lane, pre, buf, vs);
     } else if constexpr (CHAIN) {
         ca.out_rows = a.out_rows; ca.rows_stride = a.rows_stride; ca.rows_n = a.rows_n; ca.scale = a.scale;
         head_run<ARITH, MT, CHAIN>(y, t, wlds, a.chain_w, a.chain_b, ca, p, lane, pre, buf, vs);
     }
+    TAIL_STAMP(kStampKind, 15, 0);
+    TAIL_STAMP(kStampKind, 17, 0);
 }
 
 // Pool pyramid of a VortexPooling (model.py:143-155): branch b = 1..3 sees its entry-conv pre-activation pooled b
@@ -3129,6 +3190,11 @@ static void launch_entry_persistent(const ChainArgs &ea, int strips, int max_blo
 // One VortexPooling as its step of the plan says.  Steps 0 / 1 read their head's dense-growth buffer and write (where the tail
 // carries nothing along) their slot of YY; the last one reads YY and writes Y3.  `head`: the prediction head's arguments, for
 // the tail that runs it.
+#ifdef OJF_TAIL_STAMPS  // profiling build only: which form of the two headline tails the forward pass launches (tools/tail_stamps.py)
+static int g_tail_stamp_form = ojf::kTailNext;
+static int tail_stamp_form() { return g_tail_stamp_form; }
+#endif
+
 static int run_vortex(ojf_net *net, const VortexStep &s, hipStream_t st, const ChainArgs &head)
 {
     const int h = net->h, w = net->w, c4 = net->cs / 4, o4 = net->os / 4;
@@ -3243,6 +3309,11 @@ static int run_vortex(ojf_net *net, const VortexStep &s, hipStream_t st, const C
         name = L_TAIL_HEAD;
         ta.chain_w = head.w; ta.chain_b = head.bias; ta.out_rows = head.out_rows;
         ta.rows_stride = head.rows_stride; ta.rows_n = head.rows_n; ta.scale = head.scale;
+#ifdef OJF_TAIL_STAMPS
+        if (net->plan.chain_kind == 19 && h16 && tail_stamp_form() == ojf::kTailAtBranch)
+            hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F16X3, 1, 2, 8, 19, ojf::kTailAtBranch>), grid, block, 0, st, ta);
+        else
+#endif
         if (net->plan.chain_kind == 19) OJF_LAUNCH_BY_ARITH(vortex_tail_kernel, ta, 1, 2, 8, 19);
         else OJF_LAUNCH_BY_ARITH(vortex_tail_kernel, ta, 1, 2, 8, 20);
         break;
@@ -3261,6 +3332,11 @@ static int run_vortex(ojf_net *net, const VortexStep &s, hipStream_t st, const C
         ta.entry_w = planes(next.entry_w); ta.entry_b = next.entry_b; ta.entry_out = planes(sc.Z);
         ta.entry_og = 4 * c4; ta.entry_act_n = net->cs; ta.colsum = sc.colsum;
         ta.entry_split = h16 ? c4 : 0;  // (the last VortexPooling runs the chain flow: same rule as its `split`)
+#ifdef OJF_TAIL_STAMPS
+        if (h16 && tail_stamp_form() == ojf::kTailAtBranch)
+            hipLaunchKernelGGL((vortex_tail_kernel<OJF_ARITH_F16X3, 1, 2, 8, kTailEntry, ojf::kTailAtBranch>), grid, block, 0, st, ta);
+        else
+#endif
         OJF_LAUNCH_BY_ARITH(vortex_tail_kernel, ta, 1, 2, 8, kTailEntry);
         break;
     default:  // TAIL_ALONE
@@ -3938,10 +4014,114 @@ OJF_API int ojf_entry_gemm(const float *weight, const float *bias, int c_in_phys
     return rc;
 }
 
+OJF_API int ojf_vortex_tail(int kind, const float *w1, const float *b1, const float *wf, const float *bf, int c, int c_out,
+                            const float *next_w, const float *next_b, const int *next_dims, const float *v, int c4, int npix,
+                            float *out, int og_store, int split_groups, int act_n, void *colsums, int rows_stride, int rows_n,
+                            float scale, int form, ojf_stream_t stream)
+{
+    using namespace ojf;
+    constexpr int NV = 2, NO = 8, A = OJF_ARITH_F16X3;
+    static const int head_tiles[12] = {8, 6, 6, 5, 5, 4, 4, 3, 3, 2, 2, 1};  // head_run's growth-19 topology
+    if (!w1 || !b1 || !wf || !bf || !next_w || !next_b || !next_dims || !v || !out) return fail("ojf_vortex_tail: null pointer argument");
+    if (kind != kTailEntry && kind != 19) return fail("ojf_vortex_tail: kind must be 1 (+ entry GEMM) or 19 (+ prediction head)");
+    if (kind == kTailEntry && !colsums) return fail("ojf_vortex_tail: null pointer argument (colsums)");
+    if (c < 1 || c > 16 * NV || c_out < 1 || (c_out + 15) / 16 != NO || c4 < 1 || c4 > 4 * NV || 4 * c4 < c)
+        return fail("ojf_vortex_tail: the fused tail takes up to 32 branch channels in c4 groups and 113..128 output channels");
+    if (npix < 1 || npix > (1 << 24) || (form != 0 && form != 1)) return fail("ojf_vortex_tail: bad sizes");
+    if (kind == kTailEntry) {
+        const int cs = next_dims[0];
+        if (cs < 4 || cs > 20 || cs % 4 || og_store < 0 || og_store > cs || split_groups < 0 || split_groups > cs || act_n < 0)
+            return fail("ojf_vortex_tail: bad entry layer sizes");
+    } else {
+        if (next_dims[0] != c_out) return fail("ojf_vortex_tail: the head's first layer reads the tail's channels");
+        for (int l = 0; l < 12; ++l)
+            if (next_dims[l] < 1 || (round_up(next_dims[l], 4) + 15) / 16 != head_tiles[l])
+                return fail("ojf_vortex_tail: the head's channel counts do not fit the 8-6-6-5-5-4-4-3-3-2-2-1 tile chain");
+        if (rows_n < 1 || rows_n > next_dims[11] || rows_stride < rows_n) return fail("ojf_vortex_tail: bad row sizes");
+    }
+    hipStream_t st = as_stream(stream);
+    // packed as build_vortex packs the net's: [W1_b | Wf_b] fragments per branch, one common row scale for the four column blocks
+    std::vector<float> tw, tb, nw, nb, bfin((size_t)NO * 16, 0.0f);
+    const std::vector<float> rf = chain_row_scales(A, NO, 4 * c_out, [&](int oc, int k) { return oc < c_out ? wf[(size_t)oc * 4 * c_out + k] : 0.0f; });
+    for (int br = 0; br < 4; ++br) {
+        auto wb = [&](int oc, int k) { return oc < c_out && k < c ? w1[((size_t)br * c_out + oc) * c + k] : 0.0f; };
+        const std::vector<float> r1 = chain_row_scales(A, NO, c, wb);
+        pack_chain_layer(tw, A, NO, NV, r1, wb);
+        pack_chain_layer(tw, A, NO, NO, rf, [&](int oc, int k) { return oc < c_out && k < c_out ? wf[(size_t)oc * 4 * c_out + (size_t)c_out * br + k] : 0.0f; });
+        append_chain_bias(tb, A, NO, c_out, b1 + (size_t)br * c_out, r1);
+    }
+    std::vector<float> rfi(rf.size());
+    for (size_t i = 0; i < rf.size(); ++i) rfi[i] = 1.0f / rf[i];
+    for (int o = 0; o < c_out; ++o) bfin[o] = bf[o];
+    if (kind == kTailEntry) {
+        const int cs = next_dims[0];
+        auto we = [&](int oc, int k) { return oc < 4 * cs && k < c_out ? next_w[(size_t)oc * c_out + k] : 0.0f; };
+        const std::vector<float> re = chain_row_scales(A, 5, c_out, we);
+        pack_chain_layer(nw, A, 5, 8, re, we);
+        append_chain_bias(nb, A, 5, 4 * cs, next_b, re);
+    } else {
+        const float *wl0 = next_w, *bl0 = next_b;
+        for (int l = 0; l < 11; ++l) {
+            const int ci = next_dims[l], co = next_dims[l + 1];
+            auto wl = [&](int oc, int k) { return oc < co && k < ci ? wl0[(size_t)oc * ci + k] : 0.0f; };
+            const std::vector<float> rs = chain_row_scales(A, head_tiles[l + 1], ci, wl);
+            pack_chain_layer(nw, A, head_tiles[l + 1], head_tiles[l], rs, wl);
+            append_chain_bias(nb, A, head_tiles[l + 1], co, bl0, rs);
+            wl0 += (size_t)co * ci;
+            bl0 += co;
+        }
+    }
+    float *dtw = nullptr, *dtb = nullptr, *dnw = nullptr, *dnb = nullptr, *dbf = nullptr, *dri = nullptr;
+    int rc = upload(tw, &dtw);
+    if (!rc) rc = upload(tb, &dtb);
+    if (!rc) rc = upload(nw, &dnw);
+    if (!rc) rc = upload(nb, &dnb);
+    if (!rc) rc = upload(bfin, &dbf);
+    if (!rc) rc = upload(rfi, &dri);
+    if (!rc) {
+        TailArgs ta;
+        for (int br = 0; br < 4; ++br) ta.v[br] = planes(v) + (size_t)br * c4 * npix;
+        ta.w = planes(dtw); ta.b1 = dtb; ta.bias_final = dbf; ta.rinv_final = dri;
+        ta.out = nullptr; ta.c4 = c4; ta.out_g0 = 0; ta.og_store = 0; ta.npix = npix;
+        ta.ovf = overflow_flag();
+        ta.chain_w = nullptr; ta.chain_b = nullptr; ta.out_rows = nullptr; ta.rows_stride = 0; ta.rows_n = 0; ta.scale = 1.0f;
+        ta.entry_w = nullptr; ta.entry_b = nullptr; ta.entry_out = nullptr; ta.entry_og = 0; ta.entry_act_n = 0; ta.colsum = nullptr; ta.entry_split = 0;
+        const dim3 grid(((npix + 15) / 16 + kChainWaves - 1) / kChainWaves), block(kChainThreads);
+        if (kind == kTailEntry) {
+            ta.entry_w = planes(dnw); ta.entry_b = dnb; ta.entry_out = planes(out);
+            ta.entry_og = og_store; ta.entry_act_n = act_n; ta.colsum = static_cast<ColSums *>(colsums); ta.entry_split = split_groups;
+            if (form == 1) hipLaunchKernelGGL((vortex_tail_kernel<A, 1, NV, NO, kTailEntry>), grid, block, 0, st, ta);
+            else hipLaunchKernelGGL((vortex_tail_kernel<A, 1, NV, NO, kTailEntry, kTailAtBranch>), grid, block, 0, st, ta);
+        } else {
+            ta.chain_w = planes(dnw); ta.chain_b = dnb; ta.out_rows = out; ta.rows_stride = rows_stride; ta.rows_n = rows_n; ta.scale = scale;
+            if (form == 1) hipLaunchKernelGGL((vortex_tail_kernel<A, 1, NV, NO, 19>), grid, block, 0, st, ta);
+            else hipLaunchKernelGGL((vortex_tail_kernel<A, 1, NV, NO, 19, kTailAtBranch>), grid, block, 0, st, ta);
+        }
+        rc = check_hip(hipGetLastError(), "ojf_vortex_tail launch");
+        if (!rc) rc = check_hip(hipStreamSynchronize(st), "ojf_vortex_tail sync");  // test-only API: packs per call
+    }
+    for (float *d : {dtw, dtb, dnw, dnb, dbf, dri})
+        if (d) (void)hipFree(d);
+    return rc;
+}
+
 #ifdef OJF_POOL_STAMPS
 extern "C" __attribute__((visibility("default"))) int ojf_debug_pool_stamps(void *host_dst, size_t bytes)
 {
     return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(ojf::g_pool_stamps), bytes < sizeof(ojf::g_pool_stamps) ? bytes : sizeof(ojf::g_pool_stamps));
+}
+#endif
+
+#ifdef OJF_TAIL_STAMPS
+extern "C" __attribute__((visibility("default"))) int ojf_debug_tail_stamps(void *host_dst, size_t bytes)
+{
+    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(ojf::g_tail_stamps), bytes < sizeof(ojf::g_tail_stamps) ? bytes : sizeof(ojf::g_tail_stamps));
+}
+extern "C" __attribute__((visibility("default"))) int ojf_debug_tail_form(int form)  // 0 requests at each branch's head, 1 one branch ahead (the product)
+{
+    if (form < 0 || form > 1) return -1;
+    ojf::g_tail_stamp_form = form;
+    return 0;
 }
 #endif
 
